@@ -2,7 +2,7 @@
 """bench.py — headline benchmark: streaming 4096-tap FIR convolution
 (bench_conv1d_accel) x 1024 channels x 512-sample buffers @ 48 kHz on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over the resident batch of synthetic input:
 BUFFERS_PER_STEP = 128 consecutive audio buffers (512 new samples for every one of a
@@ -20,18 +20,24 @@ sent as per-rank rows), each rank transforms its slice; there is no per-buffer c
 independent), so scaling is weak.  A plain `python bench.py --gpus N` starts the N
 ranks itself (torch.distributed.run) before touching any GPU and relays rank 0's line.
 
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can
+measure or check runs only under --full (the fields it fills are marked (full) below, and are
+None or absent without it).  --dump-outputs DIR writes what the last timed launch computed as
+float32 .npy files (dump_outputs()); the inputs are seeded, so two builds compare file for file.
+
 One JSON line on rank 0:
   value          = 1024-channel buffers per second, whole job (N * 128 K / max-rank time)
+  ms_per_step    = wall-clock milliseconds of one timed step (one launch of 128 buffers)
   roofline       = algorithmic bytes per launch / average launch duration (HIP events on the
                    launch stream over the timed region), against 8 TB/s HBM
-  parity_checked = after the timed region: sampled channels of the last step's first and last
+  parity_checked = (full) after the timed region: sampled channels of the last step's first and last
                    buffer against the float64 direct form (the CPU oracle); mismatch => exit 1
-  round_trip     = (config) p50 / p95 of one buffer pinned host -> GPU -> pinned host through gab_conv_round_trip
+  round_trip     = (full, config) p50 / p95 of one buffer pinned host -> GPU -> pinned host through gab_conv_round_trip
                    (returns on the launch's own completion event), against the link floor measured in the same run
-  one_buffer_per_doorbell = (config) the resident engine: pipelined rate, and under in_flight_1 the time from doorbell
+  one_buffer_per_doorbell = (full, config) the resident engine: pipelined rate, and under in_flight_1 the time from doorbell
                    to `completed` with ONE buffer in flight (the reference's iteration), back to back and paced
   a bit-identity flag of either leg that is False => exit 1
-  cpu_baseline   = the CPU oracle (the reference golden extended with history), timed on a
+  cpu_baseline   = (full) the CPU oracle (the reference golden extended with history), timed on a
                    bounded sample of the same workload on this box's cores (N = 1 only)
 """
 import argparse
@@ -55,6 +61,9 @@ HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
 PARITY_CHANNELS = 16            # sampled per checked buffer
 PARITY_TOL = 1e-5               # of the stream's peak (north_star: 1e-5 relative for float DSP)
 TRAFFIC_SOURCE = "profiles/r06_conv_batch_pmc_means.json"
+DUMP_CHANNELS = 64              # --dump-outputs: channels sampled from every buffer of the last step
+DUMP_SAMPLE_BYTES = 48 << 20    # ... fewer for a longer step, so that the files stay under 64 MB in all
+DUMP_SEED = 7
 
 
 def cpu_threads():
@@ -163,19 +172,27 @@ def dry_run(args, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="timed steps of %d buffers each" % BUFFERS_PER_STEP)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps of %d buffers each (>= 1)" % BUFFERS_PER_STEP)
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps (besides the fixed clock warm-up)")
     ap.add_argument("--buffers-per-step", type=int, default=BUFFERS_PER_STEP, help="buffers per launch (>= 9)")
     ap.add_argument("--clock-warm-steps", type=int, default=CLOCK_WARM_STEPS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-legs", action="store_true", help="only the timed region (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the in-run parity check against the CPU oracle, the power sample, "
+                         "the side legs (one launch per buffer, the doorbell engine, the round trips), the CPU baseline and "
+                         "the rocFFT yardstick; the --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: no power sample, side legs or yardstick")
     ap.add_argument("--batch-sizes", action="store_true",
-                    help="also time 8 / 16 / 32 buffers per launch (off by default: those launches carry the headline "
+                    help="with --full: also time 8 / 16 / 32 buffers per launch (off by default: those launches carry the headline "
                          "kernel's name and would mix into a profiler's per-kernel average of the 128-buffer launches)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     ap.add_argument("--ir-distribution", choices=("broadcast", "slices"), default="broadcast",
                     help="N > 1: every rank receives the whole impulse-response bank (north_star's RCCL broadcast) or only its rows")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])
@@ -275,13 +292,16 @@ def main():
         elapsed = float(t.item())
     wall_us = elapsed * 1e6 / n_buffers
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, yb, NB, B, T, np, torch)
+
     # ---- in-run parity: the timed launches' own output against the float64 direct form --------
-    parity = parity_check(plan, host_in, yb, ir_dev, T, B, L, NB, np, torch) if rank == 0 else None
+    parity = parity_check(plan, host_in, yb, ir_dev, T, B, L, NB, np, torch) if rank == 0 and args.full else None
 
     alg = algorithmic_bytes(T, B, L)
     side = {}
     power_state = None
-    if not args.no_side_legs and world == 1:           # the one-GPU real-time path: reported at N = 1 only
+    if args.full and not args.no_side_legs and world == 1:      # the one-GPU real-time path: reported at N = 1 only
         power_state = power_state_under_load(run_steps, torch)
         side = side_legs(gab, plan, ir_dev, host_in, xb, stream, dev, T, B, L, np, torch, args.batch_sizes)
 
@@ -371,7 +391,7 @@ def main():
     result["config"].update(side)
 
     # ---- CPU baseline: the oracle on this box's cores, bounded sample (rank 0, N = 1) ----
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, ir_dev, host_in, T, B, L, np)
     elif rank == 0:
         result["cpu_baseline"] = None
@@ -379,7 +399,7 @@ def main():
     plan.close()
     # ---- library yardstick (tools only, a child process; never on the product path): the
     # reference's pipeline on rocFFT, same GPU, same shape (tools/ubench/library_baseline.cpp)
-    if world == 1 and rank == 0 and not args.no_side_legs:
+    if args.full and world == 1 and rank == 0 and not args.no_side_legs:
         result["library_baseline"] = library_baseline(T, B, L)
     if rank == 0:
         print(json.dumps(result), flush=True)
@@ -424,6 +444,31 @@ def parity_check(plan, host_in, yb, ir_dev, T, B, L, NB, np, torch):
     return {"channels": int(len(chans)), "buffers": "first and last buffer of the last timed step",
             "against": "oracle orc_conv_accel_stream_f64 (float64 direct form) fed the 9 input blocks each output depends on",
             "max_err_of_peak": err, "tolerance": PARITY_TOL, "ok": bool(err <= PARITY_TOL and peak > 0)}
+
+
+def dump_channels(T, NB, B):
+    """The channels --dump-outputs samples from every buffer of the last step: DUMP_CHANNELS of them (fewer for a
+    step longer than 192 buffers), drawn with a fixed seed, ascending."""
+    import numpy as np
+    n = max(1, min(DUMP_CHANNELS, T, DUMP_SAMPLE_BYTES // (4 * NB * B)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(T, size=n, replace=False))
+
+
+def dump_outputs(path, yb, NB, B, T, np, torch):
+    """--dump-outputs: what the last timed launch wrote, the sample-major [NB][B][T] output a caller of
+    gab_conv_process_batch receives, as float32 .npy files under `path`:
+      output_first_buffer.npy      [B][T]  the step's first buffer whole (its window reaches into the previous launch)
+      output_last_buffer.npy       [B][T]  the step's last buffer whole
+      output_sampled_channels.npy  [NB][B][C]  the dump_channels() channels of every buffer of the step
+    20 MiB at the default shape.  The inputs and the bank are seeded and every step processes the same buffers, so
+    the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    out = yb.view(NB, B, T)
+    chans = torch.from_numpy(dump_channels(T, NB, B)).to(yb.device)
+    arrays = {"output_first_buffer": out[0], "output_last_buffer": out[NB - 1],
+              "output_sampled_channels": out.index_select(2, chans)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy().astype(np.float32))
 
 
 def library_baseline(T, B, L):

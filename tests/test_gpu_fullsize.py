@@ -430,7 +430,7 @@ def test_bench_under_a_launcher_walks_the_rccl_path_on_one_gpu(ranks, distributi
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                         "--gpus", str(ranks), "--steps", "3", "--warmup", "1", "--clock-warm-steps", "5",
-                        "--no-side-legs", "--no-cpu-baseline", "--ir-distribution", distribution],
+                        "--full", "--no-side-legs", "--no-cpu-baseline", "--ir-distribution", distribution],
                        capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
@@ -443,3 +443,43 @@ def test_bench_under_a_launcher_walks_the_rccl_path_on_one_gpu(ranks, distributi
     assert len(pr["us_per_buffer"]) == ranks and all(v > 0 for v in pr["us_per_buffer"]) and len(pr["ir_broadcast_ms"]) == ranks
     bank = 4 * 4096 * 1024 * ranks
     assert pr["ir_bytes_received"] == ([0] if ranks == 1 else [0, bank if distribution == "broadcast" else bank // 2])
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(orc, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline fields and
+    none of the legs --full adds; DIR holds the last timed launch's output as float32 .npy files (its first and last
+    buffer whole, seeded channels of every buffer), under 64 MB, whose sampled channels match the oracle's float64
+    direct form fed the 9 input blocks each output depends on."""
+    import json, subprocess, sys
+    import bench
+    from gpuaudiobench_amd import harness
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    NB, T, B, L = 16, 1024, 512, 4096
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--clock-warm-steps", "5", "--buffers-per-step", str(NB), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1])
+    assert d["metric"] == "audio_buffers_per_sec" and d["unit"] == "buffers/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["parity_checked"] is None and d["cpu_baseline"] is None and "library_baseline" not in d
+    assert d["config"]["power_state"] is None and "round_trip" not in d["config"]
+
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["output_first_buffer.npy", "output_last_buffer.npy", "output_sampled_channels.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 << 20
+    first, last, sampled = (np.load(os.path.join(tmp_path, f)) for f in files)
+    chans = bench.dump_channels(T, NB, B)
+    assert first.dtype == last.dtype == sampled.dtype == np.float32
+    assert first.shape == last.shape == (B, T) and sampled.shape == (NB, B, len(chans))
+    assert np.array_equal(bits(sampled[0]), bits(first[:, chans])) and np.array_equal(bits(sampled[-1]), bits(last[:, chans]))
+
+    check = chans[:16]
+    ir = harness.conv_accel_ir(L, T).reshape(T, L)[check]
+    xs = [harness.noise(T * B, seed=42 + i).reshape(T, B) for i in range(NB)]
+    for n, got in ((NB - 1, sampled[NB - 1][:, :16]), (0, sampled[0][:, :16])):
+        hist = np.zeros(len(check) * L, np.float32)
+        for k in range(n - L // B, n + 1):
+            ref = orc.conv_accel_stream(np.ascontiguousarray(xs[k % NB][check]).ravel(), ir.ravel(), hist, L, B,
+                                        len(check), f64=True).reshape(B, len(check))
+        assert np.abs(got - ref).max() <= TOL * np.abs(ref).max(), n

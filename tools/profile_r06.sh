@@ -10,9 +10,9 @@ TAG=${1:-r06}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-DRIVER="python3 bench.py --steps 20 --warmup 5"                                  # the driver's command, as it is
+DRIVER="python3 bench.py --steps 20 --warmup 5 --full"                           # the driver's command with every leg
 BENCH="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-side-legs"  # the same launches without the CPU legs (PMC passes)
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line_steps20_warmup5.json 2> $OUT/bench.err; echo "untraced bench rc=$?"
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_line_steps20_warmup5.json 2> $OUT/bench.err; echo "untraced bench rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench -- $DRIVER > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_rocprof.err; echo "trace rc=$?"
 for C in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS" "SQ_WAIT_ANY SQ_WAVES SQ_ACTIVE_INST_ANY"; do
   N=$(echo $C | tr ' ' '_')
