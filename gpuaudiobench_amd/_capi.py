@@ -20,6 +20,7 @@ CONV_STREAMING = 1
 CONV_STREAMING_HOST_IO = 2
 CONV_SCHEME_CLASSIC = 0
 CONV_SCHEME_SPLIT = 1
+CONV_SCHEME_FDL = 2
 DWG_NAIVE = 0
 DWG_ACCEL = 1
 
@@ -45,7 +46,7 @@ class FdtdParams(C.Structure):
 
 class BenchConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
-        "fs", "buffer_size", "n_tracks", "n_runs", "ir_length", "fdtd_grid", "conv_mode", "quiet", "modal_mode", "conv_batch", "fdtd_form", "datacopy_mode")]
+        "fs", "buffer_size", "n_tracks", "n_runs", "ir_length", "fdtd_grid", "conv_mode", "quiet", "modal_mode", "conv_batch", "fdtd_form", "datacopy_mode", "conv_scheme")]
 
 
 class BenchResult(C.Structure):
@@ -100,6 +101,7 @@ PROTOTYPES = {
     "gab_dwg": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "gab_fft_r2c_1024": (_I, [_P, _P, _I, _P]),
     "gab_conv_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_conv_create_scheme": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
     "gab_conv_destroy": (_I, [_P]),
     "gab_conv_set_ir": (_I, [_P, _P, _P]),
     "gab_conv_reset": (_I, [_P, _P]),

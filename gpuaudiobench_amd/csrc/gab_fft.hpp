@@ -614,8 +614,31 @@ struct WaveFFT1024 {
     }
 };
 
+// Partner exchange: every thread publishes its R bins (k = tid + r*N/R) and
+// fetches conj(Z[(N-k) mod N]).  Threads beyond N/R only meet the barrier.
+template <int N, int R, bool RAW = false>
+__device__ __forceinline__ void partner_exchange(const cf (&z)[R], cf (&zp)[R],
+                                                 cf* __restrict__ lds, int tid, bool active = true) {
+    constexpr int NT = N / R;
+    if (active) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) lds[tid + r * NT] = z[r];
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int k = tid + r * NT;
+            cf v = lds[(N - k) & (N - 1)];
+            zp[r] = RAW ? v : conj(v);      // RAW: the caller folds the conjugate into its product
+        }
+    }
+}
+
 // Host: fill the float64-accurate twiddle table (kTwiddleN complex floats).
 void build_twiddles(float* table_xy);
+// The table of the current device (kTwiddleN entries): made at its first use, kept for the process.
+const cf* device_twiddles();
 
 }  // namespace fft
 }  // namespace gab

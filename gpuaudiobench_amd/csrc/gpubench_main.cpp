@@ -45,6 +45,8 @@ void printHelp() {
     printf("                      iteration's upload, kernel and download overlapped in one call: gab_conv_round_trip)\n");
     printf("  --convBatch [n]     Conv1D_accel: an iteration is ONE launch over n HBM-resident buffers (throughput mode,\n");
     printf("                      no per-iteration copies); default: one buffer per iteration with its copies\n");
+    printf("  --convScheme [s]    Conv1D_accel: default (the library's routing for the shape) | fdl (long impulse responses:\n");
+    printf("                      partitioned overlap-save with a frequency-domain delay line; not with --convMode roundtrip)\n");
     printf("  --gpus [n]          Run on n devices, one host thread each: gain, GainStats, IIRFilter, FFT1D, RndMemRead, Conv1D\n");
     printf("                      and Conv1D_accel as contiguous channel shards of --nTracks (Conv1D_accel's impulse-response\n");
     printf("                      bank broadcast once over RCCL; Conv1D with its halo rows; RndMemRead with the pool on every\n");
@@ -299,6 +301,13 @@ int main(int argc, char** argv) {
             if (!need("--convBatch")) return 1;
             CONV_BATCH = atoi(argv[++i]);
             if (CONV_BATCH < 1) { printf("Error: --convBatch must be >= 1\n"); return 1; }
+        }
+        else if (strcmp(argv[i], "--convScheme") == 0) {
+            if (!need("--convScheme")) return 1;
+            const char* m = argv[++i];
+            if (strcmp(m, "fdl") == 0) CONV_SCHEME = 2;
+            else if (strcmp(m, "default") == 0) CONV_SCHEME = 0;
+            else { printf("Error: --convScheme takes default or fdl\n"); return 1; }
         }
         else if (strcmp(argv[i], "--convMode") == 0) {
             if (!need("--convMode")) return 1;

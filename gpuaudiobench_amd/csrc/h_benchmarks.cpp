@@ -588,7 +588,8 @@ Conv1DAccelBenchmark::Conv1DAccelBenchmark(int ir_length, size_t buffer_size, si
       track_offset_(track_offset),
       total_tracks_(total_tracks ? total_tracks : track_count),
       round_trip_(CONV_STREAMING == 2),
-      batch_(CONV_BATCH > 1 ? CONV_BATCH : 0) {
+      batch_(CONV_BATCH > 1 ? CONV_BATCH : 0),
+      scheme_(CONV_SCHEME) {
     if (ir_length <= 0) throw std::invalid_argument("Conv1DAccelBenchmark: ir_length must be > 0");
     say("Conv1DAccelBenchmark: IR length = %d, FFT size = %d\n", ir_length_, fft_size_);
     ir_buffer_size = track_count * ir_length;
@@ -611,8 +612,17 @@ void Conv1DAccelBenchmark::setupBenchmark() {
     h_ir_buf = allocateHostBuffer<float>(ir_buffer_size, "conv1d_accel host IR buffer");
     d_ir_buf = allocateDeviceBuffer<float>(ir_buffer_size, "conv1d_accel device IR buffer");
     cpu_reference = allocateHostBuffer<float>(getTotalElements(), "conv1d_accel cpu reference");
-    checkGab(gab_conv_create(&plan_, static_cast<int>(getTrackCount()), static_cast<int>(getBufferSize()),
-                             ir_length_), "gab_conv_create");
+    if (scheme_ == GAB_CONV_SCHEME_FDL) {
+        if (round_trip_)
+            throw std::invalid_argument("Conv1DAccelBenchmark: --convMode roundtrip does not run the fdl scheme (it has no round-trip form)");
+        checkGab(gab_conv_create_scheme(&plan_, static_cast<int>(getTrackCount()), static_cast<int>(getBufferSize()),
+                                        ir_length_, scheme_), "gab_conv_create_scheme");
+    } else if (scheme_ != 0) {
+        throw std::invalid_argument("Conv1DAccelBenchmark: the plan scheme is 0 (the default routing) or 2 (the fdl scheme)");
+    } else {
+        checkGab(gab_conv_create(&plan_, static_cast<int>(getTrackCount()), static_cast<int>(getBufferSize()),
+                                 ir_length_), "gab_conv_create");
+    }
     if (round_trip_) {
         if (mode_ != Mode::STREAMING || batch_ > 1)
             throw std::invalid_argument("Conv1DAccelBenchmark: --convMode roundtrip is the streaming mode, one buffer per iteration");

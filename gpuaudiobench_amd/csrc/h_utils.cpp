@@ -29,6 +29,7 @@ int FDTD_GRID = 0;
 int CONV_STREAMING = 1;
 int MODAL_REAL = 0;
 int CONV_BATCH = 0;
+int CONV_SCHEME = 0;
 int FDTD_STEPS = 0;
 int FDTD_FORM = 0;
 int DATACOPY_SEQUENTIAL = 0;

@@ -46,6 +46,7 @@
 
 #include "gab_common.hpp"
 #include "gab_fft.hpp"
+#include "k_conv_fdl.hpp"
 
 namespace gab {
 namespace fft {
@@ -95,26 +96,7 @@ constexpr int kThreads = 256;
 using PadB = fft::Pad<16>;
 constexpr int kLdsHalf = PadB::size(kNB);       // cf entries per LDS buffer
 
-// Partner exchange: every thread publishes its R bins (k = tid + r*N/R) and
-// fetches conj(Z[(N-k) mod N]).  Threads beyond N/R only meet the barrier.
-template <int N, int R, bool RAW = false>
-__device__ __forceinline__ void partner_exchange(const cf (&z)[R], cf (&zp)[R],
-                                                 cf* __restrict__ lds, int tid, bool active = true) {
-    constexpr int NT = N / R;
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) lds[tid + r * NT] = z[r];
-    }
-    __syncthreads();
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int k = tid + r * NT;
-            cf v = lds[(N - k) & (N - 1)];
-            zp[r] = RAW ? v : fft::conj(v);      // RAW: the caller folds the conjugate into its product
-        }
-    }
-}
+using fft::partner_exchange;      // (gab_fft.hpp: shared with k_conv_fdl.hip)
 
 // The bank stores k <= N/2 only; the upper half is the conjugate (P and M come
 // from Hermitian spectra).  Loads are split from the arithmetic so a caller can
@@ -2532,6 +2514,8 @@ struct gab_conv_plan {
     unsigned upos = 0;
     float4* pmU = nullptr;
     gab::fft::cf* ring = nullptr;
+    // the fdl scheme (k_conv_fdl.hip, gab_conv_create_scheme): a plan of its own kind; every supported entry hands it on
+    gab::fdl::Plan* fdl = nullptr;
     // Ordering between gab_conv_reset (memsets on the caller's stream) and launches on OTHER streams
     // (channel ranges): the reset waits for every stream that launched since the previous reset, and
     // a stream's first launch after a reset waits for the reset's event.
@@ -2625,6 +2609,53 @@ int gab_conv_create(gab_conv_plan** out, int tracks, int bufsize, int ir_len) {
     });
 }
 
+int gab_conv_create_scheme(gab_conv_plan** out, int tracks, int bufsize, int ir_len, int scheme) {
+    return gab::guarded([&]() -> int {
+        if (!out) return gab::bad_arg("gab_conv_create_scheme: null plan pointer");
+        if (scheme == GAB_CONV_SCHEME_CLASSIC || scheme == GAB_CONV_SCHEME_SPLIT) {
+            if (int rc = gab_conv_create(out, tracks, bufsize, ir_len)) return rc;
+            if (int rc = gab_conv_set_scheme(*out, scheme)) {
+                const std::string why = gab::last_error();
+                gab_conv_destroy(*out);
+                *out = nullptr;
+                gab::set_last_error(why);
+                return rc;
+            }
+            return GAB_OK;
+        }
+        if (scheme != GAB_CONV_SCHEME_FDL) return gab::bad_arg("gab_conv_create_scheme: unknown scheme (0 classic, 1 split, 2 fdl)");
+        if (tracks < 1) return gab::bad_arg("gab_conv_create_scheme: the fdl scheme needs tracks >= 1");
+        if (bufsize < 128 || bufsize > 2048 || (bufsize & (bufsize - 1)) != 0)
+            return gab::bad_arg("gab_conv_create_scheme: the fdl scheme needs a power-of-two buffer size from 128 to 2048");
+        if (ir_len < 1 || ir_len > (1 << 21))
+            return gab::bad_arg("gab_conv_create_scheme: the fdl scheme needs 1 <= ir_len <= 2097152");
+        if (int rc = gab::refuse_unsupported_runtime_mode("gab_conv_create_scheme")) return rc;
+        auto* p = new gab_conv_plan;
+        p->tracks = tracks; p->bufsize = bufsize; p->ir_len = ir_len;
+        p->pairs = (tracks + 1) / 2;
+        try {
+            GAB_HIP_CHECK(hipGetDevice(&p->device));
+            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->reset_ev, hipEventDisableTiming));
+            p->fdl = gab::fdl::create(tracks, bufsize, ir_len);
+        } catch (...) {
+            gab_conv_destroy(p);
+            throw;
+        }
+        gab::resident_add(p, p->device, gab::kResidentEngine,
+                          [](const void* o) { return static_cast<const gab_conv_plan*>(o)->eng_running; });
+        *out = p;
+        return GAB_OK;
+    });
+}
+
+// Entries a plan of the fdl scheme has no form of: refused, the plan stays usable.
+static int gab_conv_refuse_fdl(const gab_conv_plan* p, const char* who) {
+    if (!p || !p->fdl) return GAB_OK;
+    gab::set_last_error(std::string(who) + ": not on a plan of the fdl scheme (it has no round-trip, newest-block or engine form; "
+                        "use gab_conv_process / gab_conv_process_batch)");
+    return GAB_ERR_INVALID_ARG;
+}
+
 int gab_conv_destroy(gab_conv_plan* p) {
     if (!p) return GAB_OK;
     gab::resident_remove(p);
@@ -2645,6 +2676,7 @@ int gab_conv_destroy(gab_conv_plan* p) {
     if (p->carry) (void)hipFree(p->carry);
     if (p->pmU) (void)hipFree(p->pmU);
     if (p->ring) (void)hipFree(p->ring);
+    if (p->fdl) gab::fdl::destroy(p->fdl);
     if (p->reset_ev) (void)hipEventDestroy(p->reset_ev);
     if (p->rt_stage) (void)hipFree(p->rt_stage);
     if (p->rt_park) (void)hipFree(p->rt_park);
@@ -2671,7 +2703,9 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
         if (!p || !d_ir) return gab::bad_arg("gab_conv_set_ir: null argument");
         if (p->eng_running) return gab::bad_arg("gab_conv_set_ir: the plan's engine is running (gab_conv_engine_stop first)");
         hipStream_t s = gab::as_stream(stream);
-        if (p->uniform) {
+        if (p->fdl) {
+            gab::fdl::set_ir(p->fdl, d_ir, s);                  // every partition in one launch
+        } else if (p->uniform) {
             for (int j = 0; j < p->uJ; ++j)
                 gab::conv_ir_spectra_uniform_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
                     d_ir, p->pmU + (size_t)j * p->pairs * gab::kBinsB, p->tw, p->tracks, p->ir_len,
@@ -2699,6 +2733,12 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
 
 int gab_conv_set_scheme(gab_conv_plan* p, int scheme) {
     if (!p) return gab::bad_arg("gab_conv_set_scheme: null plan");
+    if (p->fdl) {
+        if (scheme == GAB_CONV_SCHEME_FDL) return GAB_OK;
+        return gab::bad_arg("gab_conv_set_scheme: a plan of the fdl scheme keeps it (create another plan for the classic or split cut)");
+    }
+    if (scheme == GAB_CONV_SCHEME_FDL)
+        return gab::bad_arg("gab_conv_set_scheme: the fdl scheme is chosen when the plan is created (gab_conv_create_scheme)");
     if (scheme != GAB_CONV_SCHEME_CLASSIC && scheme != GAB_CONV_SCHEME_SPLIT)
         return gab::bad_arg("gab_conv_set_scheme: unknown scheme");
     if (!p->fresh) return gab::bad_arg("gab_conv_set_scheme: only on a fresh plan (before the first buffer or right after a reset)");
@@ -2710,7 +2750,7 @@ int gab_conv_set_scheme(gab_conv_plan* p, int scheme) {
 
 int gab_conv_get_scheme(const gab_conv_plan* p, int* scheme) {
     if (!p || !scheme) return gab::bad_arg("gab_conv_get_scheme: null pointer");
-    *scheme = p->split ? GAB_CONV_SCHEME_SPLIT : GAB_CONV_SCHEME_CLASSIC;
+    *scheme = p->fdl ? GAB_CONV_SCHEME_FDL : p->split ? GAB_CONV_SCHEME_SPLIT : GAB_CONV_SCHEME_CLASSIC;
     return GAB_OK;
 }
 
@@ -2736,7 +2776,8 @@ int gab_conv_reset(gab_conv_plan* p, gab_stream_t stream) {
             p->used_streams.clear();
             p->ordered_streams.clear();
         }
-        if (p->uniform) GAB_HIP_CHECK(hipMemsetAsync(p->ring, 0, p->history_bytes, s));
+        if (p->fdl) gab::fdl::reset(p->fdl, s);
+        else if (p->uniform) GAB_HIP_CHECK(hipMemsetAsync(p->ring, 0, p->history_bytes, s));
         else GAB_HIP_CHECK(hipMemsetAsync(p->hist, 0, p->history_bytes, s));
         p->head = 0;
         p->upos = 0;
@@ -2763,6 +2804,11 @@ int gab_conv_process(gab_conv_plan* p, const float* d_in, float* d_out, int mode
         hipStream_t s = gab::as_stream(stream);
         const bool streaming = mode != GAB_CONV_STATELESS;
         if (streaming) p->order_after_reset(s);
+        if (p->fdl) {                                        // device or pinned host buffers: the same three launches
+            gab::fdl::process(p->fdl, d_in, d_out, streaming, s);
+            if (streaming) p->fresh = false;
+            return GAB_OK;
+        }
         if (p->uniform) {
             if (mode == GAB_CONV_STREAMING_HOST_IO) mode = GAB_CONV_STREAMING;      // same kernel, host pointers
             gab::ConvUniform u{p->pmU, p->ring, p->uJ, p->uS, p->ring_len - 1, p->upos};
@@ -2915,6 +2961,7 @@ static int gab_conv_round_trip_finish_check(gab_conv_plan* p, int b, bool wait, 
 }
 
 int gab_conv_round_trip_check(gab_conv_plan* p) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_round_trip_check")) return rc;
     return gab::guarded([&]() -> int {
         if (!p) return gab::bad_arg("gab_conv_round_trip_check: null plan");
         const int r0 = gab_conv_round_trip_finish_check(p, 0, true, "gab_conv_round_trip_check");
@@ -2924,6 +2971,7 @@ int gab_conv_round_trip_check(gab_conv_plan* p) {
 }
 
 int gab_conv_round_trip_set_check(gab_conv_plan* p, int mode) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_round_trip_set_check")) return rc;
     if (!p) return gab::bad_arg("gab_conv_round_trip_set_check: null plan");
     if (mode < 0 || mode > 2) return gab::bad_arg("gab_conv_round_trip_set_check: 0 (ignore the verdict), 1 (read it at the next call / gab_conv_round_trip_check), 2 (read it in the call)");
     p->rt_check_mode = mode;
@@ -2931,6 +2979,7 @@ int gab_conv_round_trip_set_check(gab_conv_plan* p, int mode) {
 }
 
 int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_stream_t stream) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_round_trip")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !h_in || !h_out) return gab::bad_arg("gab_conv_round_trip: null argument");
         if (!p->ir_set) return gab::bad_arg("gab_conv_round_trip: gab_conv_set_ir has not been called");
@@ -3131,6 +3180,7 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
 }
 
 int gab_conv_round_trip_keep_warm(gab_conv_plan* p, int on) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_round_trip_keep_warm")) return rc;
     return gab::guarded([&]() -> int {
         if (!p) return gab::bad_arg("gab_conv_round_trip_keep_warm: null plan");
         if (on && !p->warm) {
@@ -3143,12 +3193,14 @@ int gab_conv_round_trip_keep_warm(gab_conv_plan* p, int on) {
 }
 
 int gab_conv_round_trip_keep_warm_placement(gab_conv_plan* p, unsigned* hw_id, unsigned* xcc_id, int capacity, int* started) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_round_trip_keep_warm_placement")) return rc;
     if (!p || !started) return gab::bad_arg("gab_conv_round_trip_keep_warm_placement: null argument");
     if (!p->warm) { *started = 0; return GAB_OK; }               // no keep-warm launch has been made for this plan
     return gab_keep_warm_placement(p->warm, hw_id, xcc_id, capacity, started);
 }
 
 int gab_conv_newest_block(gab_conv_plan* p, float* d_out, gab_stream_t stream) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_newest_block")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !d_out) return gab::bad_arg("gab_conv_newest_block: null argument");
         if (!p->fused || p->fresh) return gab::bad_arg("gab_conv_newest_block: a 512-sample plan that has taken at least one buffer");
@@ -3161,6 +3213,7 @@ int gab_conv_newest_block(gab_conv_plan* p, float* d_out, gab_stream_t stream) {
 
 // ---- the doorbell-fed engine ------------------------------------------------------------------------------------------
 int gab_conv_engine_rings(gab_conv_plan* p, int ring_buffers, float** d_in_ring, float** d_out_ring) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_rings")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !d_in_ring || !d_out_ring) return gab::bad_arg("gab_conv_engine_rings: null argument");
         if (!(p->fused && p->split)) return gab::bad_arg("gab_conv_engine_rings: the engine runs the split cut (512-sample buffers, 1025..4096 taps, channels divisible by 4)");
@@ -3191,6 +3244,7 @@ int gab_conv_engine_rings(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
 }
 
 int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring, float** d_out_ring, gab_stream_t stream) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_start")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !d_in_ring || !d_out_ring) return gab::bad_arg("gab_conv_engine_start: null argument");
         if (!p->ir_set) return gab::bad_arg("gab_conv_engine_start: gab_conv_set_ir has not been called");
@@ -3271,6 +3325,7 @@ int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
 }
 
 int gab_conv_engine_submit(gab_conv_plan* p, int n_more, int flush) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_submit")) return rc;
     if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_submit: no running engine");
     if (n_more < 0) return gab::bad_arg("gab_conv_engine_submit: negative count");
     if (p->eng_published + (unsigned)n_more >= 0x40000000u) return gab::bad_arg("gab_conv_engine_submit: more than 2^30 buffers in one launch (stop and start again)");
@@ -3283,6 +3338,7 @@ int gab_conv_engine_submit(gab_conv_plan* p, int n_more, int flush) {
 int gab_conv_engine_publish(gab_conv_plan* p, int n_more) { return gab_conv_engine_submit(p, n_more, 0); }
 
 int gab_conv_engine_running(gab_conv_plan* p, int* running) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_running")) return rc;
     if (!p || !running) return gab::bad_arg("gab_conv_engine_running: null argument");
     *running = 0;
     if (!p->eng_running) return GAB_OK;
@@ -3293,6 +3349,7 @@ int gab_conv_engine_running(gab_conv_plan* p, int* running) {
 }
 
 int gab_conv_engine_wait(gab_conv_plan* p, int count, double timeout_seconds) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_wait")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !p->eng_words) return gab::bad_arg("gab_conv_engine_wait: no engine");
         if (count < 0 || (unsigned)count > p->eng_published) return gab::bad_arg("gab_conv_engine_wait: count exceeds what has been published");
@@ -3331,6 +3388,7 @@ int gab_conv_engine_wait(gab_conv_plan* p, int count, double timeout_seconds) {
 }
 
 int gab_conv_engine_completed(gab_conv_plan* p, int* completed) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_completed")) return rc;
     if (!p || !completed || !p->eng_words) return gab::bad_arg("gab_conv_engine_completed: no engine");
     const unsigned c = __atomic_load_n(&p->eng_words[16], __ATOMIC_ACQUIRE);      // two writers may cross: keep the maximum seen
     if ((int)(c - p->eng_seen_completed) > 0) p->eng_seen_completed = c;
@@ -3339,6 +3397,7 @@ int gab_conv_engine_completed(gab_conv_plan* p, int* completed) {
 }
 
 int gab_conv_engine_feed(gab_conv_plan* p, int n_buffers, int ahead) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_feed")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_feed: no running engine");
         // a buffer is reported back once FIVE later ones are published (asked for a period early, delivered a period late,
@@ -3368,6 +3427,7 @@ int gab_conv_engine_feed(gab_conv_plan* p, int n_buffers, int ahead) {
 }
 
 int gab_conv_engine_feed_one_in_flight(gab_conv_plan* p, int n_buffers, float* latency_us) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_feed_one_in_flight")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_feed_one_in_flight: no running engine");
         if (n_buffers < 0) return gab::bad_arg("gab_conv_engine_feed_one_in_flight: negative count");
@@ -3383,6 +3443,7 @@ int gab_conv_engine_feed_one_in_flight(gab_conv_plan* p, int n_buffers, float* l
 }
 
 int gab_conv_engine_stop(gab_conv_plan* p) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_stop")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_stop: no running engine");
         __atomic_store_n(&p->eng_words[0], p->eng_published | 0x80000000u, __ATOMIC_RELEASE);
@@ -3413,6 +3474,7 @@ int gab_conv_engine_stop(gab_conv_plan* p) {
 }
 
 int gab_conv_engine_set_idle_limit(gab_conv_plan* p, double seconds) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_set_idle_limit")) return rc;
     if (!p) return gab::bad_arg("gab_conv_engine_set_idle_limit: null plan");
     if (!(seconds >= 0.5 && seconds <= 3600.0)) return gab::bad_arg("gab_conv_engine_set_idle_limit: 0.5 .. 3600 seconds");
     if (p->eng_running) return gab::bad_arg("gab_conv_engine_set_idle_limit: the plan's engine is running (it takes the limit at its start)");
@@ -3425,6 +3487,7 @@ int gab_conv_engine_set_idle_limit(gab_conv_plan* p, double seconds) {
 // link legs do not overlap with the transform (gab_conv_round_trip's do): this is the per-buffer engine as a complete
 // replacement of that iteration with a stated number, not the fastest round trip.
 int gab_conv_engine_round_trip(gab_conv_plan* p, const float* h_in, float* h_out) {
+    if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_round_trip")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !h_in || !h_out) return gab::bad_arg("gab_conv_engine_round_trip: null argument");
         if (!p->eng_running) return gab::bad_arg("gab_conv_engine_round_trip: no running engine (gab_conv_engine_start first)");
@@ -3470,6 +3533,12 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
         if (p->eng_running) return gab::bad_arg("gab_conv_process_batch: the plan's engine is running and owns its history (gab_conv_engine_stop first)");
         if (n_buffers <= 0) return gab::bad_arg("gab_conv_process_batch: n_buffers must be > 0");
         hipStream_t s = gab::as_stream(stream);
+        if (p->fdl) {
+            p->order_after_reset(s);
+            gab::fdl::process_batch(p->fdl, d_in, d_out, n_buffers, s);
+            p->fresh = false;
+            return GAB_OK;
+        }
         if (p->fused && (p->split || p->tail)) {
             // At most kBatchChunk buffers per launch.  Nothing holds the workgroups of a launch together, and the eight duos
             // whose 16-byte pieces make up one 128-byte output line must store within a period or two of each other — the
@@ -3547,6 +3616,10 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
 
 int gab_conv_state_bytes(const gab_conv_plan* p, size_t* spectra, size_t* history) {
     if (!p) return gab::bad_arg("gab_conv_state_bytes: null plan");
+    if (p->fdl) {                           // spectra: the taps' spectra; history: the delay line and the previous block
+        gab::fdl::state_bytes(p->fdl, spectra, history);
+        return GAB_OK;
+    }
     // everything resident for the plan: a plan that can use the split cut holds both sets of spectra
     // (classic for batch / host-io launches) and the carry ring beside the history ring
     const size_t bank = p->pmF ? sizeof(float4) * (size_t)p->pairs * (gab::kBinsA + gab::kBinsB) : 0;

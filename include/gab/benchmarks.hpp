@@ -263,6 +263,10 @@ public:
     // Streaming mode only; validate() checks the first buffer of a batch from reset against the golden.
     // Defaults to the CONV_BATCH global (--convBatch).
     void setBatch(int n_buffers) { batch_ = n_buffers > 1 ? n_buffers : 0; }
+    // The plan's scheme, from the CONV_SCHEME global (--convScheme, gab_bench_config::conv_scheme): 0 creates the plan
+    // with gab_conv_create (its routing by shape), GAB_CONV_SCHEME_FDL with gab_conv_create_scheme — long impulse
+    // responses, uniformly partitioned overlap-save with a frequency-domain delay line; every mode but the round trip.
+    int scheme() const { return scheme_; }
     int batch() const { return batch_; }
     int irLength() const { return ir_length_; }
     int fftSize() const { return fft_size_; }
@@ -283,6 +287,7 @@ private:
     gab_conv_plan* plan_ = nullptr;
     const float* d_shared_ir_ = nullptr;
     int batch_ = 0;
+    int scheme_ = 0;                  // 0: gab_conv_create's routing; 2: the fdl scheme (gab_conv_create_scheme)
     float* d_batch_in_ = nullptr;
     float* d_batch_out_ = nullptr;
     size_t ir_buffer_size;

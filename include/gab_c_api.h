@@ -223,6 +223,17 @@ typedef struct gab_conv_plan gab_conv_plan;
  * the far shares already parked for the next two buffers were made with the previous taps.       */
 #define GAB_CONV_SCHEME_CLASSIC 0
 #define GAB_CONV_SCHEME_SPLIT 1
+/* FDL: long impulse responses — uniformly partitioned overlap-save with a frequency-domain delay line
+ * (partition = the buffer, B; transform 2B; K = ceil(ir_len / B) partitions, one complex multiply-add per
+ * bin and partition per buffer).  Chosen at creation only, by gab_conv_create_scheme; gab_conv_create's
+ * routing is unchanged.  Shapes: bufsize a power of two from 128 to 2048, tracks >= 1 (an odd last channel
+ * is paired with a zero partner), 1 <= ir_len <= 2^21.  Supported: set_ir (every partition at once, also
+ * mid-stream: from the next buffer on the output is bit-identical to a plan that had the new taps from the
+ * start), reset, destroy, process (STATELESS / STREAMING / STREAMING_HOST_IO), process_batch (bit-identical
+ * to per-buffer calls), get_scheme, state_bytes (spectra: the taps' spectra; history: the delay line and the
+ * previous block; the plan's scratch — partial sums, a stateless call's spectrum — is not counted).  The round-trip, newest-block and engine entries, and set_scheme to another cut, refuse
+ * with GAB_ERR_INVALID_ARG and leave the plan usable.                                                 */
+#define GAB_CONV_SCHEME_FDL 2
 int gab_conv_set_scheme(gab_conv_plan* plan, int scheme);
 int gab_conv_get_scheme(const gab_conv_plan* plan, int* scheme);
 #define GAB_CONV_STREAMING_HOST_IO 2  /* the same, d_in / d_out in pinned host memory: identical kernel
@@ -232,6 +243,9 @@ int gab_conv_get_scheme(const gab_conv_plan* plan, int* scheme);
 /* allocateAccelBuffers + setupFFTPlans (:88-150).  Allocates the spectra bank
  * and the history ring on the current device.                                */
 int gab_conv_create(gab_conv_plan** plan, int tracks, int bufsize, int ir_len);
+/* gab_conv_create with the cut named: CLASSIC / SPLIT = gab_conv_create then gab_conv_set_scheme (same
+ * errors); FDL = a plan of that scheme.  Arguments are checked before any device call.                  */
+int gab_conv_create_scheme(gab_conv_plan** plan, int tracks, int bufsize, int ir_len, int scheme);
 int gab_conv_destroy(gab_conv_plan* plan);
 /* precomputeImpulseResponseFFTs (:175-228): d_ir is tracks x ir_len floats on
  * the device.  Synchronous with respect to `stream`.                         */
@@ -521,6 +535,8 @@ typedef struct {
     int    fdtd_form;       /* FDTD3D: GAB_FDTD_FORM_AUTO (0) | GAB_FDTD_FORM_STEP (1)              */
     int    datacopy_mode;   /* datacopy*: 0 upload and download at once (gab_datatransfer_round_trip)
                                | 1 H2D -> kernel -> D2H one after the other (the reference's schedule) */
+    int    conv_scheme;     /* Conv1D_accel: 0 gab_conv_create's routing (default) | 2 the fdl scheme
+                               (gab_conv_create_scheme; not with conv_mode 2, the round trip)          */
 } gab_bench_config;
 
 typedef struct {
