@@ -573,6 +573,46 @@ __global__ __launch_bounds__(kThreads, 2) void conv_split_host_io_kernel(
     conv_split_buffer(in, out, hist, pmA, sp, tw, T, head, lds);
 }
 
+// gab_conv_set_ir on a split plan that has run: the carry ring holds the far share of the next two blocks, computed
+// with the OLD taps [1024,4096) one buffer ahead.  F of the newest block k (ring slot `head`) over the eight blocks the
+// ring holds, k-7 .. k, yields exactly blocks k+1 and k+2: the far role's operations in its order (conv_split_buffer),
+// so the carry is what a plan that had the new taps from the start holds for every pair F ran for at block k, and
+// equal to rounding for the other pairs (their F ran at block k-1, on another window).  One workgroup per pair, rare.
+__global__ __launch_bounds__(kThreads) void conv_split_carry_refresh_kernel(
+    const float* __restrict__ hist, const float4* __restrict__ pmF, cf* __restrict__ carry,
+    const cf* __restrict__ tw, int head) {
+    __shared__ cf lds[2 * kLdsHalf];
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x;
+    const cf* const hp = reinterpret_cast<const cf*>(hist) + (size_t)q * kSlots * kB;
+    cf* const cp = carry + (size_t)q * kCarrySlots * kB;
+    using FB = fft::BlockFFT<kNB, 16, false>;
+    using FBi = fft::BlockFFT<kNB, 16, true>;
+    cf* const X = lds;
+    cf* const Y = lds + kLdsHalf;
+    cf zb[16];
+    typename FB::Bases twb_base;
+    FB::load_twiddles(twb_base, tw, tid);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)                                      // blocks k-7 .. k, oldest first
+        zb[r] = hp[((head + 1 + (r >> 1)) & (kSlots - 1)) * kB + (r & 1) * kThreads + tid];
+    float4 cb[16];
+    load_spectra<kNB, 16>(cb, pmF + (size_t)q * kBinsB, tid);
+    typename FB::Twiddles twb;
+    FB::expand_twiddles(twb_base, twb);
+    FB::run(zb, X, Y, twb, tid);
+    cf zpb[16];
+    partner_exchange<kNB, 16, true>(zb, zpb, X, tid);
+    spectral_product<kNB, 16>(zb, zpb, cb, tid);
+    FBi::template run<typename FB::Twiddles, 4>(zb, Y, X, twb, tid);     // only [12..15]
+    cf* const c1 = cp + ((head + 1) & (kCarrySlots - 1)) * kB;            // block k+1
+    cf* const c2 = cp + ((head + 2) & (kCarrySlots - 1)) * kB;            // block k+2
+    c1[tid] = zb[12];
+    c1[tid + kThreads] = zb[13];
+    c2[tid] = zb[14];
+    c2[tid + kThreads] = zb[15];
+}
+
 // ---- the real-time round trip: one buffer, pinned host in -> pinned host out, both link directions busy at once ----
 // gab_conv_round_trip (classic cut).  What crosses the link is 2 MiB each way at C3; the reference moves them one after
 // the other around its kernels (cuda/bench_base.cu:30-42, bench_conv1d_accel.cu:258-304).  Measured on this part
@@ -2526,6 +2566,22 @@ struct gab_conv_plan {
     std::vector<hipStream_t> used_streams;      // launched on since the last reset
     std::vector<hipStream_t> ordered_streams;   // already wait for reset_ev
     std::mutex order_mu;
+    hipEvent_t ir_ev = nullptr;                  // gab_conv_set_ir's waits (reset_ev stays the reset's)
+
+    // Before anything on `s` rewrites state that launches still in flight on other streams read (the reset's memsets,
+    // set_ir's spectra): `s` waits for every stream launched on since the last reset, through `ev`.
+    void wait_for_used_streams(hipStream_t s, hipEvent_t ev, bool clear) {
+        std::lock_guard<std::mutex> lock(order_mu);
+        for (hipStream_t u : used_streams) {
+            if (u == s) continue;
+            GAB_HIP_CHECK(hipEventRecord(ev, u));
+            GAB_HIP_CHECK(hipStreamWaitEvent(s, ev, 0));
+        }
+        if (clear) {
+            used_streams.clear();
+            ordered_streams.clear();
+        }
+    }
 
     // called before every launch on `s`
     void order_after_reset(hipStream_t s) {
@@ -2551,6 +2607,7 @@ int gab_conv_create(gab_conv_plan** out, int tracks, int bufsize, int ir_len) {
         p->pairs = (tracks + 1) / 2;
         GAB_HIP_CHECK(hipGetDevice(&p->device));
         GAB_HIP_CHECK(hipEventCreateWithFlags(&p->reset_ev, hipEventDisableTiming));
+        GAB_HIP_CHECK(hipEventCreateWithFlags(&p->ir_ev, hipEventDisableTiming));
         p->fused = (bufsize == gab::kB && ir_len <= gab::kNB);
         p->tail = ir_len > gab::kB;
         const bool pow2 = (bufsize & (bufsize - 1)) == 0;
@@ -2636,6 +2693,7 @@ int gab_conv_create_scheme(gab_conv_plan** out, int tracks, int bufsize, int ir_
         try {
             GAB_HIP_CHECK(hipGetDevice(&p->device));
             GAB_HIP_CHECK(hipEventCreateWithFlags(&p->reset_ev, hipEventDisableTiming));
+            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->ir_ev, hipEventDisableTiming));
             p->fdl = gab::fdl::create(tracks, bufsize, ir_len);
         } catch (...) {
             gab_conv_destroy(p);
@@ -2678,6 +2736,7 @@ int gab_conv_destroy(gab_conv_plan* p) {
     if (p->ring) (void)hipFree(p->ring);
     if (p->fdl) gab::fdl::destroy(p->fdl);
     if (p->reset_ev) (void)hipEventDestroy(p->reset_ev);
+    if (p->ir_ev) (void)hipEventDestroy(p->ir_ev);
     if (p->rt_stage) (void)hipFree(p->rt_stage);
     if (p->rt_park) (void)hipFree(p->rt_park);
     if (p->rt_counters) (void)hipFree(p->rt_counters);
@@ -2703,6 +2762,7 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
         if (!p || !d_ir) return gab::bad_arg("gab_conv_set_ir: null argument");
         if (p->eng_running) return gab::bad_arg("gab_conv_set_ir: the plan's engine is running (gab_conv_engine_stop first)");
         hipStream_t s = gab::as_stream(stream);
+        p->wait_for_used_streams(s, p->ir_ev, false);       // launches in flight on other streams run with the taps they were queued under
         if (p->fdl) {
             gab::fdl::set_ir(p->fdl, d_ir, s);                  // every partition in one launch
         } else if (p->uniform) {
@@ -2721,6 +2781,14 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
                     d_ir, p->pmA2, p->pmF, p->tw, p->tracks, p->ir_len, gab::kB, 2 * gab::kB);
             int rc = gab::launch_status("conv_ir_spectra_kernel");
             if (rc) return rc;
+            if (p->split && !p->fresh) {
+                // the carry ring holds the far share of the next two blocks under the old taps: recompute it from the
+                // history ring (block head - 1 is the newest) with the new ones
+                gab::conv_split_carry_refresh_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
+                    p->hist, p->pmF, p->carry, p->tw, (p->head + gab::kSlots - 1) & (gab::kSlots - 1));
+                rc = gab::launch_status("conv_split_carry_refresh_kernel");
+                if (rc) return rc;
+            }
         } else {
             GAB_HIP_CHECK(hipMemcpyAsync(p->ir_copy, d_ir, p->spectra_bytes,
                                          hipMemcpyDeviceToDevice, s));
@@ -2765,17 +2833,7 @@ int gab_conv_reset(gab_conv_plan* p, gab_stream_t stream) {
                 p->rt_words[48 + 8 * b] = 0;
             }
         hipStream_t s = gab::as_stream(stream);
-        {
-            // launches still in flight on other streams read the rings: the memsets go behind them
-            std::lock_guard<std::mutex> lock(p->order_mu);
-            for (hipStream_t u : p->used_streams) {
-                if (u == s) continue;
-                GAB_HIP_CHECK(hipEventRecord(p->reset_ev, u));
-                GAB_HIP_CHECK(hipStreamWaitEvent(s, p->reset_ev, 0));
-            }
-            p->used_streams.clear();
-            p->ordered_streams.clear();
-        }
+        p->wait_for_used_streams(s, p->reset_ev, true);      // launches still in flight on other streams read the rings: the memsets go behind them
         if (p->fdl) gab::fdl::reset(p->fdl, s);
         else if (p->uniform) GAB_HIP_CHECK(hipMemsetAsync(p->ring, 0, p->history_bytes, s));
         else GAB_HIP_CHECK(hipMemsetAsync(p->hist, 0, p->history_bytes, s));
@@ -3551,7 +3609,7 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
 #ifdef GAB_ABLATE
             if (getenv("GAB_BATCH_CHUNK")) chunk_max = std::max(1, atoi(getenv("GAB_BATCH_CHUNK")));   // diagnostic builds: to measure the above
 #endif
-            if (p->split) p->order_after_reset(s);
+            p->order_after_reset(s);                          // both cuts: a batch on another stream than the reset's waits for it
             gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
             const size_t step = (size_t)p->tracks * p->bufsize;
             for (int done = 0; done < n_buffers;) {

@@ -248,9 +248,16 @@ int gab_conv_create(gab_conv_plan** plan, int tracks, int bufsize, int ir_len);
 int gab_conv_create_scheme(gab_conv_plan** plan, int tracks, int bufsize, int ir_len, int scheme);
 int gab_conv_destroy(gab_conv_plan* plan);
 /* precomputeImpulseResponseFFTs (:175-228): d_ir is tracks x ir_len floats on
- * the device.  Synchronous with respect to `stream`.                         */
+ * the device.  Synchronous with respect to `stream`.  Mid-stream, on every
+ * route: new taps from the next buffer on; bit-identical to a plan that had
+ * them from the start, except the split cut's first buffer, which is equal to
+ * rounding (its far share of the next two blocks is recomputed here from the
+ * history).  Ordered after every launch queued on any stream since the last
+ * reset: those run with the taps they were queued under.                     */
 int gab_conv_set_ir(gab_conv_plan* plan, const float* d_ir, gab_stream_t stream);
-/* Forget all history (the state a freshly created plan has).                 */
+/* Forget all history (the state a freshly created plan has).  Ordered after
+ * launches queued on other streams; a later launch on another stream waits
+ * for it.                                                                    */
 int gab_conv_reset(gab_conv_plan* plan, gab_stream_t stream);
 /* One buffer: d_in track-major T x B, d_out sample-major [T*s+t]
  * (performBenchmarkIteration :258-304 without the host copies).  d_in / d_out

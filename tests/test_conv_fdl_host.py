@@ -10,13 +10,23 @@ FDL = 2
 
 def stream_reference(xs, ir, T, B, L):
     """Each channel's whole concatenated stream convolved with its response in float64 (scipy fftconvolve):
-    xs = n buffers [T*B] (channel-major), ir [T*L]; returns n outputs [B*T] (sample-major, out[s*T + t])."""
+    xs = n buffers [T*B] (channel-major), ir [T*L]; returns n outputs [B*T] (sample-major, out[s*T + t]).
+    ir may also be a schedule [(first_buffer, ir), ...] (the first entry at buffer 0): output buffer i then uses the
+    response in force at i, over the whole input history (which does not depend on the taps)."""
     from scipy.signal import fftconvolve
+    schedule = ir if isinstance(ir, (list, tuple)) else [(0, ir)]
+    assert schedule[0][0] == 0 and all(a[0] < b[0] for a, b in zip(schedule, schedule[1:]))
     n = len(xs)
     X = np.stack([np.asarray(x, np.float64).reshape(T, B) for x in xs], axis=1).reshape(T, n * B)
-    H = np.asarray(ir, np.float64).reshape(T, L)
-    Y = np.stack([fftconvolve(X[t], H[t])[:n * B] for t in range(T)])
-    return [np.ascontiguousarray(Y[:, i * B:(i + 1) * B].T).ravel() for i in range(n)]
+    out = []
+    for j, (first, h) in enumerate(schedule):
+        end = schedule[j + 1][0] if j + 1 < len(schedule) else n
+        if end <= first:
+            continue
+        H = np.asarray(h, np.float64).reshape(T, L)
+        Y = np.stack([fftconvolve(X[t, :end * B], H[t])[:end * B] for t in range(T)])
+        out += [np.ascontiguousarray(Y[:, i * B:(i + 1) * B].T).ravel() for i in range(first, end)]
+    return out
 
 
 @pytest.fixture(scope="module")
