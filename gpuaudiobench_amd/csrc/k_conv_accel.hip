@@ -130,33 +130,6 @@ __device__ __forceinline__ void spectral_product(cf (&z)[R], const cf (&zraw)[R]
     }
 }
 
-template <typename T>
-__device__ __forceinline__ void keep_alive(const T& v) {
-    const float* f = reinterpret_cast<const float*>(&v);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; ++i) asm volatile("" ::"v"(f[i]));
-}
-
-#ifdef GAB_ABLATE
-// split kernel (debug bit 64): [launch parity][block][8] of s_memrealtime; slot 6 = HW_ID, 7 = XCC_ID.
-// Bit 128 additionally drains the wave's loads (s_waitcnt vmcnt(0)) before slot 1, so that slot 1
-// reads "all of this wave's data has arrived" (that changes the timing it measures).
-__device__ unsigned long long g_split_stamps[2 * 8 * 8192];
-#define GAB_SSTAMP(i)                                                                          \
-    do {                                                                                       \
-        if (sp.debug & 64) {                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            if (threadIdx.x == 0)                                                              \
-                g_split_stamps[((head & 1) * 8192 + (sp.debug >> 20) + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-        }                                                                                      \
-    } while (0)
-#define GAB_SDRAIN() do { if (sp.debug & 128) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
-#else
-#define GAB_SSTAMP(i) do {} while (0)
-#define GAB_SDRAIN() do {} while (0)
-#endif
-
 // (Tried and measured slower, so not kept: running partition B first in half of
 // the workgroups to de-phase the two workgroups that share a CU, 14.8 vs 14.0 us;
 // a 512-thread radix-8 form of this kernel (8 values per thread, 4 passes), 16.6 us:
@@ -323,17 +296,9 @@ struct ConvSplit {
     const float4* pmF;     // [pairs][kBinsB]   taps [1024,4096)
     cf* carry;             // [pairs][4][512]   F's outputs, slot = block & 3
 #ifdef GAB_ABLATE
-    int debug;             // diagnostic builds only (GAB_CONV_SPLIT_DEBUG): role / stage ablations, stamps
+    int debug;             // diagnostic builds only (GAB_CONV_SPLIT_DEBUG): bit 64, the period stamps
 #endif
 };
-
-// Stage ablations exist in diagnostic builds only (-DGAB_ABLATE, libgab_hip_ablate.so): the product
-// kernels have no path that skips work.
-#ifdef GAB_ABLATE
-#define GAB_SDBG(bit) ((sp.debug & (bit)) != 0)
-#else
-#define GAB_SDBG(bit) false
-#endif
 
 constexpr int kCarrySlots = 4;
 using PadA16 = fft::Pad<16>;
@@ -354,24 +319,15 @@ __device__ __forceinline__ void conv_split_buffer(
     int slot;                                                         // index within the role
     if ((gridDim.x & 511) == 0) {
         const int run = blockIdx.x >> 8;
-        far = ((run & 1) != 0) != GAB_SDBG(256);                      // diagnostic bit 256: far workgroups first
+        far = (run & 1) != 0;
         slot = (run >> 1) * 256 + (blockIdx.x & 255);
     } else {
-        far = ((int)blockIdx.x >= duos) != GAB_SDBG(256);
+        far = (int)blockIdx.x >= duos;
         slot = (int)blockIdx.x >= duos ? blockIdx.x - duos : blockIdx.x;
     }
     const int d = xcd_contiguous(slot, duos);
 
-    GAB_SSTAMP(0);
-#ifdef GAB_ABLATE
-    if (GAB_SDBG(64) && threadIdx.x == 0) {
-        g_split_stamps[((head & 1) * 8192 + (sp.debug >> 20) + blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_getreg(63492);   // HW_ID
-        g_split_stamps[((head & 1) * 8192 + (sp.debug >> 20) + blockIdx.x) * 8 + 7] = __builtin_amdgcn_s_getreg(63508);   // XCC_ID
-    }
-#endif
     if (far) {
-        if (GAB_SDBG(4)) return;
-        if (GAB_SDBG(512)) __builtin_amdgcn_s_setprio(2);
         // ---- F of one pair: window = the seven newest blocks of the ring + the new block
         const int q = 2 * d + (head & 1);
         const int ta = 2 * q, tb = ta + 1;
@@ -400,29 +356,20 @@ __device__ __forceinline__ void conv_split_buffer(
         __builtin_amdgcn_sched_barrier(0);
         typename FB::Twiddles twb;
         FB::expand_twiddles(twb_base, twb);
-        GAB_SDRAIN();
-        GAB_SSTAMP(1);
         FB::run(zb, X, Y, twb, tid);
-        GAB_SSTAMP(2);
         cf zpb[16];
         partner_exchange<kNB, 16, true>(zb, zpb, X, tid);
         spectral_product<kNB, 16>(zb, zpb, cb, tid);
-        GAB_SSTAMP(3);
         FBi::template run<typename FB::Twiddles, 4>(zb, Y, X, twb, tid);     // only [12..15]
-        GAB_SSTAMP(4);
         cf* const c1 = cp + ((head + 1) & (kCarrySlots - 1)) * kB;            // block k+1
         cf* const c2 = cp + ((head + 2) & (kCarrySlots - 1)) * kB;            // block k+2
-        if (GAB_SDBG(16)) { keep_alive(zb[12]); keep_alive(zb[13]); keep_alive(zb[14]); keep_alive(zb[15]); return; }
         c1[tid] = zb[12];
         c1[tid + kThreads] = zb[13];
         c2[tid] = zb[14];
         c2[tid + kThreads] = zb[15];
-        GAB_SSTAMP(5);
         return;
     }
 
-    if (GAB_SDBG(1)) return;
-    if (GAB_SDBG(1024)) __builtin_amdgcn_s_setprio(2);
     // ---- near: wave w holds one 1024-point transform: pair (w >> 1) of the duo, window w & 1
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -458,14 +405,11 @@ __device__ __forceinline__ void conv_split_buffer(
     load_spectra<kNA, 16>(c, (second ? sp.pmA2 : pmA) + (size_t)q * kBinsA, lane);
     __builtin_amdgcn_sched_barrier(0);
     WF::expand_twiddles(t);
-    if (!second && !GAB_SDBG(8)) {                                 // the new block enters the ring
+    if (!second) {                                                  // the new block enters the ring
 #pragma unroll
         for (int j = 0; j < 8; ++j) hp[head * kB + lane + 64 * j] = z[8 + j];
     }
-    GAB_SDRAIN();
-    GAB_SSTAMP(1);
     WF::run(z, img, t, lane);
-    GAB_SSTAMP(2);
     const unsigned rb = (unsigned)lane + ((unsigned)lane >> 4);      // Pad(lane + 64 r) = rb + 68 r
     {
         cf zp[16];
@@ -482,10 +426,7 @@ __device__ __forceinline__ void conv_split_buffer(
         for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];
     }
     __syncthreads();
-    GAB_SSTAMP(3);
     cf y[8];
-    const bool pieces8 = GAB_SDBG(2048);      // A/B: one float2 per pair and sample, no swap
-    if (pieces8 && second) return;
     if (!second) {
         {
             const cf* const other = img + kWaveImg;                   // the A2 transform of the same pair
@@ -497,15 +438,8 @@ __device__ __forceinline__ void conv_split_buffer(
 #pragma unroll
         for (int j = 0; j < 8; ++j) park[j] = cy[lane + 64 * j];
         WFi::run(z, img, t, lane);
-        GAB_SSTAMP(4);
 #pragma unroll
         for (int j = 0; j < 8; ++j) y[j] = fft::cadd(z[8 + j], park[j]);
-        if (pieces8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<float2*>(out + (size_t)T * (lane + 64 * j) + ta) = make_float2(y[j].x, y[j].y);
-            return;
-        }
         // The two pairs of a duo are four neighbouring channels: 16 bytes per sample.  The waves
         // swap halves through LDS so that each stores float4 pieces — half as many partial-line
         // writes into L2 as with one float2 per pair (the output scatter is 8 KiB-strided).
@@ -520,11 +454,6 @@ __device__ __forceinline__ void conv_split_buffer(
     }
     __syncthreads();
     if (second) return;
-    if (GAB_SDBG(32)) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) keep_alive(y[j]);
-        return;
-    }
     {
         float* const o0 = out + 4 * (size_t)d;
         if (w == 0) {
@@ -543,7 +472,6 @@ __device__ __forceinline__ void conv_split_buffer(
             }
         }
     }
-    GAB_SSTAMP(5);
 }
 
 __global__ __launch_bounds__(kThreads, 2) void conv_split_kernel(
@@ -653,11 +581,8 @@ constexpr unsigned kRtSentinel = 0xffa5c3e1u;       // a negative NaN with a pay
 // -1.7e38: no audio) waits for the upload's completion like the sentinel itself.
 __device__ __forceinline__ bool rt_pending(unsigned w) { return (w >> 24) == (kRtSentinel >> 24); }
 constexpr size_t kRtUploadPiece = (size_t(4) << 20) - 256;   // bytes per engine copy of an upload that a kernel consumes as it lands (below the runtime's 4 MiB - 1 packet limit, a multiple of 256)
-constexpr int kRtCompletion = 2;                   // how gab_conv_round_trip observes the launch's end (see there)
 constexpr int kRtPollLimit = 1 << 21;              // x ~0.5 us of s_sleep: about a second, then the launch gives up
 constexpr int kRtMaxGroups = 40;
-[[maybe_unused]] constexpr int kEngineWaves = 12;  // gab_conv_engine_start: conv_split_engine12_kernel; diagnostic builds: GAB_ENGINE_WAVES=8 -> round 5's conv_split_engine_kernel
-[[maybe_unused]] constexpr int kBatchWaves = 12;   // gab_conv_process_batch on a split plan: conv_split_batch12_kernel; diagnostic builds: GAB_BATCH_WAVES=8 / 6 / 64 / 26
 constexpr size_t kBatchChunk = 256;                // buffers per conv_split_batch12_kernel launch at most (see gab_conv_process_batch)
 struct ConvRoundTrip {
     unsigned* stage;                  // [T*B] fine-grained device memory
@@ -937,26 +862,12 @@ __global__ __launch_bounds__(kThreads, 2) void conv_batch_kernel(
 //    buffers therefore runs n + 1 periods (the far and forward waves idle in the last one).
 // (Round 2's form — near role on four waves with both near transforms per pair, carry ring in memory,
 // 6.4 us per buffer — is in the history of this file; this one runs 5.3.)
-// Round 5's workgroup (k_conv_accel_diag.hpp, diagnostic builds) = 512 threads: waves 0-1 forward (pair 0, pair 1), waves 2-3
-// inverse, waves 4-7 far — one near and one far wave per SIMD; the product's is the twelve-wave one further down, which says
-// what it changes (two far groups, the carry through memory, spectra in LDS).  Every wave executes kBatchBarriers s_barriers per period; a
+// (Round 5's workgroup — 512 threads: waves 0-1 forward (pair 0, pair 1), waves 2-3 inverse, waves 4-7 far, one near and one
+// far wave per SIMD — is in the history of this file.)  The product's is the twelve-wave one further down, which says what it
+// changes (two far groups, the carry through memory, spectra in LDS).  Every wave executes kBatchBarriers s_barriers per period; a
 // wave-held transform arrives at two of them from inside (WaveFFT1024's hook), so that each role does
 // about one transform pass per barrier interval.
 constexpr int kBatchBarriers = 6;
-
-#ifdef GAB_ABLATE
-// diagnostic bit 64: in period 32 of a launch every wave's lane 0 stamps s_memrealtime (100 MHz) —
-// near waves when they ARRIVE at each of the six barriers (slots 0-5) and after the last (6), far waves
-// after each barrier RELEASES them (slots 0-5) and at the period's start (6); slot = [block][wave][8].
-#define GAB_BSTAMP(i)                                                                                     \
-    do {                                                                                                  \
-        if (GAB_SDBG(64) && nb == (ENGINE ? 4000 : 32) && lane == 0)     /* the engine: once the clocks have settled */   \
-            g_split_stamps[((size_t)blockIdx.x * 8 + w) * 8 + (i)] = __builtin_amdgcn_s_memrealtime();    \
-    } while (0)
-#else
-#define GAB_BSTAMP(i) do {} while (0)
-#endif
-struct ArriveAtBarrier { __device__ __forceinline__ void operator()(int) const { __syncthreads(); } };
 
 // ENGINE (gab_conv_engine_*, conv_split_engine12_resident below): the batch launch's period code kept on the device; it takes
 // buffer nb from slot nb % ring of an input ring when the doorbell word says it has been published, instead of n_buffers known at
@@ -984,7 +895,7 @@ struct ConvEngine {
     unsigned* completed;          // pinned host
     unsigned* error;              // pinned host
     int ring;                     // buffers in the input and output rings (>= 3)
-    int poll_every_period;        // 1; diagnostic builds may turn it off (the word is then read only when the engine stalls)
+    int poll_every_period;        // always 1: the doorbell is asked every period (an argument still: dropping it changes the kernel's code)
     unsigned* started;            // device: workgroups that have begun (zero at launch)
     unsigned* resident;           // pinned host: [0] = 1 once the first workgroup runs, [1] = workgroups once the last one does
     unsigned long long idle_ticks;   // of the 100 MHz wall clock: a stalled workgroup gives up after that long without the doorbell moving
@@ -992,37 +903,13 @@ struct ConvEngine {
 constexpr double kEngineIdleSeconds = 4.0;     // the default of gab_conv_engine_set_idle_limit
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
-// experiments only (GAB_EXTRA_FLAGS=-DGAB_ENGV=bits, a build of its own): 1 no progress words / aggregator, 2 plain output
-// stores, 4 plain input loads, 8 history from the input ring as a batch launch takes it (needs a ring of >= 9 slots),
-// 32 the doorbell is read only when the engine stalls, 64 rings in fine-grained device memory, 256 non-temporal input loads (64 + 256: the engine as it was before the rings became ordinary memory).  Compile-time: a run-time switch at every load perturbs what it measures.
-#ifndef GAB_ENGV
-#define GAB_ENGV 0
-#endif
-#define GAB_EABL(bit) ((GAB_ENGV & (bit)) != 0)
-// (experiments on the twelve-wave engine's output stores: GAB_ENGSTORE 1 "sc0 sc1", 2 "nt sc1", 3 "nt", 4 plain;
-// GAB_ENGWB / GAB_ENGWB8: an L2 write-back by every inverse wave before its progress word / by one wave per XCD and period;
-// GAB_ENGPUSH: whole lines written through a second time — profiles/r06_engine12.md)
-#ifndef GAB_ENGSTORE
-#define GAB_ENGSTORE 0
-#endif
-#if GAB_ENGSTORE == 1
-#define GAB_ENGSTORE_BITS "sc0 sc1"
-#elif GAB_ENGSTORE == 2
-#define GAB_ENGSTORE_BITS "nt sc1"
-#elif GAB_ENGSTORE == 3
-#define GAB_ENGSTORE_BITS "nt"
-#elif GAB_ENGSTORE == 4
-#define GAB_ENGSTORE_BITS ""
-#else
-#define GAB_ENGSTORE_BITS "sc1"
-#endif
 
 // ---- n buffers per launch on TWELVE waves, three per SIMD (round 6) ----------------------------------------------------------
-// Round 5's batch launch (k_conv_accel_diag.hpp) holds two waves per SIMD at 244 registers: a near wave and a far wave, and what the period costs
+// Round 5's batch launch held two waves per SIMD at 244 registers: a near wave and a far wave, and what the period costs
 // beyond the far role's own chain is what two waves cannot hide of each other's latency.  Here the far role is
 // TWO groups of four waves, group g owning pair g of the duo for the whole launch; a pair's turn comes every other buffer,
 // so a group takes TWO periods — twelve barrier intervals — per transform and each SIMD holds a near wave and a wave of
-// either group.  Same arithmetic on the same values in the same order as conv_split_batch_kernel (same transform passes,
+// either group.  Same arithmetic on the same values in the same order as round 5's launch (same transform passes,
 // same twiddle powers, same products, same sums): bit-identical to it and to n launches of conv_split_kernel.
 // What makes 168 registers per wave and 160 KB of LDS enough:
 //   * a group transforms in ONE padded LDS image (write, barrier, read, barrier: it has twelve intervals for six exchanges);
@@ -1068,9 +955,10 @@ __device__ __forceinline__ void spectral_product_part(cf (&z)[R], const cf (&zra
 #ifdef GAB_ABLATE
 // diagnostic bit 64: in periods 32 and 33 of a launch every wave's lane 0 stamps s_memrealtime (100 MHz) when it ARRIVES at each of
 // the six barriers: slot = [block][wave (12)][period - 32][barrier]; tools/stamp_batch12.py
+__device__ unsigned long long g_split_stamps[2 * 8 * 8192];
 #define GAB_B12BAR(period, i)                                                                                         \
     do {                                                                                                              \
-        if (GAB_SDBG(64) && ((period) == 32 || (period) == 33) && lane == 0)                                          \
+        if ((sp.debug & 64) && ((period) == 32 || (period) == 33) && lane == 0)                                       \
             g_split_stamps[(((size_t)blockIdx.x * 12 + w) * 2 + ((period) - 32)) * 6 + (i)] = __builtin_amdgcn_s_memrealtime(); \
         __syncthreads();                                                                                              \
     } while (0)
@@ -1109,10 +997,6 @@ __device__ __forceinline__ void conv_split_batch12_resident(
         // ---- far waves: group g turns pair g of the duo, one transform per two periods
         const int g = __builtin_amdgcn_readfirstlane((w - 4) >> 2);
         const int ft = (tid - kThreads) & (kThreads - 1);
-#ifdef GAB_ABLATE
-        if (GAB_SDBG(2048)) __builtin_amdgcn_s_setprio(2);            // diagnostic builds: the far waves ahead of the near ones
-        if (GAB_SDBG(4096) && g == 1) __builtin_amdgcn_s_setprio(1);  // ... or only the younger group (the SIMD favours the older)
-#endif
         cf* const img = far_img + g * kLdsHalf;
         const int q = 2 * d + g;
         const cf* const hp = reinterpret_cast<const cf*>(hist) + (size_t)q * kSlots * kB;
@@ -1481,11 +1365,6 @@ __device__ __forceinline__ void conv_split_batch12_resident(
     }
 }
 
-#ifdef GAB_ABLATE      // diagnostic builds only: round 5's eight-wave launches (GAB_BATCH_WAVES / GAB_ENGINE_WAVES = 8) and the
-                       // six-wave forms (GAB_BATCH_WAVES = 6 / 64 / 26) that were measured against the product's and not kept
-#include "k_conv_accel_diag.hpp"
-#endif
-
 __global__ __launch_bounds__(kB12Threads) void conv_split_batch12_kernel(
     const float* __restrict__ in, float* __restrict__ out, float* __restrict__ hist,
     const float4* __restrict__ pmA, ConvSplit sp, const cf* __restrict__ tw, int T, int head0, int n_buffers) {
@@ -1494,8 +1373,8 @@ __global__ __launch_bounds__(kB12Threads) void conv_split_batch12_kernel(
 }
 
 // ---- the doorbell-fed engine on the twelve-wave period code (round 6) ----------------------------------------------------------
-// conv_split_batch12_resident's roles behind conv_split_engine_resident's doorbell: the same gate (every wave asks it once per
-// period, in step), bursts that start cold and end with a drain period, ring slots, system-scope input loads, write-through
+// conv_split_batch12_resident's roles behind the doorbell that ConvEngine describes: a gate that every wave asks once per
+// period (in step), bursts that start cold and end with a drain period, ring slots, system-scope input loads, write-through
 // outputs, per-wave progress words.  A far group's transform spans two periods, so a transform begun in a burst's LAST period is
 // finished in the burst's drain period; the window of a group's next turn is asked for a period ahead where that buffer is
 // published (block k-1 then comes from the input ring), else at the turn itself (block k-1 from the history ring).
@@ -1503,7 +1382,7 @@ __global__ __launch_bounds__(kB12Threads) void conv_split_batch12_kernel(
 // diagnostic bit 64: every wave's lane 0 stamps its ARRIVAL at each barrier of periods 4000 and 4001 (tools/stamp_engine12.py)
 #define GAB_E12BAR(i)                                                                                                 \
     do {                                                                                                              \
-        if (GAB_SDBG(64) && (nb == 4000 || nb == 4001) && lane == 0)                                                  \
+        if ((sp.debug & 64) && (nb == 4000 || nb == 4001) && lane == 0)                                               \
             g_split_stamps[(((size_t)blockIdx.x * 12 + w) * 2 + (nb - 4000)) * 6 + (i)] = __builtin_amdgcn_s_memrealtime(); \
         __syncthreads();                                                                                              \
     } while (0)
@@ -1610,11 +1489,11 @@ __device__ __forceinline__ void conv_split_engine12_resident(
                     const unsigned long long t_poll = __builtin_amdgcn_s_memrealtime();
                     for (;;) {
                         u4 pa, pb;
-                        if (aggregator && !GAB_EABL(1)) aggregate_request(pa, pb);
+                        if (aggregator) aggregate_request(pa, pb);
                         unsigned mine = 0;
                         if (lane == 0) mine = read_door();
                         v = __builtin_amdgcn_readfirstlane(mine);
-                        if (aggregator && !GAB_EABL(1)) aggregate_report(pa, pb);
+                        if (aggregator) aggregate_report(pa, pb);
                         const int p2 = (int)(v & 0x3fffffffu);
                         if (p2 >= nb + 2 || (v >> 31) || (((v >> 30) & 1u) && p2 >= nb + 1)) break;
                         if ((++tries & 255) == 0 && __builtin_amdgcn_s_memrealtime() - t_poll > eng.idle_ticks) {   // the producer is gone: stop here, say so
@@ -1643,9 +1522,7 @@ __device__ __forceinline__ void conv_split_engine12_resident(
     // system- or agent-scope loads 6.09-6.13, by plain loads — which may be stale — 6.2-6.3).
     auto ld = [](const float* p) -> float {
         if constexpr (ENGINE)
-            return GAB_EABL(4)     ? *p
-                   : GAB_EABL(256) ? __builtin_nontemporal_load(p)
-                                   : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // sc0 sc1
+            return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // sc0 sc1
         else return *p;
     };
 
@@ -2040,26 +1917,20 @@ __device__ __forceinline__ void conv_split_engine12_resident(
             unsigned door_next = s_door[nb & 1];                  // (no per-period poll: the word as last seen)
             u4 prog_a = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, prog_b = prog_a;
             if constexpr (ENGINE) {
-                if (nb >= base + 2 && !GAB_EABL(1)) {
+                if (nb >= base + 2) {
                     // this wave's rows of buffer nb - 2 were stored a period ago: drained by now, so the wait is free,
                     // and the count of finished buffers can go out (write-through, nobody waits for it)
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef GAB_ENGWB
-                    asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifdef GAB_ENGWB8
-                    if (blockIdx.x < 8 && pr == 1) asm volatile("buffer_wbl2 sc1" ::: "memory");
-#endif
                     if (lane == 0) __hip_atomic_store(&eng.progress[2 * blockIdx.x + pr], (unsigned)(nb - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 if (tid == kPoller && eng.poll_every_period)      // asked now, needed at the period's end
                     door_next = blockIdx.x == 0 ? __hip_atomic_load(eng.doorbell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
                                                 : __hip_atomic_load(eng.relay, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (aggregator && pr == 0 && !GAB_EABL(1)) aggregate_request(prog_a, prog_b);
+                if (aggregator && pr == 0) aggregate_request(prog_a, prog_b);
             }
             auto close_period = [&]() {                           // before the closing barrier
                 if constexpr (ENGINE) {
-                    if (aggregator && pr == 0 && !GAB_EABL(1)) aggregate_report(prog_a, prog_b);
+                    if (aggregator && pr == 0) aggregate_report(prog_a, prog_b);
                     if (tid == kPoller) {
                         s_door[(nb + 1) & 1] = door_next;
                         if (blockIdx.x == 0 && eng.poll_every_period)
@@ -2067,10 +1938,7 @@ __device__ __forceinline__ void conv_split_engine12_resident(
                     }
                 }
             };
-            bool idle_period = nb == base;                        // a burst's first period: nothing to turn yet
-#ifdef GAB_ABLATE
-            if (GAB_SDBG(1)) idle_period = true;                  // diagnostic builds: near role idle
-#endif
+            const bool idle_period = nb == base;                  // a burst's first period: nothing to turn yet
             if (idle_period) {
                 for (int i = 0; i < kBatchBarriers - 1; ++i) __syncthreads();
                 close_period();
@@ -2099,22 +1967,6 @@ __device__ __forceinline__ void conv_split_engine12_resident(
 #pragma unroll
                 for (int j = 0; j < 8; ++j) y[j] = fft::cadd(z[8 + j], park[j]);
                 GAB_E12BAR(3);                                    // barrier 4
-#ifdef GAB_ENGPUSH
-                // experiment (the cost alone, no protocol): this wave's share of the eight-workgroup line group's rows of the buffer
-                // stored FOUR periods ago is read back from L2 here and written through as whole 128-byte lines behind the stores
-                u4 pl[4] = {};
-                const bool push = nb >= base + 5;
-                char* pbase = nullptr;
-                if (push) {
-                    int ps = oslot - 4;
-                    if (ps < 0) ps += eng.ring;
-                    pbase = reinterpret_cast<char*>(out + (size_t)ps * step) + (size_t)(d >> 3) * 128 +
-                            (size_t)((((d & 7) * 2 + pr) * 32) + (lane >> 3)) * T * 4 + (lane & 7) * 16;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(pl[j]) : "v"(pbase + (size_t)8 * j * T * 4) : "memory");
-                }
-#endif
                 // the two pairs of a duo are four neighbouring channels: the waves swap halves through LDS
                 // so that each stores float4 pieces (pair 0 keeps samples lane + 64 j, j < 4, pair 1 j >= 4)
                 if (pr == 0) {
@@ -2128,10 +1980,10 @@ __device__ __forceinline__ void conv_split_engine12_resident(
                 {
                     float* const o0 = outb + 4 * (size_t)d;
                     auto put = [&](float* dst, float a, float b2, float c2, float d2) {
-                        if (ENGINE && !GAB_EABL(2)) {             // write-through: in memory before `completed` says so
+                        if (ENGINE) {                             // write-through: in memory before `completed` says so
                             typedef float f4v __attribute__((ext_vector_type(4)));
                             const f4v val = {a, b2, c2, d2};
-                            asm volatile("global_store_dwordx4 %0, %1, off " GAB_ENGSTORE_BITS ::"v"(dst), "v"(val) : "memory");
+                            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(val) : "memory");
                         } else {
                             *reinterpret_cast<float4*>(dst) = make_float4(a, b2, c2, d2);
                         }
@@ -2150,24 +2002,14 @@ __device__ __forceinline__ void conv_split_engine12_resident(
                         }
                     }
                 }
-#ifdef GAB_ENGPUSH
-                if (push) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (loads and stores may come back out of order with each other)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(pbase + (size_t)8 * j * T * 4), "v"(pl[j]) : "memory");
-                }
-#endif
                 close_period();
                 GAB_E12BAR(5);                                    // barrier 6 closes the period
             }
             if (!more) {
                 // the burst is through: this wave's last rows must be in memory before its count says so (the one wait for
                 // stores on this path: a workgroup that goes idle has nothing to hide it behind)
-                if (!GAB_EABL(1)) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0) __hip_atomic_store(&eng.progress[2 * blockIdx.x + pr], (unsigned)nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (lane == 0) __hip_atomic_store(&eng.progress[2 * blockIdx.x + pr], (unsigned)nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 boundary = true;
                 continue;
             }
@@ -2467,7 +2309,7 @@ __global__ void conv_direct_shift_kernel(const float* __restrict__ in, const flo
 // C ABI
 // ---------------------------------------------------------------------------
 #ifdef GAB_ABLATE
-// diagnostic builds: the ablation mask of the split kernels comes from the environment
+// diagnostic builds: GAB_CONV_SPLIT_DEBUG=64 turns on the twelve-wave launches' period stamps
 static int gab_split_debug_mask() {
     static const int dbg = getenv("GAB_CONV_SPLIT_DEBUG") ? atoi(getenv("GAB_CONV_SPLIT_DEBUG")) : 0;
     return dbg;
@@ -2939,17 +2781,13 @@ static void gab_conv_round_trip_init(gab_conv_plan* p) {
     GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->rt_stage), 2 * n * 4, hipDeviceMallocFinegrained));
     GAB_HIP_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->rt_stage), (int)gab::kRtSentinel, 2 * n));
     GAB_HIP_CHECK(hipMalloc(&p->rt_park, n * 4));
-    int groups = 16;                                  // 64 channels = 256-byte rows at 1024 channels
-    int taper = 1;                                    // the first and the last group cut into quarter, quarter, half (round 5)
-#ifdef GAB_ABLATE
-    if (getenv("GAB_RT_GROUPS")) groups = std::max(1, atoi(getenv("GAB_RT_GROUPS")));
-    if (getenv("GAB_RT_TAPER")) taper = atoi(getenv("GAB_RT_TAPER"));      // 0 equal groups, 1 both ends, 2 the head only, 3 the tail only
-#endif
+    const int groups = 16;                            // 64 channels = 256-byte rows at 1024 channels
     int ppg = (p->pairs + groups - 1) / groups;
     ppg += ppg & 1;                                   // whole float4 columns per row
     // Groups are drained in the order the upload lands them.  The link's downward direction cannot start before the FIRST
     // group is through, and after the LAST rows have landed nothing hides that group's transform and drain: both are cut
-    // finer (their rows are narrower — 64-byte pieces for 16 channels — but few).  Boundaries in pairs, every group even.
+    // finer, into quarter, quarter, half (their rows are narrower — 64-byte pieces for 16 channels — but few).  Boundaries in
+    // pairs, every group even.
     std::vector<int> sizes;
     for (int at = 0; at < p->pairs; at += ppg) sizes.push_back(std::min(ppg, p->pairs - at));
     auto cut = [&](int n, bool rising) {             // n pairs -> n/4, n/4, n/2 (rising) or n/2, n/4, n/4
@@ -2960,8 +2798,8 @@ static void gab_conv_round_trip_init(gab_conv_plan* p) {
     };
     std::vector<int> fine;
     for (size_t i = 0; i < sizes.size(); ++i) {
-        const bool head = i == 0 && (taper == 1 || taper == 2) && sizes.size() > 2;
-        const bool tail = i + 1 == sizes.size() && (taper == 1 || taper == 3) && sizes.size() > 2;
+        const bool head = i == 0 && sizes.size() > 2;
+        const bool tail = i + 1 == sizes.size() && sizes.size() > 2;
         std::vector<int> v = head ? cut(sizes[i], true) : tail ? cut(sizes[i], false) : std::vector<int>{sizes[i]};
         fine.insert(fine.end(), v.begin(), v.end());
     }
@@ -3088,13 +2926,8 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         unsigned* const landed = p->rt_words + 16;
         volatile unsigned* const error = p->rt_words + 32;
         bool upload = true;
-        // How the launch's end is observed: kRtCompletion (measured, profiles/r05_roundtrip_completion.txt).
-        //   0 hipStreamSynchronize   1 an event recorded behind the launch, queried   2 the launch's own stop event
-        //   (hipExtLaunchKernelGGL), queried   3 hipStreamQuery   9 (diagnostic builds only) round 4's rule: the hint word
-        int completion = gab::kRtCompletion;
 #ifdef GAB_ABLATE
         if (getenv("GAB_RT_SKIP_UPLOAD")) upload = false;   // diagnostic builds: the input never lands — every wait must run out
-        if (getenv("GAB_RT_COMPLETION")) completion = atoi(getenv("GAB_RT_COMPLETION"));   // diagnostic builds: to price the rules
 #endif
         // The kernel takes a word the moment it is no longer the sentinel and puts the sentinel back: that is only right
         // if the upload writes every word exactly ONCE — one engine copy from pinned (or device) memory does.  What the
@@ -3150,13 +2983,11 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         gab::ConvRoundTrip rt{stage, p->rt_park, h_out, p->rt_counters, p->rt_words, p->rt_words + 16, p->rt_words + 32,
                               epoch, p->rt_groups, {}};
         for (int g = 0; g <= p->rt_groups; ++g) rt.bound[g] = p->rt_bound[g];
-        if (completion == 2)
-            hipExtLaunchKernelGGL(gab::conv_round_trip_kernel, dim3(p->pairs), dim3(gab::kThreads), 0, s, nullptr, p->rt_done_ev, 0,
-                                  rt, p->hist, (const float4*)p->pmA, (const float4*)p->pmB, (const gab::fft::cf*)p->tw, p->tracks, p->head);
-        else
-            gab::conv_round_trip_kernel<<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(rt, p->hist, p->pmA, p->pmB, p->tw, p->tracks, p->head);
+        // The launch's own stop event (hipExtLaunchKernelGGL) is how its end is observed: queried below (measured against
+        // hipStreamSynchronize, an event recorded behind the launch and hipStreamQuery: profiles/r05_roundtrip_completion.txt).
+        hipExtLaunchKernelGGL(gab::conv_round_trip_kernel, dim3(p->pairs), dim3(gab::kThreads), 0, s, nullptr, p->rt_done_ev, 0,
+                              rt, p->hist, (const float4*)p->pmA, (const float4*)p->pmB, (const gab::fft::cf*)p->tw, p->tracks, p->head);
         int rc = gab::launch_status("conv_round_trip_kernel");
-        if (!rc && completion == 1) GAB_HIP_CHECK(hipEventRecord(p->rt_done_ev, s));
         if (rc) {                                       // nothing ran: the epoch, the history and the counters stay as they were
             if (upload) rearm_stage();                  // (the upload did: its words must not pass for the next call's)
             return rc;
@@ -3216,11 +3047,11 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
             }
         }
         (void)hipGetLastError();                        // (hipStreamQuery's hipErrorNotReady)
-        if (ended || completion == 0) {
+        if (ended) {
             GAB_HIP_CHECK(hipStreamSynchronize(s));
-        } else if (completion != 9) {
+        } else {
             for (spins = 0;;) {
-                const hipError_t q = completion == 3 ? hipStreamQuery(s) : hipEventQuery(p->rt_done_ev);
+                const hipError_t q = hipEventQuery(p->rt_done_ev);
                 if (q == hipSuccess) break;
                 (void)hipGetLastError();
                 if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -3290,9 +3121,8 @@ int gab_conv_engine_rings(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
             p->eng_ring = 0;
             // ordinary device memory: the launch reads the input ring with system-scope loads and writes the output
             // ring with write-through stores, so what a copy engine writes is seen and what it reads is there
-            unsigned flags = (GAB_ENGV & 64) ? hipDeviceMallocFinegrained : hipDeviceMallocDefault;   // (experiments: fine-grained, as before)
-            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_in), n * 4 * ring_buffers, flags));
-            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_out), n * 4 * ring_buffers, flags));
+            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_in), n * 4 * ring_buffers, hipDeviceMallocDefault));
+            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_out), n * 4 * ring_buffers, hipDeviceMallocDefault));
             p->eng_ring = ring_buffers;
         }
         *d_in_ring = p->eng_in;
@@ -3307,20 +3137,12 @@ int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
         if (!p || !d_in_ring || !d_out_ring) return gab::bad_arg("gab_conv_engine_start: null argument");
         if (!p->ir_set) return gab::bad_arg("gab_conv_engine_start: gab_conv_set_ir has not been called");
         if (p->eng_running) return gab::bad_arg("gab_conv_engine_start: the plan's engine is already running");
-#ifdef GAB_ABLATE
-        int waves = gab::kEngineWaves;                  // diagnostic builds: round 5's eight-wave engine for A/B on one box (same bits)
-        if (getenv("GAB_ENGINE_WAVES")) waves = atoi(getenv("GAB_ENGINE_WAVES"));
-#endif
         {
             // Every workgroup of the engine stays on the device until the stop and waits for words other workgroups write
             // (the relayed doorbell): all of them must be resident AT ONCE.  One fits per compute unit (153 KB of LDS).
             int dev = 0, cus = 0, per_cu = 0;
             GAB_HIP_CHECK(hipGetDevice(&dev));
             GAB_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-#ifdef GAB_ABLATE
-            if (waves != 12) GAB_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gab::conv_split_engine_kernel, gab::kBatchThreads, 0));
-            else
-#endif
             GAB_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gab::conv_split_engine12_kernel, gab::kB12Threads, 0));
             const long room = (long)cus * per_cu;
             if ((long)(p->tracks / 4) > room)
@@ -3354,19 +3176,8 @@ int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
         p->order_after_reset(s);
         GAB_HIP_CHECK(hipMemsetAsync(p->eng_done, 0, prog_words * sizeof(unsigned), s));
         gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
-        int poll = (GAB_ENGV & 32) ? 0 : 1;
-#ifdef GAB_ABLATE
-        if (getenv("GAB_ENGINE_NOPOLL")) poll = 0;      // diagnostic builds: the doorbell is read only when the engine stalls
-
-#endif
-        gab::ConvEngine eng{p->eng_words, p->eng_done + prog_words - 1, p->eng_done, p->eng_words + 16, p->eng_words + 32, ring_buffers, poll,
+        gab::ConvEngine eng{p->eng_words, p->eng_done + prog_words - 1, p->eng_done, p->eng_words + 16, p->eng_words + 32, ring_buffers, 1,
                             p->eng_done + prog_words - 33, p->eng_words + 48, (unsigned long long)(p->eng_idle_seconds * 1e8)};
-#ifdef GAB_ABLATE
-        if (waves != 12)
-            gab::conv_split_engine_kernel<<<dim3(p->tracks / 4), dim3(gab::kBatchThreads), 0, s>>>(
-                p->eng_in, p->eng_out, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, eng);
-        else
-#endif
         gab::conv_split_engine12_kernel<<<dim3(p->tracks / 4), dim3(gab::kB12Threads), 0, s>>>(
             p->eng_in, p->eng_out, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, eng);
         int rc = gab::launch_status("conv_split_engine12_kernel");
@@ -3605,51 +3416,18 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
             // and 1.9 x the bytes per buffer, and a buffer takes 5.63 us instead of 5.17 (profiles/r05_batch_buffers_per_launch.txt;
             // the classic cut's launch: 10.5 instead of 9.3).  A launch boundary puts them back in step for the price of one
             // cold start per chunk (0.03 us per buffer).
-            size_t chunk_max = gab::kBatchChunk;
-#ifdef GAB_ABLATE
-            if (getenv("GAB_BATCH_CHUNK")) chunk_max = std::max(1, atoi(getenv("GAB_BATCH_CHUNK")));   // diagnostic builds: to measure the above
-#endif
             p->order_after_reset(s);                          // both cuts: a batch on another stream than the reset's waits for it
             gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
             const size_t step = (size_t)p->tracks * p->bufsize;
             for (int done = 0; done < n_buffers;) {
-                const int n = (int)std::min<size_t>(chunk_max, (size_t)(n_buffers - done));
+                const int n = (int)std::min<size_t>(gab::kBatchChunk, (size_t)(n_buffers - done));
                 int rc;
                 if (p->split) {
                     // the split cut, both roles of a duo in one resident workgroup: same bits as n split launches.
-                    // Twelve waves, three per SIMD (round 6); diagnostic builds keep the other forms for A/B on one box: same bits
-#ifdef GAB_ABLATE
-                    int waves = gab::kBatchWaves;
-                    if (getenv("GAB_BATCH_WAVES")) waves = atoi(getenv("GAB_BATCH_WAVES"));
-                    if (waves == 26) {
-                        gab::conv_split_batch2x6_kernel<<<dim3(p->tracks / 4), dim3(gab::kB26Threads), 0, s>>>(
-                            d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
-                        rc = gab::launch_status("conv_split_batch2x6_kernel");
-                    } else if (waves == 64) {                   // six waves per pair at four waves per SIMD (128 registers)
-                        static bool dyn_set = false;
-                        if (!dyn_set) {
-                            GAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gab::conv_split_batch6r_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(gab::kB6Lds * sizeof(gab::fft::cf))));
-                            dyn_set = true;
-                        }
-                        gab::conv_split_batch6r_kernel<<<dim3(p->tracks / 2), dim3(gab::kB6Threads), gab::kB6Lds * sizeof(gab::fft::cf), s>>>(
-                            d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
-                        rc = gab::launch_status("conv_split_batch6r_kernel");
-                    } else if (waves == 6) {
-                        gab::conv_split_batch6_kernel<<<dim3(p->tracks / 2), dim3(gab::kB6Threads), 0, s>>>(
-                            d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
-                        rc = gab::launch_status("conv_split_batch6_kernel");
-                    } else if (waves == 8) {                    // round 5's eight-wave workgroup
-                        gab::conv_split_batch_kernel<<<dim3(p->tracks / 4), dim3(gab::kBatchThreads), 0, s>>>(
-                            d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
-                        rc = gab::launch_status("conv_split_batch_kernel");
-                    } else
-#endif
-                    {
-                        gab::conv_split_batch12_kernel<<<dim3(p->tracks / 4), dim3(gab::kB12Threads), 0, s>>>(
-                            d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
-                        rc = gab::launch_status("conv_split_batch12_kernel");
-                    }
+                    // Twelve waves, three per SIMD (round 6)
+                    gab::conv_split_batch12_kernel<<<dim3(p->tracks / 4), dim3(gab::kB12Threads), 0, s>>>(
+                        d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
+                    rc = gab::launch_status("conv_split_batch12_kernel");
                 } else {
                     gab::conv_batch_kernel<<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(
                         d_in + done * step, d_out + done * step, p->hist, p->pmA, p->pmB, p->tw, p->tracks, p->head, n);

@@ -1032,7 +1032,7 @@ def test_conv_accel_engine_round_trip_from_pinned_host_memory(gab, orc, T):
 def test_conv_accel_batch_equals_one_launch_per_buffer(gab, orc, T, B, L, n):
     """gab_conv_process_batch: n buffers in one launch walk the same history as n launches — same
     bits — including across two batches, mixed with single launches, and for shapes that take other
-    kernels.  A plan on the split cut batches with the split cut (conv_split_batch_kernel: both roles
+    kernels.  A plan on the split cut batches with the split cut (conv_split_batch12_kernel: both roles
     of a duo in one resident workgroup) and stays on it; other plans batch with the classic cut."""
     import torch
     ir = dev(orc.conv_accel_ir(L, T))

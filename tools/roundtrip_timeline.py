@@ -1,4 +1,4 @@
-"""Timeline of ONE gab_conv_round_trip call (diagnostic build: GAB_LIB_PATH=.../libgab_hip_ablate.so [GAB_RT_GROUPS=G]).
+"""Timeline of ONE gab_conv_round_trip call (diagnostic build: GAB_LIB_PATH=.../libgab_hip_ablate.so).
 Device side: per channel group, the first workgroup's entry, the moment the group's last rows had landed, the start and
 the end of its drain to the pinned output (s_memrealtime, 100 MHz, relative to the first workgroup of the launch);
 host side: the call's own marks on the host clock.  Prints a table (median over the calls) and the p50 of the call."""

@@ -2,10 +2,9 @@
 every workgroup stamps its ARRIVAL at each of the six barriers of periods 32 and 33 of a 64-buffer launch (two periods: the two
 far groups are one period out of step).  A barrier releases when its last wave arrives: per interval, the median length and,
 per wave, the median time from the previous release to its arrival (its work in that interval) and how often it was the last.
-    GAB_BATCH_WAVES=12 python tools/stamp_batch12.py"""
+    GAB_LIB_PATH=gpuaudiobench_amd/libgab_hip_ablate.so python tools/stamp_batch12.py"""
 import ctypes, os, sys
 os.environ.setdefault("GAB_CONV_SPLIT_DEBUG", "64")
-os.environ.setdefault("GAB_BATCH_WAVES", "12")
 sys.path.insert(0, ".")
 import numpy as np, torch
 import gpuaudiobench_amd as gab

@@ -1,8 +1,7 @@
-"""Diagnostic build only (GAB_LIB_PATH=.../libgab_hip_ablate.so, GAB_ENGINE_WAVES=12): tools/stamp_batch12.py's barrier timeline for the
+"""Diagnostic build only (GAB_LIB_PATH=.../libgab_hip_ablate.so): tools/stamp_batch12.py's barrier timeline for the
 twelve-wave ENGINE launch (periods 4000 and 4001 of a run whose buffers were all published before the launch looked)."""
 import ctypes, os, sys
 os.environ.setdefault("GAB_CONV_SPLIT_DEBUG", "64")
-os.environ.setdefault("GAB_ENGINE_WAVES", "12")
 sys.path.insert(0, ".")
 import numpy as np, torch
 import gpuaudiobench_amd as gab
