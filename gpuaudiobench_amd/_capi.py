@@ -146,7 +146,17 @@ PROTOTYPES = {
     "gab_fdtd_halo": (_I, [_P, _I, C.POINTER(_P), C.POINTER(C.c_size_t)]),
     "gab_fdtd_emit": (_I, [_P, _P, _I, _I, _P]),
     "gab_fdtd_strip": (_I, [_P, C.POINTER(_P), C.POINTER(_I)]),
-    "gab_generate_noise": (_I, [_P, _Z, C.c_uint]),
+    "gab_eq_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_eq_destroy": (_I, [_P]),
+    "gab_eq_set_coeffs": (_I, [_P, _P, _P]),
+    "gab_eq_set_coeffs_tracks": (_I, [_P, _P, _I, _I, _P]),
+    "gab_eq_reset": (_I, [_P, _P]),
+    "gab_eq_process": (_I, [_P, _P, _P, _P]),
+    "gab_eq_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_eq_process_sequential": (_I, [_P, _P, _P, _P]),
+    "gab_eq_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_eq_form": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),
     "gab_shard_range_aligned": (_I, [_I, _I, _Z, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

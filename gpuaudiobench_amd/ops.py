@@ -432,6 +432,96 @@ class ConvPlan:
             pass
 
 
+class EqPlan:
+    """gab_eq_plan: `sections` biquads in series on each of `tracks` channels, every (track, section) with its own
+    coefficients, state carried from buffer to buffer.  A new plan is the identity filter."""
+
+    def __init__(self, tracks, bufsize, sections):
+        self.tracks, self.bufsize, self.sections = tracks, bufsize, sections
+        self._h = C.c_void_p()
+        check(lib.gab_eq_create(C.byref(self._h), tracks, bufsize, sections))
+
+    def set_coeffs(self, coeffs, first_track=None, n_tracks=None):
+        """coeffs: device tensor [tracks][sections][5] = {b0,b1,b2,a1,a2} (a0 = 1), or [n_tracks][sections][5]
+        for tracks [first_track, first_track + n_tracks)."""
+        if first_track is None:
+            assert coeffs.numel() == self.tracks * self.sections * 5
+            check(lib.gab_eq_set_coeffs(self._h, _dev(coeffs), _stream()))
+        else:
+            assert coeffs.numel() == n_tracks * self.sections * 5
+            check(lib.gab_eq_set_coeffs_tracks(self._h, _dev(coeffs), first_track, n_tracks, _stream()))
+
+    def set_sos(self, sos, tracks=None):
+        """sos: scipy's second-order sections, [sections][6] = {b0,b1,b2,a0,a1,a2} for every track or
+        [tracks][sections][6]; divided by a0.  tracks = (first_track, n_tracks): only those channels
+        ([sections][6] for each of them, or [n_tracks][sections][6])."""
+        import numpy as np
+        sos = np.asarray(sos, np.float64)
+        first, n = (0, self.tracks) if tracks is None else (int(tracks[0]), int(tracks[1]))
+        if sos.ndim == 2:
+            sos = np.broadcast_to(sos, (n,) + sos.shape)
+        if sos.shape != (n, self.sections, 6):
+            raise ValueError("sos must be [sections][6] or [tracks][sections][6]")
+        c = (sos[:, :, [0, 1, 2, 4, 5]] / sos[:, :, 3:4]).astype(np.float32)
+        d = torch.from_numpy(np.ascontiguousarray(c)).cuda()
+        if tracks is None:
+            self.set_coeffs(d)
+        else:
+            self.set_coeffs(d, first, n)
+
+    def reset(self):
+        check(lib.gab_eq_reset(self._h, _stream()))
+
+    def process(self, x, out=None, sequential=False):
+        """One buffer, track-major [tracks*bufsize]; out may be x (in place).  sequential=True: the ordered form."""
+        assert x.numel() == self.tracks * self.bufsize
+        out = torch.empty_like(x) if out is None else out
+        fn = lib.gab_eq_process_sequential if sequential else lib.gab_eq_process
+        check(fn(self._h, _dev(x), _dev(out), _stream()))
+        return out
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch."""
+        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
+        assert rest == 0
+        out = torch.empty_like(xs) if out is None else out
+        check(lib.gab_eq_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
+        return out
+
+    def state(self):
+        """A copy of the carried state, [tracks][sections][2] = (z1, z2)."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_eq_state(self._h, C.byref(p), C.byref(n)))
+        return _view(p.value, n.value // 2, 2).clone().view(self.tracks, self.sections, 2)
+
+    @property
+    def form(self):
+        """(samples per lane, segments per buffer) of the scan kernel; (0, 0): the sequential kernel only."""
+        m, h = C.c_int(0), C.c_int(0)
+        check(lib.gab_eq_form(self._h, C.byref(m), C.byref(h)))
+        return m.value, h.value
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        return (self._h, _dev(x), _dev(out), st)
+
+    @staticmethod
+    def launch(args):
+        check(lib.gab_eq_process(*args))
+
+    def close(self):
+        if self._h:
+            lib.gab_eq_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fdtd_default_params(nx, ny=None, nz=None):
     P = FdtdParams()
     check(lib.gab_fdtd_default_params(nx, nx if ny is None else ny, nx if nz is None else nz,

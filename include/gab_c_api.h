@@ -475,6 +475,53 @@ int gab_fdtd_strip(gab_fdtd_plan* plan, float** d_strip, int* capacity);
 /* Copy the plan's own pressure planes (nx*ny*(z_end-z_begin) floats, x fastest) to d_dst. */
 int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t stream);
 
+/* ---- biquad cascades: a parametric equaliser per track (additive; no counterpart in the reference, whose
+ * IIRFilterKernel runs ONE biquad shared by every track) --------------------------------------------------
+ * `tracks` channels, `sections` second-order sections in series on each (1..16), every (track, section) with its
+ * own coefficients {b0,b1,b2,a1,a2} (a0 = 1; gab_iir's order), the DF-II state (z1, z2 as gab_iir documents it)
+ * carried from buffer to buffer: state layout [tracks][sections][2].
+ *   process             one buffer.  d_in / d_out track-major [t*B + s]; d_out == d_in (in place) is allowed — a wave
+ *                       has read all of its samples before it writes any.  bufsize a power of two from 64 to 2048
+ *                       with 16-byte aligned buffers takes the scan kernel (gab_iir's wave scan, once per section on
+ *                       samples that stay in registers: one read and one write of the audio whatever `sections` is;
+ *                       re-associates the recurrence: equal to the ordered form to rounding, not bit for bit); every
+ *                       other bufsize >= 1, and unaligned pointers, the sequential kernel, as gab_iir falls back.
+ *                       Which scan a plan runs (gab_eq_form) is fixed at creation from (bufsize, sections) alone,
+ *                       never from `tracks`: a track's bits do not depend on how many other tracks the plan holds,
+ *                       so a channel shard equals the unsharded job bit for bit.
+ *   process_batch       n_buffers buffers back to back, [n][T*B], in ONE launch, the state running through: same
+ *                       bits as n calls of process (a batch is more segments of the same scan).  A plan without a
+ *                       scan form (or unaligned pointers) launches the sequential kernel once per buffer.
+ *   process_sequential  one lane per track, every section in the ordered form of gab_iir_sequential (one rounding
+ *                       per operation): with one section and the same coefficients on every track, its bits.
+ *                       process and process_sequential share the plan's state; switching between them mid-stream
+ *                       is allowed and equal to rounding.
+ *   set_coeffs          d_coeffs: device, [tracks][sections][5].  The scan's constants are made on the device in
+ *                       float64 and rounded once.  Synchronous with respect to `stream`.  A section outside the
+ *                       stability triangle (|a2| < 1, |a1| < 1 + a2) or with a value that is not finite:
+ *                       GAB_ERR_INVALID_ARG naming the first such (track, section); the plan then keeps the
+ *                       coefficients it had.  Mid-stream the new coefficients take effect with the next buffer and the
+ *                       carried state is kept as it is: the output is the ordered form run with the coefficients
+ *                       switched at that buffer boundary.
+ *   set_coeffs_tracks   the same for tracks [first_track, first_track + n_tracks), d_coeffs [n_tracks][sections][5]:
+ *                       one channel's knobs moved; no other track's bits change.
+ *   reset               zero state.    state: the plan's own state array, for inspection.
+ *   form                the scan's samples per lane and segments per buffer; 0, 0: the sequential kernel only.
+ * A new plan is the identity filter (b0 = 1, everything else 0) with zero state.  tracks >= 1, bufsize >= 1,
+ * 1 <= sections <= 16; arguments are checked before any device call.  One thread at a time per plan.           */
+typedef struct gab_eq_plan gab_eq_plan;
+int gab_eq_create(gab_eq_plan** plan, int tracks, int bufsize, int sections);
+int gab_eq_destroy(gab_eq_plan* plan);
+int gab_eq_set_coeffs(gab_eq_plan* plan, const float* d_coeffs, gab_stream_t stream);
+int gab_eq_set_coeffs_tracks(gab_eq_plan* plan, const float* d_coeffs, int first_track, int n_tracks,
+                             gab_stream_t stream);
+int gab_eq_reset(gab_eq_plan* plan, gab_stream_t stream);
+int gab_eq_process(gab_eq_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_eq_process_batch(gab_eq_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_eq_process_sequential(gab_eq_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_eq_state(gab_eq_plan* plan, float** d_state, size_t* n_floats);
+int gab_eq_form(const gab_eq_plan* plan, int* samples_per_lane, int* segments);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
