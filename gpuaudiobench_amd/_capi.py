@@ -21,6 +21,8 @@ CONV_STREAMING_HOST_IO = 2
 CONV_SCHEME_CLASSIC = 0
 CONV_SCHEME_SPLIT = 1
 CONV_SCHEME_FDL = 2
+MIX_TRACK_MAJOR = 0
+MIX_SAMPLE_MAJOR = 1
 DWG_NAIVE = 0
 DWG_ACCEL = 1
 
@@ -156,6 +158,15 @@ PROTOTYPES = {
     "gab_eq_process_sequential": (_I, [_P, _P, _P, _P]),
     "gab_eq_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
     "gab_eq_form": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "gab_mix_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_mix_destroy": (_I, [_P]),
+    "gab_mix_set_gains": (_I, [_P, _P, _I, _P]),
+    "gab_mix_set_gains_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_mix_reset": (_I, [_P, _P]),
+    "gab_mix_process": (_I, [_P, _P, _P, _I, _P]),
+    "gab_mix_process_batch": (_I, [_P, _P, _P, _I, _I, _P]),
+    "gab_mix_gains": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_mix_form": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -522,6 +522,113 @@ class EqPlan:
             pass
 
 
+class MixPlan:
+    """gab_mix_plan: `tracks` channels summed into `buses` buses with a linear gain per (track, bus), in a fixed
+    summation order (`form`).  A new plan is silence; new gains are ramped in over the next buffer unless ramp=False."""
+
+    _LAYOUTS = {"track": 0, "sample": 1}
+
+    def __init__(self, tracks, bufsize, buses):
+        self.tracks, self.bufsize, self.buses = tracks, bufsize, buses
+        self._h = C.c_void_p()
+        check(lib.gab_mix_create(C.byref(self._h), tracks, bufsize, buses))
+
+    def set_gains(self, g, ramp=True, first_track=None, n_tracks=None):
+        """g: device tensor [tracks][buses], or [n_tracks][buses] for tracks [first_track, first_track + n_tracks)
+        (n_tracks=None: as many rows as g holds).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        if first_track is None:
+            if n_tracks is not None:
+                raise ValueError("n_tracks needs first_track")
+            assert g.numel() == self.tracks * self.buses
+            check(lib.gab_mix_set_gains(self._h, _dev(g), 1 if ramp else 0, _stream()))
+        else:
+            if n_tracks is None:                    # the rows g holds
+                n_tracks, rest = divmod(g.numel(), self.buses)
+                if rest or n_tracks == 0:
+                    raise ValueError("g must hold whole rows of %d buses" % self.buses)
+            assert g.numel() == n_tracks * self.buses
+            check(lib.gab_mix_set_gains_tracks(self._h, _dev(g), first_track, n_tracks, 1 if ramp else 0, _stream()))
+
+    @staticmethod
+    def stereo_gains(gain_db, pan):
+        """[tracks][2] float32 for a two-bus plan: constant-power law gL = g cos((pan + 1) pi / 4),
+        gR = g sin((pan + 1) pi / 4), g = 10^(gain_db / 20), pan in [-1, 1]; float64, rounded once."""
+        import numpy as np
+        db, pan = np.broadcast_arrays(np.asarray(gain_db, np.float64), np.asarray(pan, np.float64))
+        if pan.size and (pan.min() < -1.0 or pan.max() > 1.0):
+            raise ValueError("pan must be in [-1, 1]")
+        g = 10.0 ** (db / 20.0)
+        th = (pan + 1.0) * (np.pi / 4.0)
+        return np.stack([g * np.cos(th), g * np.sin(th)], axis=-1).astype(np.float32)
+
+    def set_stereo(self, gain_db, pan, ramp=True):
+        """Per-track level (dB) and pan for a two-bus plan (bus 0 left, bus 1 right); scalars apply to every track."""
+        import numpy as np
+        if self.buses != 2:
+            raise ValueError("set_stereo needs a plan of two buses")
+        g = self.stereo_gains(gain_db, pan)
+        g = np.array(np.broadcast_to(g, (self.tracks, 2)), np.float32, order="C")
+        self.set_gains(torch.from_numpy(g).cuda(), ramp=ramp)
+
+    def reset(self):
+        """current := target: a pending ramp is dropped."""
+        check(lib.gab_mix_reset(self._h, _stream()))
+
+    def process(self, x, out=None, layout="track"):
+        """One buffer: x [tracks*bufsize] track-major ("track") or sample-major ("sample", ConvPlan's output);
+        returns [buses*bufsize], bus-major.  out must not overlap x."""
+        assert x.numel() == self.tracks * self.bufsize
+        if out is None:
+            out = torch.empty(self.buses * self.bufsize, dtype=torch.float32, device=x.device)
+        assert out.numel() == self.buses * self.bufsize
+        check(lib.gab_mix_process(self._h, _dev(x), _dev(out), self._LAYOUTS[layout], _stream()))
+        return out
+
+    def process_batch(self, xs, out=None, layout="track"):
+        """Consecutive buffers [n][tracks*bufsize] -> [n][buses*bufsize] in one launch."""
+        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
+        assert rest == 0
+        if out is None:
+            out = torch.empty(n * self.buses * self.bufsize, dtype=torch.float32, device=xs.device)
+        assert out.numel() == n * self.buses * self.bufsize
+        check(lib.gab_mix_process_batch(self._h, _dev(xs), _dev(out), n, self._LAYOUTS[layout], _stream()))
+        return out
+
+    def gains(self):
+        """Copies of (current, target), each [tracks][buses]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_mix_gains(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return (_view(a.value, self.tracks, self.buses).clone(), _view(b.value, self.tracks, self.buses).clone())
+
+    @property
+    def form(self):
+        """(leaf_tracks, group_leaves) of the summation tree; a function of (bufsize, buses) alone."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib.gab_mix_form(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def prepare(self, x, out, layout="track", stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        return (self._h, _dev(x), _dev(out), self._LAYOUTS[layout], st)
+
+    @staticmethod
+    def launch(args):
+        check(lib.gab_mix_process(*args))
+
+    def close(self):
+        if self._h:
+            lib.gab_mix_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fdtd_default_params(nx, ny=None, nz=None):
     P = FdtdParams()
     check(lib.gab_fdtd_default_params(nx, nx if ny is None else ny, nx if nz is None else nz,

@@ -522,6 +522,59 @@ int gab_eq_process_sequential(gab_eq_plan* plan, const float* d_in, float* d_out
 int gab_eq_state(gab_eq_plan* plan, float** d_state, size_t* n_floats);
 int gab_eq_form(const gab_eq_plan* plan, int* samples_per_lane, int* segments);
 
+/* ---- mix bus: tracks summed into buses with ramped gains, in a fixed order (additive; no counterpart in the
+ * reference, whose kernels are per track) ---------------------------------------------------------------------
+ * out[m][s] = sum over t of g[t][m] x[t][s]: `tracks` channels into `buses` buses (1..64), a linear gain per
+ * (track, bus).
+ *   gains          device, [tracks][buses] float32.  The plan carries two matrices: `current` (what the last processed
+ *                  sample was mixed with) and `target`; a new plan has both zero: silence.
+ *     set_gains(ramp = 1)  target := the new matrix, current stays.  The next processed buffer is mixed with
+ *                  g(t, m, s) = fmaf(target - current, r[s], current), r[s] = (s + 1) / bufsize (a table made on the
+ *                  host in float64, rounded once, uploaded at creation: no device division enters the bits); after
+ *                  that buffer current := target exactly.  Two sets before a buffer: the ramp still starts from
+ *                  current, the audible gains.
+ *     set_gains(ramp = 0)  current := target := the new matrix, at once.
+ *     set_gains_tracks     the same for rows [first_track, first_track + n_tracks), d_gains [n_tracks][buses]; the other
+ *                  rows keep their current and target.
+ *                  A value that is not finite: GAB_ERR_INVALID_ARG naming the first such (track, bus); the plan keeps
+ *                  what it had.  Both are synchronous with respect to `stream` and take effect with the next buffer.
+ *     reset        current := target (a pending ramp is dropped).      gains: the plan's own two arrays, for inspection.
+ *   process        one buffer.  d_out is bus-major [m*B + s] (track-major with the buses as tracks: a bus can go straight
+ *                  into a gab_eq_plan of `buses` tracks).  d_in in either layout, named by `layout`; the two layouts
+ *                  give the same bits for the same samples.  d_in and d_out must not overlap.  Any bufsize, any
+ *                  tracks, any alignment: 16-byte aligned pointers with bufsize a multiple of 4 take the fast
+ *                  kernels, everything else a general kernel with the same bits.
+ *   process_batch  n_buffers buffers back to back ([n][T*B] in, [n][M*B] out) in one launch; a pending ramp runs through
+ *                  the first of them; same bits as n calls of process.  One launch takes as many buffers as the plan's
+ *                  workspace holds partial sums for (sized at creation: 32 MiB's worth, at least 1 and at most 64
+ *                  buffers; plans of up to 256 tracks need none and take 64); a longer batch is that many per launch,
+ *                  one launch after the other.  process and process_batch allocate nothing and wait for nothing.
+ * The bits of one output, with g = target[t][m] on a buffer without a pending ramp and the ramp formula on a buffer
+ * with one (then for every track, also those whose row did not move):
+ *   1. leaf:  leaf_tracks consecutive tracks, acc = 0.0f; for t ascending: acc = fmaf(g, x[t][s], acc);
+ *   2. group: group_leaves consecutive leaves added in ascending order with plain float adds, from the first leaf's value;
+ *   3. the groups added in ascending order the same way.  A last leaf or group may be short.
+ * No float atomics: the order is a function of the indices alone.  leaf_tracks and group_leaves are fixed at creation
+ * from (bufsize, buses) alone — never from tracks, the layout, the device or the batch length — and gab_mix_form
+ * reports them: a plan's bits are the same on every box, and one restatement of the three steps above, given those two
+ * integers, is the kernel's bits for every shape.
+ * tracks >= 1, bufsize >= 1, 1 <= buses <= 64; arguments are checked before any device call.  One thread at a time
+ * per plan.                                                                                                          */
+typedef struct gab_mix_plan gab_mix_plan;
+#define GAB_MIX_TRACK_MAJOR  0   /* d_in [t*B + s]: what gab_eq_process, gab_gain, gab_iir write */
+#define GAB_MIX_SAMPLE_MAJOR 1   /* d_in [T*s + t]: what gab_conv_process writes                 */
+int gab_mix_create(gab_mix_plan** plan, int tracks, int bufsize, int buses);
+int gab_mix_destroy(gab_mix_plan* plan);
+int gab_mix_set_gains(gab_mix_plan* plan, const float* d_gains, int ramp, gab_stream_t stream);
+int gab_mix_set_gains_tracks(gab_mix_plan* plan, const float* d_gains, int first_track, int n_tracks, int ramp,
+                             gab_stream_t stream);
+int gab_mix_reset(gab_mix_plan* plan, gab_stream_t stream);
+int gab_mix_process(gab_mix_plan* plan, const float* d_in, float* d_out, int layout, gab_stream_t stream);
+int gab_mix_process_batch(gab_mix_plan* plan, const float* d_in, float* d_out, int n_buffers, int layout,
+                          gab_stream_t stream);
+int gab_mix_gains(gab_mix_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_mix_form(const gab_mix_plan* plan, int* leaf_tracks, int* group_leaves);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
