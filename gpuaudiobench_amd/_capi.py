@@ -23,6 +23,8 @@ CONV_SCHEME_SPLIT = 1
 CONV_SCHEME_FDL = 2
 MIX_TRACK_MAJOR = 0
 MIX_SAMPLE_MAJOR = 1
+DELAY_LINEAR = 0
+DELAY_LAGRANGE3 = 1
 DWG_NAIVE = 0
 DWG_ACCEL = 1
 
@@ -167,6 +169,15 @@ PROTOTYPES = {
     "gab_mix_process_batch": (_I, [_P, _P, _P, _I, _I, _P]),
     "gab_mix_gains": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_mix_form": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "gab_delay_create": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
+    "gab_delay_destroy": (_I, [_P]),
+    "gab_delay_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_delay_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_delay_reset": (_I, [_P, _P]),
+    "gab_delay_process": (_I, [_P, _P, _P, _P]),
+    "gab_delay_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_delay_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_delay_line": (_I, [_P, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_P)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

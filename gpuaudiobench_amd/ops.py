@@ -629,6 +629,88 @@ class MixPlan:
             pass
 
 
+class DelayPlan:
+    """gab_delay_plan: a delay line per track, read at a fractional position (interp "linear" or "lagrange3"), with a
+    feedback path.  Parameters per track {delay (samples), feedback, wet, dry}; a new plan is pass-through; new
+    parameters are ramped in over the next buffer unless ramp=False."""
+
+    _INTERP = {"linear": 0, "lagrange3": 1}
+
+    def __init__(self, tracks, bufsize, max_delay, interp="linear"):
+        if interp not in self._INTERP:
+            raise ValueError("interp must be 'linear' or 'lagrange3'")
+        self.tracks, self.bufsize, self.max_delay, self.interp = tracks, bufsize, max_delay, interp
+        self.min_delay = 2 if interp == "lagrange3" else 1
+        self._h = C.c_void_p()
+        check(lib.gab_delay_create(C.byref(self._h), tracks, bufsize, max_delay, self._INTERP[interp]))
+
+    def set_params(self, params, ramp=True, first_track=0):
+        """params: device tensor [n][4] = {delay, feedback, wet, dry} for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n, rest = divmod(params.numel(), 4)
+        if rest or n == 0:
+            raise ValueError("params must hold whole rows of 4 values")
+        if first_track == 0 and n == self.tracks:
+            check(lib.gab_delay_set_params(self._h, _dev(params), 1 if ramp else 0, _stream()))
+        else:
+            check(lib.gab_delay_set_params_tracks(self._h, _dev(params), first_track, n, 1 if ramp else 0, _stream()))
+
+    def reset(self):
+        """Zero lines, current := target, a pending ramp dropped."""
+        check(lib.gab_delay_reset(self._h, _stream()))
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize]; out may be x itself."""
+        assert x.numel() == self.tracks * self.bufsize
+        out = torch.empty_like(x) if out is None else out
+        assert out.numel() == x.numel()
+        check(lib.gab_delay_process(self._h, _dev(x), _dev(out), _stream()))
+        return out
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch."""
+        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
+        assert rest == 0
+        out = torch.empty_like(xs) if out is None else out
+        assert out.numel() == xs.numel()
+        check(lib.gab_delay_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][4]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_delay_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return _view(a.value, self.tracks, 4).clone(), _view(b.value, self.tracks, 4).clone()
+
+    def line(self):
+        """Copies of (ring [tracks][capacity] float32, write positions [tracks] int64)."""
+        r, p, cap = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_delay_line(self._h, C.byref(r), C.byref(cap), C.byref(p)))
+        ring = _view(r.value, self.tracks, cap.value).clone()
+        pos = _view(p.value, self.tracks, 1).clone().view(torch.int32).to(torch.int64).view(self.tracks)
+        return ring, pos
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
+        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        return (self._h, _dev(x), _dev(out), st)
+
+    @staticmethod
+    def launch(args):
+        check(lib.gab_delay_process(*args))
+
+    def close(self):
+        if self._h:
+            lib.gab_delay_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fdtd_default_params(nx, ny=None, nz=None):
     P = FdtdParams()
     check(lib.gab_fdtd_default_params(nx, nx if ny is None else ny, nx if nz is None else nz,

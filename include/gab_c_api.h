@@ -575,6 +575,76 @@ int gab_mix_process_batch(gab_mix_plan* plan, const float* d_in, float* d_out, i
 int gab_mix_gains(gab_mix_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_mix_form(const gab_mix_plan* plan, int* leaf_tracks, int* group_leaves);
 
+/* ---- delay: a delay line per track, read at a fractional position, with feedback and ramped parameters (additive;
+ * the reference's waveguide has fixed integer lengths and its own reflection rule) ------------------------------
+ * Latency compensation and pre-delay (feedback 0), echo and comb (feedback), chorus and flanger (a delay that moves).
+ *   parameters     device, [tracks][4] float32 = {delay, feedback, wet, dry}, delay in samples.  The plan carries two
+ *                  tables, `current` and `target`; a new plan has {min_delay, 0, 0, 1} in both on every track
+ *                  (pass-through) and a zero line.
+ *     set_params(ramp = 1)  target := the new table, current stays.  On the next processed buffer every parameter p of
+ *                  every track is p[s] = fmaf(target - current, r[s], current), r[s] = (s + 1) / bufsize (a table made on
+ *                  the host in float64, rounded once, uploaded at creation; target - current rounded once); after that
+ *                  buffer current := target by a copy.  Two sets before a buffer: the ramp still starts from current.
+ *     set_params(ramp = 0)  current := target := the new table, at once.
+ *     set_params_tracks     the same for rows [first_track, first_track + n_tracks), d_params [n_tracks][4]; the other
+ *                  rows keep their current and target.
+ *                  The values are checked on the device first: every value finite, min_delay <= delay <= max_delay,
+ *                  |feedback| < 1.  A violation: GAB_ERR_INVALID_ARG naming the first (track, field) in index order
+ *                  (field 0 delay, 1 feedback, 2 wet, 3 dry); the plan keeps what it had.  Both calls are synchronous
+ *                  with respect to `stream` and take effect with the next buffer.
+ *     reset        the lines and write positions zero, current := target, a pending ramp dropped: the stream that
+ *                  follows is a new plan's with the same target.
+ *     params       the plan's own two tables, for inspection.
+ *     line         the ring's base ([tracks][capacity] float32), the capacity (a power of two >= max_delay + 3 +
+ *                  bufsize) and the per-track write positions ([tracks] unsigned: the ring index of the next sample),
+ *                  for inspection.
+ *   process        one buffer, track-major [t*B + s] in and out, as gab_eq_process takes and writes.  d_out == d_in is
+ *                  allowed (no other overlap).  Any bufsize, any alignment, any track count: the same bits.
+ *   process_batch  n_buffers buffers back to back ([n][T*B]) in one launch; a pending ramp runs through the first of
+ *                  them; same bits as n calls of process.  process and process_batch allocate nothing and wait for
+ *                  nothing; the write position is device state.
+ * The bits of one sample.  On a buffer without a pending ramp p = target, on one with a ramp the formula above, for all
+ * four parameters.  Then the delay, and only the delay, is clamped: d = fminf(fmaxf(d, min_delay), max_delay).  The
+ * clamp is a guard that is part of the bits: a tap below min_delay would read the sample being written, so the kernel
+ * does not rest on an argument about roundings.  For the tables set_params admits it never acts downwards (min_delay -
+ * current is a float32 and rounding is monotone, so the ramp's value is at least min_delay for every r in (0, 1]); a
+ * ramp's value between its ends is simply kept inside [min_delay, max_delay].  For absolute sample n of a track, x the input, w the line (zero before
+ * the first sample and after a reset):
+ *     i  = (int)floorf(d);   fr = d - (float)i                      (exact)
+ *     GAB_DELAY_LINEAR (min_delay 1):
+ *       a = w[n-i];  b = w[n-i-1];   v = fmaf(fr, b - a, a)         (b - a rounded once)
+ *     GAB_DELAY_LAGRANGE3 (min_delay 2), the third-order Lagrange weights of the points -1, 0, 1, 2 at fr, every
+ *     difference, sum and product below rounded once, products taken left to right, fmaf only where written:
+ *       am = w[n-i+1];  a = w[n-i];  b = w[n-i-1];  b2 = w[n-i-2]
+ *       fm1 = fr - 1;   fm2 = fr - 2;   fp1 = fr + 1;   c6 = (float)(1.0 / 6.0)
+ *       hm = ((fr  * fm1) * fm2) * (-c6)          h0 = ((fp1 * fm1) * fm2) * 0.5f
+ *       h1 = ((fp1 * fr ) * fm2) * (-0.5f)        h2 = ((fp1 * fr ) * fm1) * c6
+ *       v = hm * am;   v = fmaf(h1, b, v);   v = fmaf(h2, b2, v);   v = fmaf(h0, a, v)
+ *     (fr == 0: hm, h1, h2 are zeros and h0 is exactly 1, so v == w[n-i].)
+ *     w[n] = fmaf(feedback, v, x[n])                                what enters the line
+ *     y[n] = fmaf(wet, v, dry * x[n])                               the output (dry * x[n] rounded once)
+ * Nothing else has rounding freedom: every launch form gives the same bits, and a shard of tracks as its own plan gives
+ * those tracks' bits.  Precision: delay is a float32, so a delay near 2^17 samples resolves 2^-7 of a sample.
+ * Stability: |feedback| < 1 bounds a linear line (its two weights are non-negative and sum to 1, loop gain |feedback|).
+ * The Lagrange weights sum to 1 but their magnitudes sum to up to 1.25 (at fr = 0.5), so a worst-case signal sees a loop
+ * gain of 1.25 |feedback|: only |feedback| < 0.8 bounds a Lagrange line's level and rounding-error growth for every
+ * input.  Above that a value is admitted, but |feedback| < 1 alone does not give such a bound.
+ * tracks >= 1, bufsize >= 1, min_delay <= max_delay <= 2^20; arguments are checked before any device call.  One thread
+ * at a time per plan.                                                                                               */
+typedef struct gab_delay_plan gab_delay_plan;
+#define GAB_DELAY_LINEAR    0   /* two-point interpolation, min_delay 1  */
+#define GAB_DELAY_LAGRANGE3 1   /* four-point interpolation, min_delay 2 */
+int gab_delay_create(gab_delay_plan** plan, int tracks, int bufsize, int max_delay, int interp);
+int gab_delay_destroy(gab_delay_plan* plan);
+int gab_delay_set_params(gab_delay_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_delay_set_params_tracks(gab_delay_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                                gab_stream_t stream);
+int gab_delay_reset(gab_delay_plan* plan, gab_stream_t stream);
+int gab_delay_process(gab_delay_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_delay_process_batch(gab_delay_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_delay_line(gab_delay_plan* plan, float** d_ring, size_t* capacity, unsigned** d_pos);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
