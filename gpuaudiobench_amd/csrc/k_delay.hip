@@ -17,10 +17,11 @@
 
 #include <climits>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "gab_common.hpp"
+#include "gab_plan.hpp"
 
 namespace gab {
 namespace {
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(256) void delay_check_kernel(const float* __restric
     if (i >= n) return;
     const float v = src[i];
     const int field = (int)(i & 3);
-    bool bad = (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u;
+    bool bad = not_finite(__float_as_uint(v));
     if (field == 0) bad = bad || !(v >= dmin && v <= dmax);
     if (field == 1) bad = bad || !(fabsf(v) < 1.0f);
     if (bad) atomicMin(flag, (unsigned)i);
@@ -259,13 +260,10 @@ __global__ __launch_bounds__(256) void delay_check_kernel(const float* __restric
 struct gab_delay_plan {
     int tracks = 0, bufsize = 0, max_delay = 0, interp = 0, min_delay = 0;
     size_t capacity = 0;               // floats of a track's ring: a power of two >= max_delay + 3 + bufsize
-    bool pending = false;              // a ramp from current to target waits for the next buffer
-    float* d_current = nullptr;        // [T][4]
-    float* d_target = nullptr;         // [T][4]
-    float* d_ramp = nullptr;           // [B]: (s + 1) / B
-    float* d_ring = nullptr;           // [T][capacity]
-    unsigned* d_pos = nullptr;         // [T]: the ring index of the next sample
-    unsigned* d_flag = nullptr;
+    gab::RampedTable params;           // current, target: [T][4]
+    gab::DeviceBuf<float> ring;        // [T][capacity]
+    gab::DeviceBuf<unsigned> pos;      // [T]: the ring index of the next sample
+    gab::DeviceBuf<unsigned> flag;
 };
 
 namespace gab {
@@ -279,11 +277,11 @@ int delay_process(gab_delay_plan* p, const float* d_in, float* d_out, int n_buff
     const dim3 grid((unsigned)((p->tracks + kDelayWaves - 1) / kDelayWaves));
     const unsigned mask = (unsigned)(p->capacity - 1);
     const float dmin = (float)p->min_delay, dmax = (float)p->max_delay;
-    const bool ramp = p->pending;
+    const bool ramp = p->params.pending;
 #define GAB_DELAY(LL, RR)                                                                                           \
-    delay_kernel<LL, RR><<<grid, kDelayWaves * 64, 0, s>>>(d_in, d_out, p->d_ring, p->d_pos, p->d_current,         \
-                                                            p->d_target, p->d_ramp, p->tracks, p->bufsize, n_buffers, \
-                                                            mask, dmin, dmax)
+    delay_kernel<LL, RR><<<grid, kDelayWaves * 64, 0, s>>>(                                                        \
+        d_in, d_out, p->ring.get(), p->pos.get(), p->params.current.get(), p->params.target.get(),                 \
+        p->params.ramp.get(), p->tracks, p->bufsize, n_buffers, mask, dmin, dmax)
     if (p->interp == GAB_DELAY_LAGRANGE3) {
         if (ramp) GAB_DELAY(true, true); else GAB_DELAY(true, false);
     } else {
@@ -291,27 +289,22 @@ int delay_process(gab_delay_plan* p, const float* d_in, float* d_out, int n_buff
     }
 #undef GAB_DELAY
     if (int rc = launch_status("delay_kernel")) return rc;
-    if (ramp) {
-        GAB_HIP_CHECK(hipMemcpyAsync(p->d_current, p->d_target, (size_t)p->tracks * 4 * sizeof(float),
-                                     hipMemcpyDeviceToDevice, s));
-        p->pending = false;
-    }
+    if (ramp) p->params.snap(s);
     return GAB_OK;
 }
 
-// check, then commit: a refused set leaves both tables as they were.
+// check, then commit (gab_plan.hpp): a refused set leaves both tables and a pending ramp as they were.
 int delay_set_range(gab_delay_plan* p, const float* d_params, int first_track, int n_tracks, int ramp, hipStream_t s,
                     const char* who) {
     const size_t n = (size_t)n_tracks * 4;
-    if (n > 0xfffffff0u) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = 0xffffffffu;
-    GAB_HIP_CHECK(hipMemsetAsync(p->d_flag, 0xff, sizeof(unsigned), s));
-    delay_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_params, p->d_flag, n, (float)p->min_delay,
-                                                                         (float)p->max_delay);
-    if (int rc = launch_status("delay_check_kernel")) return rc;
-    GAB_HIP_CHECK(hipMemcpyAsync(&first_bad, p->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
-    if (first_bad != 0xffffffffu) {
+    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
+    unsigned first_bad = kNoneRefused;
+    if (int rc = first_refused(p->flag, s, "delay_check_kernel", [&] {
+            delay_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_params, p->flag.get(), n,
+                                                                                 (float)p->min_delay, (float)p->max_delay);
+        }, &first_bad))
+        return rc;
+    if (first_bad != kNoneRefused) {
         const int field = (int)(first_bad & 3u);
         const char* rule = field == 0 ? "must be finite and within [min_delay, max_delay]"
                                       : (field == 1 ? "must be finite and below 1 in magnitude" : "must be finite");
@@ -320,25 +313,8 @@ int delay_set_range(gab_delay_plan* p, const float* d_params, int first_track, i
                        "; the plan keeps its parameters");
         return GAB_ERR_INVALID_ARG;
     }
-    const size_t off = (size_t)first_track * 4;
-    GAB_HIP_CHECK(hipMemcpyAsync(p->d_target + off, d_params, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (ramp) {
-        p->pending = true;
-    } else {
-        GAB_HIP_CHECK(hipMemcpyAsync(p->d_current + off, d_params, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
+    p->params.commit(d_params, (size_t)first_track * 4, n, ramp != 0, s);
     return GAB_OK;
-}
-
-void delay_free(gab_delay_plan* p) {
-    if (p->d_current) (void)hipFree(p->d_current);
-    if (p->d_target) (void)hipFree(p->d_target);
-    if (p->d_ramp) (void)hipFree(p->d_ramp);
-    if (p->d_ring) (void)hipFree(p->d_ring);
-    if (p->d_pos) (void)hipFree(p->d_pos);
-    if (p->d_flag) (void)hipFree(p->d_flag);
-    delete p;
 }
 
 }  // namespace
@@ -360,36 +336,25 @@ int gab_delay_create(gab_delay_plan** out, int tracks, int bufsize, int max_dela
         while (cap < (size_t)max_delay + 3 + (size_t)bufsize) cap *= 2;
         if (cap > ((size_t)1 << 31)) return gab::bad_arg("gab_delay_create: bufsize is too large for a track's ring");
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_delay_create")) return rc;
-        auto* p = new gab_delay_plan;
+        auto p = std::make_unique<gab_delay_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->max_delay = max_delay; p->interp = interp;
         p->min_delay = min_delay; p->capacity = cap;
-        try {
-            const size_t n = (size_t)tracks * 4;
-            GAB_HIP_CHECK(hipMalloc(&p->d_current, n * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_target, n * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_ramp, (size_t)bufsize * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_ring, (size_t)tracks * cap * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_pos, (size_t)tracks * sizeof(unsigned)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_flag, sizeof(unsigned)));
-            // pass-through: {min_delay, 0, 0, 1} on every track, an empty line
-            std::vector<float> init(n);
-            for (int t = 0; t < tracks; ++t) {
-                init[(size_t)t * 4 + 0] = (float)min_delay; init[(size_t)t * 4 + 1] = 0.0f;
-                init[(size_t)t * 4 + 2] = 0.0f;             init[(size_t)t * 4 + 3] = 1.0f;
-            }
-            GAB_HIP_CHECK(hipMemcpy(p->d_current, init.data(), n * sizeof(float), hipMemcpyHostToDevice));
-            GAB_HIP_CHECK(hipMemcpy(p->d_target, init.data(), n * sizeof(float), hipMemcpyHostToDevice));
-            GAB_HIP_CHECK(hipMemset(p->d_ring, 0, (size_t)tracks * cap * sizeof(float)));
-            GAB_HIP_CHECK(hipMemset(p->d_pos, 0, (size_t)tracks * sizeof(unsigned)));
-            // r[s] = (s + 1) / B in float64, rounded once: no device division enters the bits
-            std::vector<float> r((size_t)bufsize);
-            for (int s = 0; s < bufsize; ++s) r[(size_t)s] = (float)(((double)s + 1.0) / (double)bufsize);
-            GAB_HIP_CHECK(hipMemcpy(p->d_ramp, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
-        } catch (...) {
-            gab::delay_free(p);
-            throw;
+        const size_t n = (size_t)tracks * 4;
+        p->params.create(n, bufsize);
+        p->ring.alloc((size_t)tracks * cap);
+        p->pos.alloc((size_t)tracks);
+        p->flag.alloc(1);
+        // pass-through: {min_delay, 0, 0, 1} on every track, an empty line
+        std::vector<float> init(n);
+        for (int t = 0; t < tracks; ++t) {
+            init[(size_t)t * 4 + 0] = (float)min_delay; init[(size_t)t * 4 + 1] = 0.0f;
+            init[(size_t)t * 4 + 2] = 0.0f;             init[(size_t)t * 4 + 3] = 1.0f;
         }
-        *out = p;
+        GAB_HIP_CHECK(hipMemcpy(p->params.current.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemcpy(p->params.target.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, (size_t)tracks * cap * sizeof(float)));
+        GAB_HIP_CHECK(hipMemset(p->pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
+        *out = p.release();
         return GAB_OK;
     });
 }
@@ -397,7 +362,7 @@ int gab_delay_create(gab_delay_plan** out, int tracks, int bufsize, int max_dela
 int gab_delay_destroy(gab_delay_plan* plan) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_delay_destroy: null pointer");
-        gab::delay_free(plan);
+        delete plan;
         return GAB_OK;
     });
 }
@@ -414,7 +379,7 @@ int gab_delay_set_params_tracks(gab_delay_plan* plan, const float* d_params, int
                                 gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_params) return gab::bad_arg("gab_delay_set_params_tracks: null pointer");
-        if (first_track < 0 || n_tracks <= 0 || first_track > plan->tracks - n_tracks)
+        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
             return gab::bad_arg("gab_delay_set_params_tracks: the track range is outside the plan");
         return gab::delay_set_range(plan, d_params, first_track, n_tracks, ramp, gab::as_stream(stream),
                                     "gab_delay_set_params_tracks");
@@ -425,11 +390,9 @@ int gab_delay_reset(gab_delay_plan* plan, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_delay_reset: null pointer");
         hipStream_t s = gab::as_stream(stream);
-        GAB_HIP_CHECK(hipMemsetAsync(plan->d_ring, 0, (size_t)plan->tracks * plan->capacity * sizeof(float), s));
-        GAB_HIP_CHECK(hipMemsetAsync(plan->d_pos, 0, (size_t)plan->tracks * sizeof(unsigned), s));
-        GAB_HIP_CHECK(hipMemcpyAsync(plan->d_current, plan->d_target, (size_t)plan->tracks * 4 * sizeof(float),
-                                     hipMemcpyDeviceToDevice, s));
-        plan->pending = false;
+        GAB_HIP_CHECK(hipMemsetAsync(plan->ring.get(), 0, plan->ring.size() * sizeof(float), s));
+        GAB_HIP_CHECK(hipMemsetAsync(plan->pos.get(), 0, plan->pos.size() * sizeof(unsigned), s));
+        plan->params.snap(s);
         return GAB_OK;
     });
 }
@@ -452,9 +415,9 @@ int gab_delay_process_batch(gab_delay_plan* plan, const float* d_in, float* d_ou
 int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_delay_params: null pointer");
-        *d_current = plan->d_current;
-        *d_target = plan->d_target;
-        *n_floats = (size_t)plan->tracks * 4;
+        *d_current = plan->params.current.get();
+        *d_target = plan->params.target.get();
+        *n_floats = plan->params.current.size();
         return GAB_OK;
     });
 }
@@ -462,9 +425,9 @@ int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, 
 int gab_delay_line(gab_delay_plan* plan, float** d_ring, size_t* capacity, unsigned** d_pos) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_ring || !capacity || !d_pos) return gab::bad_arg("gab_delay_line: null pointer");
-        *d_ring = plan->d_ring;
+        *d_ring = plan->ring.get();
         *capacity = plan->capacity;
-        *d_pos = plan->d_pos;
+        *d_pos = plan->pos.get();
         return GAB_OK;
     });
 }

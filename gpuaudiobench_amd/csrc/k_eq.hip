@@ -9,9 +9,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <string>
 
-#include "gab_common.hpp"
+#include "gab_plan.hpp"
 
 namespace gab {
 namespace {
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void eq_consts_kernel(const float* __restrict_
         for (int k = 0; k < 5; ++k) c[k] = src[(size_t)idx * 5 + k];
     if (!commit) {
         bool ok = true;
-        for (int k = 0; k < 5; ++k) ok = ok && (__float_as_uint(c[k]) & 0x7f800000u) != 0x7f800000u;
+        for (int k = 0; k < 5; ++k) ok = ok && !not_finite(__float_as_uint(c[k]));
         const double a1 = c[3], a2 = c[4];
         ok = ok && fabs(a2) < 1.0 && fabs(a1) < 1.0 + a2;
         if (!ok) atomicMin(flag, (unsigned)idx);
@@ -320,9 +321,9 @@ struct gab_eq_plan {
     int tracks = 0, bufsize = 0, sections = 0;
     int M = 0, H = 0;                  // the scan's form; 0, 0: the sequential kernel only
     int row_words = 0;
-    float* d_table = nullptr;          // [T][S][row_words]
-    float* d_state = nullptr;          // [T][S][2]
-    unsigned* d_flag = nullptr;
+    gab::DeviceBuf<float> table;       // [T][S][row_words]
+    gab::DeviceBuf<float> state;       // [T][S][2]
+    gab::DeviceBuf<unsigned> flag;
 };
 
 namespace gab {
@@ -332,8 +333,8 @@ int eq_launch_scan(const gab_eq_plan* p, const float* d_in, float* d_out, int n_
     const dim3 grid((p->tracks + 3) / 4);
     const int T = p->tracks, S = p->sections;
 #define GAB_EQ_SCAN(MV, HV)                                                                                      \
-    eq_scan_kernel<MV, HV><<<grid, 256, 0, s>>>(d_in, d_out, p->d_state,                                        \
-                                                reinterpret_cast<const EqRow<MV>*>(p->d_table), T, S, n_buffers)
+    eq_scan_kernel<MV, HV><<<grid, 256, 0, s>>>(d_in, d_out, p->state.get(),                                    \
+                                                reinterpret_cast<const EqRow<MV>*>(p->table.get()), T, S, n_buffers)
     switch (p->M * 16 + p->H) {
         case 1 * 16 + 1: GAB_EQ_SCAN(1, 1); break;
         case 2 * 16 + 1: GAB_EQ_SCAN(2, 1); break;
@@ -352,8 +353,8 @@ int eq_launch_scan(const gab_eq_plan* p, const float* d_in, float* d_out, int n_
 
 int eq_launch_sequential(const gab_eq_plan* p, const float* d_in, float* d_out, hipStream_t s) {
     const dim3 grid((p->tracks + kEqTracks - 1) / kEqTracks);
-    eq_sequential_kernel<<<grid, 256, 0, s>>>(d_in, d_out, p->d_state, p->d_table, p->row_words, p->tracks,
-                                              p->bufsize, p->sections);
+    eq_sequential_kernel<<<grid, 256, 0, s>>>(d_in, d_out, p->state.get(), p->table.get(), p->row_words,
+                                              p->tracks, p->bufsize, p->sections);
     return launch_status("eq_sequential_kernel");
 }
 
@@ -361,38 +362,28 @@ bool eq_aligned(const void* a, const void* b) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
 }
 
-// check, then commit: a refused set leaves the table as it was.  src null: the identity filter.
+// check, then commit (gab_plan.hpp): a refused set leaves the table as it was.  src null: the identity filter.
 int eq_set_range(gab_eq_plan* p, const float* d_coeffs, int first_track, int n_tracks, hipStream_t s, const char* who) {
     const int S = p->sections;
     const long long n = (long long)n_tracks * S;
-    const dim3 grid((unsigned)((n + 255) / 256));
+    auto launch = [&](int commit) {
+        eq_consts_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(
+            d_coeffs, p->table.get(), p->flag.get(), first_track, n_tracks, S, p->M ? p->M : 1, p->row_words, commit);
+    };
     if (d_coeffs) {
-        unsigned first_bad = 0xffffffffu;
-        GAB_HIP_CHECK(hipMemsetAsync(p->d_flag, 0xff, sizeof(unsigned), s));
-        eq_consts_kernel<<<grid, 256, 0, s>>>(d_coeffs, p->d_table, p->d_flag, first_track, n_tracks, S,
-                                              p->M ? p->M : 1, p->row_words, 0);
-        if (int rc = launch_status("eq_consts_kernel")) return rc;
-        GAB_HIP_CHECK(hipMemcpyAsync(&first_bad, p->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        GAB_HIP_CHECK(hipStreamSynchronize(s));
-        if (first_bad != 0xffffffffu) {
+        unsigned first_bad = kNoneRefused;
+        if (int rc = first_refused(p->flag, s, "eq_consts_kernel", [&] { launch(0); }, &first_bad)) return rc;
+        if (first_bad != kNoneRefused) {
             set_last_error(std::string(who) + ": track " + std::to_string(first_track + (int)(first_bad / (unsigned)S)) +
                            " section " + std::to_string((int)(first_bad % (unsigned)S)) +
                            " is unstable (needs |a2| < 1 and |a1| < 1 + a2) or not finite; the plan keeps its coefficients");
             return GAB_ERR_INVALID_ARG;
         }
     }
-    eq_consts_kernel<<<grid, 256, 0, s>>>(d_coeffs, p->d_table, p->d_flag, first_track, n_tracks, S,
-                                          p->M ? p->M : 1, p->row_words, 1);
+    launch(1);
     if (int rc = launch_status("eq_consts_kernel")) return rc;
     GAB_HIP_CHECK(hipStreamSynchronize(s));
     return GAB_OK;
-}
-
-void eq_free(gab_eq_plan* p) {
-    if (p->d_table) (void)hipFree(p->d_table);
-    if (p->d_state) (void)hipFree(p->d_state);
-    if (p->d_flag) (void)hipFree(p->d_flag);
-    delete p;
 }
 
 }  // namespace
@@ -407,25 +398,17 @@ int gab_eq_create(gab_eq_plan** out, int tracks, int bufsize, int sections) {
         if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_eq_create: tracks and bufsize must be > 0");
         if (sections < 1 || sections > gab::kEqMaxSections) return gab::bad_arg("gab_eq_create: sections must be 1..16");
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_eq_create")) return rc;
-        auto* p = new gab_eq_plan;
+        auto p = std::make_unique<gab_eq_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->sections = sections;
         gab::eq_pick_form(bufsize, sections, &p->M, &p->H);
         p->row_words = gab::eq_row_words(p->M ? p->M : 1);
-        try {
-            const size_t n = (size_t)tracks * sections;
-            GAB_HIP_CHECK(hipMalloc(&p->d_table, n * p->row_words * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_state, n * 2 * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_flag, sizeof(unsigned)));
-            GAB_HIP_CHECK(hipMemset(p->d_state, 0, n * 2 * sizeof(float)));
-            if (int rc = gab::eq_set_range(p, nullptr, 0, tracks, nullptr, "gab_eq_create")) {   // the identity filter
-                gab::eq_free(p);
-                return rc;
-            }
-        } catch (...) {
-            gab::eq_free(p);
-            throw;
-        }
-        *out = p;
+        const size_t n = (size_t)tracks * sections;
+        p->table.alloc(n * p->row_words);
+        p->state.alloc(n * 2);
+        p->flag.alloc(1);
+        GAB_HIP_CHECK(hipMemset(p->state.get(), 0, n * 2 * sizeof(float)));
+        if (int rc = gab::eq_set_range(p.get(), nullptr, 0, tracks, nullptr, "gab_eq_create")) return rc;   // identity
+        *out = p.release();
         return GAB_OK;
     });
 }
@@ -433,7 +416,7 @@ int gab_eq_create(gab_eq_plan** out, int tracks, int bufsize, int sections) {
 int gab_eq_destroy(gab_eq_plan* plan) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_eq_destroy: null plan");
-        gab::eq_free(plan);
+        delete plan;
         return GAB_OK;
     });
 }
@@ -441,7 +424,7 @@ int gab_eq_destroy(gab_eq_plan* plan) {
 int gab_eq_set_coeffs_tracks(gab_eq_plan* plan, const float* d_coeffs, int first_track, int n_tracks, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_coeffs) return gab::bad_arg("gab_eq_set_coeffs_tracks: null pointer");
-        if (first_track < 0 || n_tracks <= 0 || first_track > plan->tracks - n_tracks)
+        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
             return gab::bad_arg("gab_eq_set_coeffs_tracks: the track range is outside the plan");
         return gab::eq_set_range(plan, d_coeffs, first_track, n_tracks, gab::as_stream(stream), "gab_eq_set_coeffs_tracks");
     });
@@ -457,8 +440,7 @@ int gab_eq_set_coeffs(gab_eq_plan* plan, const float* d_coeffs, gab_stream_t str
 int gab_eq_reset(gab_eq_plan* plan, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_eq_reset: null plan");
-        GAB_HIP_CHECK(hipMemsetAsync(plan->d_state, 0, (size_t)plan->tracks * plan->sections * 2 * sizeof(float),
-                                     gab::as_stream(stream)));
+        GAB_HIP_CHECK(hipMemsetAsync(plan->state.get(), 0, plan->state.size() * sizeof(float), gab::as_stream(stream)));
         return GAB_OK;
     });
 }
@@ -497,8 +479,8 @@ int gab_eq_process_batch(gab_eq_plan* plan, const float* d_in, float* d_out, int
 int gab_eq_state(gab_eq_plan* plan, float** d_state, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_state || !n_floats) return gab::bad_arg("gab_eq_state: null pointer");
-        *d_state = plan->d_state;
-        *n_floats = (size_t)plan->tracks * plan->sections * 2;
+        *d_state = plan->state.get();
+        *n_floats = plan->state.size();
         return GAB_OK;
     });
 }

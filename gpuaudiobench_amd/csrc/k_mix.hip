@@ -13,10 +13,10 @@
 
 #include <climits>
 #include <cstdint>
+#include <memory>
 #include <string>
-#include <vector>
 
-#include "gab_common.hpp"
+#include "gab_plan.hpp"
 
 namespace gab {
 namespace {
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void mix_check_kernel(const float* __restrict_
                                                        size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if ((__float_as_uint(src[i]) & 0x7f800000u) == 0x7f800000u) atomicMin(flag, (unsigned)i);
+    if (not_finite(__float_as_uint(src[i]))) atomicMin(flag, (unsigned)i);
 }
 
 }  // namespace
@@ -253,13 +253,10 @@ struct gab_mix_plan {
     int tracks = 0, bufsize = 0, buses = 0;
     int leaf_tracks = 0, group_leaves = 0;
     int n_groups = 0;
-    bool pending = false;              // a ramp from current to target waits for the next buffer
-    float* d_current = nullptr;        // [T][M]
-    float* d_target = nullptr;         // [T][M]
-    float* d_ramp = nullptr;           // [B]: (s + 1) / B
-    float* d_part = nullptr;           // [part_buffers][n_groups][M][B]: the groups' partial sums (n_groups > 1 only)
+    gab::RampedTable gains;            // current, target: [T][M]
+    gab::DeviceBuf<float> part;        // [part_buffers][n_groups][M][B]: the groups' partial sums (n_groups > 1 only)
     int part_buffers = 0;              // fixed at creation: how many buffers of a batch one launch takes
-    unsigned* d_flag = nullptr;
+    gab::DeviceBuf<unsigned> flag;
 };
 
 namespace gab {
@@ -276,7 +273,7 @@ int mix_tile(int buses) {
 int mix_launch(gab_mix_plan* p, const float* d_in, float* d_out, int n, int layout, bool ramp_first, hipStream_t s) {
     const int T = p->tracks, B = p->bufsize, M = p->buses, MT = mix_tile(M);
     const bool one = p->n_groups == 1;
-    float* dst = one ? d_out : p->d_part;
+    float* dst = one ? d_out : p->part.get();
     // Samples per lane: speed only, the bits do not depend on it.  As wide as the alignment, the buffer size and the
     // tile allow (V x tile <= 16: beyond that the unrolled tracks' gains no longer fit the scalar registers), but
     // narrower while the launch would have fewer than 512 workgroups: two for each of the MI355X's 256 compute units
@@ -294,8 +291,9 @@ int mix_launch(gab_mix_plan* p, const float* d_in, float* d_out, int n, int layo
     const dim3 grid((unsigned)(n_cols * p->n_groups), 1, (unsigned)n);
     const int threads = p->group_leaves * 64;
 #define GAB_MIX(VV, MM, SS)                                                                                      \
-    mix_kernel<VV, MM, SS><<<grid, threads, 0, s>>>(d_in, dst, p->d_current, p->d_target, p->d_ramp, T, B, M,    \
-                                                    n_cols, p->n_groups, ramp_first ? 1 : 0)
+    mix_kernel<VV, MM, SS><<<grid, threads, 0, s>>>(d_in, dst, p->gains.current.get(), p->gains.target.get(),    \
+                                                    p->gains.ramp.get(), T, B, M, n_cols, p->n_groups,           \
+                                                    ramp_first ? 1 : 0)
     if (layout == GAB_MIX_SAMPLE_MAJOR) {
         switch (MT) {
             case 1: GAB_MIX(1, 1, true); break;
@@ -329,7 +327,7 @@ int mix_launch(gab_mix_plan* p, const float* d_in, float* d_out, int n, int layo
     if (!one) {
         const size_t MB = (size_t)M * B, total = MB * n;
         if ((total + 63) / 64 > (size_t)INT_MAX) return bad_arg("gab_mix_process_batch: the batch is too large for one launch");
-        mix_groups_kernel<<<dim3((unsigned)((total + 63) / 64)), 1024, 0, s>>>(p->d_part, d_out, MB, p->n_groups, total);
+        mix_groups_kernel<<<dim3((unsigned)((total + 63) / 64)), 1024, 0, s>>>(p->part.get(), d_out, MB, p->n_groups, total);
         if (int rc = launch_status("mix_groups_kernel")) return rc;
     }
     return GAB_OK;
@@ -337,57 +335,36 @@ int mix_launch(gab_mix_plan* p, const float* d_in, float* d_out, int n, int layo
 
 int mix_process(gab_mix_plan* p, const float* d_in, float* d_out, int n_buffers, int layout, hipStream_t s) {
     const size_t in_stride = (size_t)p->tracks * p->bufsize, out_stride = (size_t)p->buses * p->bufsize;
-    const bool ramp = p->pending;
+    const bool ramp = p->gains.pending;
     for (int done = 0; done < n_buffers;) {
         const int n = n_buffers - done < p->part_buffers ? n_buffers - done : p->part_buffers;
         if (int rc = mix_launch(p, d_in + done * in_stride, d_out + done * out_stride, n, layout, ramp && done == 0, s))
             return rc;
         done += n;
     }
-    if (ramp) {     // the ramp has run through its buffer: current := target, exactly
-        GAB_HIP_CHECK(hipMemcpyAsync(p->d_current, p->d_target, (size_t)p->tracks * p->buses * sizeof(float),
-                                     hipMemcpyDeviceToDevice, s));
-        p->pending = false;
-    }
+    if (ramp) p->gains.snap(s);     // the ramp has run through its buffer: current := target, exactly
     return GAB_OK;
 }
 
-// check, then commit: a refused set leaves both matrices as they were.
+// check, then commit (gab_plan.hpp): a refused set leaves both matrices and a pending ramp as they were.
 int mix_set_range(gab_mix_plan* p, const float* d_gains, int first_track, int n_tracks, int ramp, hipStream_t s,
                   const char* who) {
     const int M = p->buses;
     const size_t n = (size_t)n_tracks * M;
-    if (n > 0xfffffff0u) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = 0xffffffffu;
-    GAB_HIP_CHECK(hipMemsetAsync(p->d_flag, 0xff, sizeof(unsigned), s));
-    mix_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_gains, p->d_flag, n);
-    if (int rc = launch_status("mix_check_kernel")) return rc;
-    GAB_HIP_CHECK(hipMemcpyAsync(&first_bad, p->d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
-    if (first_bad != 0xffffffffu) {
+    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
+    unsigned first_bad = kNoneRefused;
+    if (int rc = first_refused(p->flag, s, "mix_check_kernel", [&] {
+            mix_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_gains, p->flag.get(), n);
+        }, &first_bad))
+        return rc;
+    if (first_bad != kNoneRefused) {
         set_last_error(std::string(who) + ": the gain of track " + std::to_string(first_track + (int)(first_bad / (unsigned)M)) +
                        " bus " + std::to_string((int)(first_bad % (unsigned)M)) +
                        " is not finite; the plan keeps its gains");
         return GAB_ERR_INVALID_ARG;
     }
-    const size_t off = (size_t)first_track * M;
-    GAB_HIP_CHECK(hipMemcpyAsync(p->d_target + off, d_gains, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (ramp) {
-        p->pending = true;
-    } else {
-        GAB_HIP_CHECK(hipMemcpyAsync(p->d_current + off, d_gains, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
+    p->gains.commit(d_gains, (size_t)first_track * M, n, ramp != 0, s);
     return GAB_OK;
-}
-
-void mix_free(gab_mix_plan* p) {
-    if (p->d_current) (void)hipFree(p->d_current);
-    if (p->d_target) (void)hipFree(p->d_target);
-    if (p->d_ramp) (void)hipFree(p->d_ramp);
-    if (p->d_part) (void)hipFree(p->d_part);
-    if (p->d_flag) (void)hipFree(p->d_flag);
-    delete p;
 }
 
 }  // namespace
@@ -405,34 +382,23 @@ int gab_mix_create(gab_mix_plan** out, int tracks, int bufsize, int buses) {
         if (n_groups * (((long long)bufsize + 63) / 64) > INT_MAX)
             return gab::bad_arg("gab_mix_create: tracks x bufsize is too large for one launch");
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_mix_create")) return rc;
-        auto* p = new gab_mix_plan;
+        auto p = std::make_unique<gab_mix_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->buses = buses;
         gab::mix_pick_form(bufsize, buses, &p->leaf_tracks, &p->group_leaves);
         p->n_groups = (int)n_groups;
-        try {
-            const size_t n = (size_t)tracks * buses;
-            GAB_HIP_CHECK(hipMalloc(&p->d_current, n * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_target, n * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_ramp, (size_t)bufsize * sizeof(float)));
-            GAB_HIP_CHECK(hipMalloc(&p->d_flag, sizeof(unsigned)));
-            // The workspace of the final pass: as many buffers' partial sums as fit 32 MiB, at least one and at most
-            // kMixBatchChunk.  A longer batch is that many buffers per launch, one launch after the other.
-            const size_t per_buffer = (size_t)p->n_groups * buses * bufsize * sizeof(float);
-            size_t chunk = ((size_t)32 << 20) / per_buffer;
-            chunk = chunk < 1 ? 1 : (chunk > (size_t)gab::kMixBatchChunk ? (size_t)gab::kMixBatchChunk : chunk);
-            p->part_buffers = p->n_groups > 1 ? (int)chunk : gab::kMixBatchChunk;
-            if (p->n_groups > 1) GAB_HIP_CHECK(hipMalloc(&p->d_part, chunk * per_buffer));
-            GAB_HIP_CHECK(hipMemset(p->d_current, 0, n * sizeof(float)));
-            GAB_HIP_CHECK(hipMemset(p->d_target, 0, n * sizeof(float)));
-            // r[s] = (s + 1) / B in float64, rounded once: no device division enters the bits
-            std::vector<float> r((size_t)bufsize);
-            for (int s = 0; s < bufsize; ++s) r[(size_t)s] = (float)(((double)s + 1.0) / (double)bufsize);
-            GAB_HIP_CHECK(hipMemcpy(p->d_ramp, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
-        } catch (...) {
-            gab::mix_free(p);
-            throw;
-        }
-        *out = p;
+        const size_t n = (size_t)tracks * buses;
+        p->gains.create(n, bufsize);
+        p->flag.alloc(1);
+        // The workspace of the final pass: as many buffers' partial sums as fit 32 MiB, at least one and at most
+        // kMixBatchChunk.  A longer batch is that many buffers per launch, one launch after the other.
+        const size_t per_buffer = (size_t)p->n_groups * buses * bufsize * sizeof(float);
+        size_t chunk = ((size_t)32 << 20) / per_buffer;
+        chunk = chunk < 1 ? 1 : (chunk > (size_t)gab::kMixBatchChunk ? (size_t)gab::kMixBatchChunk : chunk);
+        p->part_buffers = p->n_groups > 1 ? (int)chunk : gab::kMixBatchChunk;
+        if (p->n_groups > 1) p->part.alloc(chunk * per_buffer / sizeof(float));
+        GAB_HIP_CHECK(hipMemset(p->gains.current.get(), 0, n * sizeof(float)));
+        GAB_HIP_CHECK(hipMemset(p->gains.target.get(), 0, n * sizeof(float)));
+        *out = p.release();
         return GAB_OK;
     });
 }
@@ -440,7 +406,7 @@ int gab_mix_create(gab_mix_plan** out, int tracks, int bufsize, int buses) {
 int gab_mix_destroy(gab_mix_plan* plan) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_mix_destroy: null pointer");
-        gab::mix_free(plan);
+        delete plan;
         return GAB_OK;
     });
 }
@@ -456,7 +422,7 @@ int gab_mix_set_gains_tracks(gab_mix_plan* plan, const float* d_gains, int first
                              gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_gains) return gab::bad_arg("gab_mix_set_gains_tracks: null pointer");
-        if (first_track < 0 || n_tracks <= 0 || first_track > plan->tracks - n_tracks)
+        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
             return gab::bad_arg("gab_mix_set_gains_tracks: the track range is outside the plan");
         return gab::mix_set_range(plan, d_gains, first_track, n_tracks, ramp, gab::as_stream(stream),
                                   "gab_mix_set_gains_tracks");
@@ -466,9 +432,7 @@ int gab_mix_set_gains_tracks(gab_mix_plan* plan, const float* d_gains, int first
 int gab_mix_reset(gab_mix_plan* plan, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan) return gab::bad_arg("gab_mix_reset: null pointer");
-        GAB_HIP_CHECK(hipMemcpyAsync(plan->d_current, plan->d_target, (size_t)plan->tracks * plan->buses * sizeof(float),
-                                     hipMemcpyDeviceToDevice, gab::as_stream(stream)));
-        plan->pending = false;
+        plan->gains.snap(gab::as_stream(stream));
         return GAB_OK;
     });
 }
@@ -496,9 +460,9 @@ int gab_mix_process_batch(gab_mix_plan* plan, const float* d_in, float* d_out, i
 int gab_mix_gains(gab_mix_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_mix_gains: null pointer");
-        *d_current = plan->d_current;
-        *d_target = plan->d_target;
-        *n_floats = (size_t)plan->tracks * plan->buses;
+        *d_current = plan->gains.current.get();
+        *d_target = plan->gains.target.get();
+        *n_floats = plan->gains.current.size();
         return GAB_OK;
     });
 }

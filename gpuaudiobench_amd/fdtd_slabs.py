@@ -26,6 +26,7 @@ import ctypes as C
 import torch
 
 from ._capi import lib, check
+from .ops import _Handle
 from .sharding import shard_range
 
 SEND_DOWN_P, SEND_DOWN_VZ, SEND_UP_P, RECV_DOWN_P, RECV_UP_P, RECV_UP_VZ = range(6)
@@ -49,8 +50,10 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class FdtdSlab:
+class FdtdSlab(_Handle):
     """One slab of the room on the current device (gab_fdtd_create_slab and friends)."""
+
+    _destroy = "gab_fdtd_destroy"
 
     def __init__(self, params, z_begin, z_end):
         self.params, self.z_begin, self.z_end = params, z_begin, z_end
@@ -95,17 +98,6 @@ class FdtdSlab:
         out = torch.empty(P.nx * P.ny * nzl, dtype=torch.float32, device="cuda")
         check(lib.gab_fdtd_copy_pressure(self._h, C.c_void_p(out.data_ptr()), _stream()))
         return out.view(nzl, P.ny, P.nx)
-
-    def close(self):
-        if self._h:
-            lib.gab_fdtd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- the schedule; works on anything with halo()/inject()/step() (the tests drive it with a

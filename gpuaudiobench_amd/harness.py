@@ -6,6 +6,7 @@ import numpy as np
 
 from ._capi import (lib, check, BenchConfig, BenchResult, BenchValidation, Statistics,
                     CONV_STREAMING, CONV_STATELESS)
+from .ops import _Handle
 
 
 def benchmark_names():
@@ -57,9 +58,10 @@ def write_csv_results(latencies, name, filename):
                                     filename.encode()))
 
 
-class DawSim:
+class DawSim(_Handle):
     """Buffer-slot scheduler: wait() returns at t0 + k*buffer_seconds (+/- jitter), spinning or
     sleeping (metal-swift/MetalSwiftBench/Core/BenchmarkUtilities.swift:140-178)."""
+    _destroy = "gab_dawsim_destroy"
     MODES = {"spin": 0, "sleep": 1}
 
     def __init__(self, buffer_seconds=512.0 / 48000.0, mode="spin", jitter_us=0.0):
@@ -74,20 +76,11 @@ class DawSim:
         check(lib.gab_dawsim_stats(self._h, C.byref(w), C.byref(m)))
         return w.value, m.value
 
-    def close(self):
-        if self._h:
-            lib.gab_dawsim_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Benchmark:
+class Benchmark(_Handle):
     """GPUABenchmark by registry name: setup() / run() / validate()."""
+
+    _destroy = "gab_bench_destroy"
 
     def __init__(self, name, **cfg):
         c = BenchConfig()
@@ -153,14 +146,3 @@ class Benchmark:
         w, m = C.c_ulonglong(0), C.c_ulonglong(0)
         check(lib.gab_bench_dawsim_stats(self._h, C.byref(w), C.byref(m)))
         return w.value, m.value
-
-    def close(self):
-        if self._h:
-            lib.gab_bench_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -13,8 +13,8 @@ from ._capi import (lib, check, WaveguideState, FdtdParams, CONV_STATELESS, CONV
                     DWG_NAIVE, DWG_ACCEL)
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _stream(stream=None):
+    return C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
 
 
 def _dev(t, dtype=torch.float32):
@@ -46,6 +46,48 @@ def _view(ptr, rows, cols):
     m = _Mem()
     m.__cuda_array_interface__ = {"shape": (rows, cols), "typestr": "<f4", "data": (ptr, False), "version": 2}
     return torch.as_tensor(m, device="cuda")
+
+
+class _Handle:
+    """A library object behind a handle `_h`: close() destroys it once, garbage collection closes what was left open."""
+
+    _h = None
+    _destroy = None     # the name of its gab_*_destroy
+
+    def close(self):
+        if self._h:
+            getattr(lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _launcher(name):
+    """launch(args) for the tuple a prepare() built: the call of process() without building its arguments again."""
+    fn = getattr(lib, name)
+
+    def launch(args):
+        check(fn(*args))
+    return staticmethod(launch)
+
+
+class _Prepared:
+    """prepare() of a plan whose process call takes (plan, in, out, stream)."""
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
+        return (self._h, _dev(x), _dev(out), _stream(stream))
+
+
+def _n_buffers(plan, xs):
+    """How many whole buffers of the plan xs holds."""
+    n, rest = divmod(xs.numel(), plan.tracks * plan.bufsize)
+    assert rest == 0
+    return n
 
 
 def device_count():
@@ -99,9 +141,11 @@ def placement_summary(places):
                                         (" ..." if len(places) > 16 else ""))
 
 
-class KeepWarm:
+class KeepWarm(_Handle):
     """gab_keep_warm: a small resident launch that keeps the device from going idle between real-time slots
     (kick() once per slot; it ends by itself idle_seconds after the last kick)."""
+
+    _destroy = "gab_keep_warm_destroy"
 
     def __init__(self, workgroups=8, idle_seconds=0.25):
         h = C.c_void_p()
@@ -121,21 +165,12 @@ class KeepWarm:
         wave that has started (gab_keep_warm_placement; HW_ID / XCC_ID as the hardware reports them)."""
         return _placement(lib.gab_keep_warm_placement, self._h)
 
-    def close(self):
-        if self._h:
-            lib.gab_keep_warm_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LinkPlan:
+class LinkPlan(_Handle):
     """gab_link_plan: the staging buffer, words and upload stream of datatransfer with both link directions
     busy at once (gab_datatransfer_round_trip)."""
+
+    _destroy = "gab_link_plan_destroy"
 
     def __init__(self, max_in_size):
         h = C.c_void_p()
@@ -148,7 +183,7 @@ class LinkPlan:
             raise TypeError("round_trip takes host tensors; the output must be pinned")
         if h_in.dtype != torch.float32 or h_out.dtype != torch.float32 or not h_in.is_contiguous() or not h_out.is_contiguous():
             raise TypeError("round_trip takes contiguous float32 tensors")
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         check(lib.gab_datatransfer_round_trip(self._h, C.c_void_p(h_in.data_ptr()) if h_in.numel() else None,
                                               C.c_void_p(h_out.data_ptr()) if h_out.numel() else None,
                                               h_in.numel(), h_out.numel(), st))
@@ -157,17 +192,6 @@ class LinkPlan:
     def check(self):
         """The verdict of the check launch behind the last round trip (gab_datatransfer_round_trip_check)."""
         check(lib.gab_datatransfer_round_trip_check(self._h))
-
-    def close(self):
-        if self._h:
-            lib.gab_link_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def iir(x, coeffs, state, tracks, bufsize, sequential=False):
@@ -232,9 +256,10 @@ def fft_r2c_1024(x, tracks):
     return out.view(tracks, 513, 2)
 
 
-class ConvPlan:
+class ConvPlan(_Handle):
     """Conv1DAccelBenchmark's device side: spectra bank + history + process()."""
 
+    _destroy = "gab_conv_destroy"
     _SCHEMES = {"classic": 0, "split": 1, "fdl": 2}
 
     def __init__(self, tracks, bufsize, ir_len, scheme=None):
@@ -286,7 +311,7 @@ class ConvPlan:
             raise TypeError("round_trip takes host tensors; the output must be pinned")
         if h_in.dtype != torch.float32 or h_out.dtype != torch.float32 or not h_in.is_contiguous() or not h_out.is_contiguous():
             raise TypeError("round_trip takes contiguous float32 tensors")
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         check(lib.gab_conv_round_trip(self._h, C.c_void_p(h_in.data_ptr()), C.c_void_p(h_out.data_ptr()), st))
         return h_out
 
@@ -315,12 +340,10 @@ class ConvPlan:
         return out
 
     def prepare_round_trip(self, h_in, h_out, stream=None):
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         return (self._h, C.c_void_p(h_in.data_ptr()), C.c_void_p(h_out.data_ptr()), st)
 
-    @staticmethod
-    def launch_round_trip(args):
-        check(lib.gab_conv_round_trip(*args))
+    launch_round_trip = _launcher("gab_conv_round_trip")
 
     # ---- the doorbell-fed resident engine (gab_conv_engine_*) ----
     def engine_rings(self, ring_buffers):
@@ -334,7 +357,7 @@ class ConvPlan:
         """Launches the resident engine; returns (in_ring, out_ring) as device tensors [ring][T*B] / [ring][B*T]
         viewing the plan's rings."""
         a, b = C.c_void_p(), C.c_void_p()
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         check(lib.gab_conv_engine_start(self._h, ring_buffers, C.byref(a), C.byref(b), st))
         n = self.tracks * self.bufsize
         return _view(a.value, ring_buffers, n), _view(b.value, ring_buffers, n)
@@ -398,43 +421,30 @@ class ConvPlan:
     def prepare_batch(self, x, n_buffers, out, stream=None):
         """The ctypes arguments of process_batch(), built once for a loop over the same resident batch."""
         assert x.numel() == n_buffers * self.tracks * self.bufsize == out.numel()
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         return (self._h, _dev(x), _dev(out), n_buffers, st)
 
-    @staticmethod
-    def launch_batch(args):
-        check(lib.gab_conv_process_batch(*args))
+    launch_batch = _launcher("gab_conv_process_batch")
 
     def prepare(self, x, out, mode=CONV_STREAMING, stream=None):
         """The ctypes arguments of process(), built once for a loop that cycles through a fixed set
         of buffers; `launch(args)` then costs ~4 us of host time instead of ~7.5."""
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         return (self._h, _dev(x), _dev(out), mode, st)
 
-    @staticmethod
-    def launch(args):
-        check(lib.gab_conv_process(*args))
+    launch = _launcher("gab_conv_process")
 
     def state_bytes(self):
         a, b = C.c_size_t(0), C.c_size_t(0)
         check(lib.gab_conv_state_bytes(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def close(self):
-        if self._h:
-            lib.gab_conv_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EqPlan:
+class EqPlan(_Handle, _Prepared):
     """gab_eq_plan: `sections` biquads in series on each of `tracks` channels, every (track, section) with its own
     coefficients, state carried from buffer to buffer.  A new plan is the identity filter."""
+
+    _destroy = "gab_eq_destroy"
 
     def __init__(self, tracks, bufsize, sections):
         self.tracks, self.bufsize, self.sections = tracks, bufsize, sections
@@ -482,8 +492,7 @@ class EqPlan:
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch."""
-        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
-        assert rest == 0
+        n = _n_buffers(self, xs)
         out = torch.empty_like(xs) if out is None else out
         check(lib.gab_eq_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
         return out
@@ -501,31 +510,14 @@ class EqPlan:
         check(lib.gab_eq_form(self._h, C.byref(m), C.byref(h)))
         return m.value, h.value
 
-    def prepare(self, x, out, stream=None):
-        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        return (self._h, _dev(x), _dev(out), st)
-
-    @staticmethod
-    def launch(args):
-        check(lib.gab_eq_process(*args))
-
-    def close(self):
-        if self._h:
-            lib.gab_eq_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    launch = _launcher("gab_eq_process")
 
 
-class MixPlan:
+class MixPlan(_Handle):
     """gab_mix_plan: `tracks` channels summed into `buses` buses with a linear gain per (track, bus), in a fixed
     summation order (`form`).  A new plan is silence; new gains are ramped in over the next buffer unless ramp=False."""
 
+    _destroy = "gab_mix_destroy"
     _LAYOUTS = {"track": 0, "sample": 1}
 
     def __init__(self, tracks, bufsize, buses):
@@ -587,8 +579,7 @@ class MixPlan:
 
     def process_batch(self, xs, out=None, layout="track"):
         """Consecutive buffers [n][tracks*bufsize] -> [n][buses*bufsize] in one launch."""
-        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
-        assert rest == 0
+        n = _n_buffers(self, xs)
         if out is None:
             out = torch.empty(n * self.buses * self.bufsize, dtype=torch.float32, device=xs.device)
         assert out.numel() == n * self.buses * self.bufsize
@@ -610,30 +601,18 @@ class MixPlan:
 
     def prepare(self, x, out, layout="track", stream=None):
         """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+        st = _stream(stream)
         return (self._h, _dev(x), _dev(out), self._LAYOUTS[layout], st)
 
-    @staticmethod
-    def launch(args):
-        check(lib.gab_mix_process(*args))
-
-    def close(self):
-        if self._h:
-            lib.gab_mix_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    launch = _launcher("gab_mix_process")
 
 
-class DelayPlan:
+class DelayPlan(_Handle, _Prepared):
     """gab_delay_plan: a delay line per track, read at a fractional position (interp "linear" or "lagrange3"), with a
     feedback path.  Parameters per track {delay (samples), feedback, wet, dry}; a new plan is pass-through; new
     parameters are ramped in over the next buffer unless ramp=False."""
 
+    _destroy = "gab_delay_destroy"
     _INTERP = {"linear": 0, "lagrange3": 1}
 
     def __init__(self, tracks, bufsize, max_delay, interp="linear"):
@@ -669,8 +648,7 @@ class DelayPlan:
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch."""
-        n, rest = divmod(xs.numel(), self.tracks * self.bufsize)
-        assert rest == 0
+        n = _n_buffers(self, xs)
         out = torch.empty_like(xs) if out is None else out
         assert out.numel() == xs.numel()
         check(lib.gab_delay_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
@@ -690,25 +668,7 @@ class DelayPlan:
         pos = _view(p.value, self.tracks, 1).clone().view(torch.int32).to(torch.int64).view(self.tracks)
         return ring, pos
 
-    def prepare(self, x, out, stream=None):
-        """The ctypes arguments of process(), built once for a loop over the same buffers; `launch(args)`."""
-        st = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-        return (self._h, _dev(x), _dev(out), st)
-
-    @staticmethod
-    def launch(args):
-        check(lib.gab_delay_process(*args))
-
-    def close(self):
-        if self._h:
-            lib.gab_delay_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    launch = _launcher("gab_delay_process")
 
 
 def fdtd_default_params(nx, ny=None, nz=None):
@@ -718,7 +678,9 @@ def fdtd_default_params(nx, ny=None, nz=None):
     return P
 
 
-class FdtdPlan:
+class FdtdPlan(_Handle):
+    _destroy = "gab_fdtd_destroy"
+
     def __init__(self, params):
         self.params = params
         self._h = C.c_void_p()
@@ -768,14 +730,3 @@ class FdtdPlan:
         out = torch.empty(P.nx * P.ny * P.nz, dtype=torch.float32, device="cuda")
         check(lib.gab_fdtd_copy_pressure(self._h, _dev(out), _stream()))
         return out.view(P.nz, P.ny, P.nx)
-
-    def close(self):
-        if self._h:
-            lib.gab_fdtd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

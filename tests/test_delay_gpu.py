@@ -11,7 +11,8 @@ import functools
 import numpy as np
 import pytest
 
-from test_delay_host import (INTERPS, Line, bits, capacity, delay_mix, delay_reference_f32, min_delay, mix_ramp, noise,
+from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
+from test_delay_host import (INTERPS, Line, capacity, delay_mix, delay_reference_f32, min_delay, mix_ramp, noise,
                              table)
 
 pytestmark = pytest.mark.gpu
@@ -19,23 +20,6 @@ pytestmark = pytest.mark.gpu
 # (tracks, bufsize, max_delay, buffers).  2 * capacity / B + 2 buffers where the wrap is the point (capacity 256 and 2048),
 # three or four where the capacity is large (a steady buffer, the ramp buffer, the steady buffer behind it).
 SHAPES = [(5, 100, 37, 8), (64, 64, 1000, 66), (130, 512, 4096, 4), (4100, 512, 600, 3), (3, 2048, 70000, 3), (1, 1, 2, 20)]
-
-
-@pytest.fixture(scope="module")
-def gab():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import gpuaudiobench_amd as g
-    return g
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.array(a, copy=True, order="C")).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 class Twin:
@@ -387,6 +371,28 @@ def test_a_refused_table_changes_nothing(gab, interp):
     assert same_params(plan, p0, p1)
     for k in range(2):                                                          # the pending ramp is still pending
         assert np.array_equal(bits(run(plan, xs[k])), bits(ys[k])), k
+    plan.close()
+    # A refused RAMPED set on a plan with NO ramp pending: none is pending afterwards, current == target == the old
+    # rows, and the next buffers are steady buffers of the old rows.
+    T, B, M = 5, 64, 16
+    q0 = delay_mix(T, B, M, interp, 4)
+    plan, twin = gab.DelayPlan(T, B, M, interp), Twin(T, B, M, interp)
+    plan.set_params(dev(q0), ramp=False)
+    twin.set_params(q0, ramp=False)
+    x = noise(T, B, 50)
+    assert np.array_equal(bits(run(plan, x)), bits(twin.process(x)))
+    bad = delay_mix(T, B, M, interp, 5)
+    bad[4, 1] = 1.0
+    with pytest.raises(gab.GabError) as e:
+        plan.set_params(dev(bad), ramp=True)
+    assert "track 4 field 1" in str(e.value)
+    with pytest.raises(gab.GabError) as e:
+        plan.set_params(dev(bad[3:]), ramp=True, first_track=3)
+    assert "track 4 field 1" in str(e.value)
+    for k in range(2):
+        assert same_params(plan, q0, q0), k
+        x = noise(T, B, 51 + k)
+        assert np.array_equal(bits(run(plan, x)), bits(twin.process(x))), k
     plan.close()
 
 

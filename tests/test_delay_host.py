@@ -29,7 +29,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_mix_host import EPS, bits, fma32, mix_ramp
+from plan_helpers import bits
+from test_mix_host import EPS, fma32, mix_ramp
 
 INTERPS = ("linear", "lagrange3")
 C6 = np.float32(1.0 / 6.0)

@@ -13,30 +13,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
 from test_eq_host import (N_BUFFERS, SCAN_CASES, bank_round_off, case_seed, eq_bank, eq_reference_f32, noise)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gab():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import gpuaudiobench_amd as g
-    return g
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def make_plan(gab, T, B, S, coeffs=None):

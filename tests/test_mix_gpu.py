@@ -9,7 +9,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from test_mix_host import (EPS, bits, gains, mix_ramp, mix_reference_f32, noise, one_hot_case, small_integer_case,
+from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
+from test_mix_host import (EPS, gains, mix_ramp, mix_reference_f32, noise, one_hot_case, small_integer_case,
                            tree_bound)
 
 pytestmark = pytest.mark.gpu
@@ -17,23 +18,6 @@ pytestmark = pytest.mark.gpu
 LAYOUTS = ("track", "sample")
 SHAPES = [(8192, 512, 16), (128, 512, 2), (5, 100, 3), (1000, 128, 64), (64, 64, 1), (130, 2048, 7), (200, 513, 4),
           (65536, 512, 2)]
-
-
-@pytest.fixture(scope="module")
-def gab():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    import gpuaudiobench_amd as g
-    return g
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def arrange(x, layout):
@@ -410,6 +394,30 @@ def test_a_refused_matrix_changes_nothing(gab):
         assert np.array_equal(bits(run(plan, x)), bits(run(twin, x))), k
         for ga, gb in zip(plan.gains(), twin.gains()):
             assert np.array_equal(bits(host(ga)), bits(host(gb)))
+    plan.close()
+    twin.close()
+    # A refused RAMPED set on a plan with NO ramp pending: none is pending afterwards, current == target == the old
+    # gains, and the next buffer is the steady buffer of the old gains.  Two groups, a ragged leaf.
+    T, B, M = 300, 96, 3
+    plan, twin = gab.MixPlan(T, B, M), gab.MixPlan(T, B, M)
+    g0 = gains(T, M, 47)
+    for p in (plan, twin):
+        p.set_gains(dev(g0), ramp=False)
+    bad = gains(T, M, 48)
+    bad[299, 2] = np.inf
+    with pytest.raises(gab.GabError) as e:
+        plan.set_gains(dev(bad), ramp=True)
+    assert "track 299 bus 2" in str(e.value)
+    with pytest.raises(gab.GabError) as e:
+        plan.set_gains(dev(bad[250:]), ramp=True, first_track=250)
+    assert "track 299 bus 2" in str(e.value)
+    for k in range(2):
+        for ga in plan.gains():
+            assert np.array_equal(bits(host(ga)), bits(g0)), k
+        x = noise(T, B, 49 + k)
+        y = run(plan, x)
+        assert np.array_equal(bits(y), bits(run(twin, x))), k
+        assert np.array_equal(bits(y), bits(mix_reference_f32(x, g0, g0, None, *plan.form))), k
     plan.close()
     twin.close()
 

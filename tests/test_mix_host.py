@@ -24,6 +24,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from plan_helpers import bits
+
 EPS = 2.0 ** -24
 
 
@@ -130,10 +132,6 @@ def noise(T, B, seed):
 
 def gains(T, M, seed):
     return np.random.RandomState(seed).uniform(-1.0, 1.0, (T, M)).astype(np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # ---- fma32 ----------------------------------------------------------------------------------------------------
