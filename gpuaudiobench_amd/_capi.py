@@ -178,6 +178,14 @@ PROTOTYPES = {
     "gab_delay_process_batch": (_I, [_P, _P, _P, _I, _P]),
     "gab_delay_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_delay_line": (_I, [_P, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_P)]),
+    "gab_meter_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_meter_destroy": (_I, [_P]),
+    "gab_meter_set_weighting": (_I, [_P, _P, _P]),
+    "gab_meter_set_decay": (_I, [_P, _F, _P]),
+    "gab_meter_reset": (_I, [_P, _P]),
+    "gab_meter_process": (_I, [_P, _P, _P, _P]),
+    "gab_meter_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_meter_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

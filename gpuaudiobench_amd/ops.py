@@ -671,6 +671,64 @@ class DelayPlan(_Handle, _Prepared):
     launch = _launcher("gab_delay_process")
 
 
+class MeterPlan(_Handle, _Prepared):
+    """gab_meter_plan: one row of eight levels (FIELDS, all linear) per track and buffer, with carried state: the
+    true-peak history, the weighting filter's state, the peak hold and a ring of the last `window` weighted mean
+    squares.  The input is only read.  A new plan weighs with BS.1770's K curve at 48 kHz and holds its peak until
+    reset."""
+
+    _destroy = "gab_meter_destroy"
+    FIELDS = ("peak", "true_peak", "ms", "kms", "peak_hold", "true_peak_max", "kms_window", "nonfinite")
+
+    def __init__(self, tracks, bufsize, window=1):
+        self.tracks, self.bufsize, self.window = tracks, bufsize, window
+        self._h = C.c_void_p()
+        check(lib.gab_meter_create(C.byref(self._h), tracks, bufsize, window))
+
+    def set_weighting(self, sections):
+        """sections: device tensor [2][5] = {b0, b1, b2, a1, a2} (a0 = 1), the same for every track; in force from
+        the next buffer, the filter state is kept."""
+        assert sections.numel() == 10
+        check(lib.gab_meter_set_weighting(self._h, _dev(sections), _stream()))
+
+    def set_decay(self, decay):
+        """peak_hold's factor per buffer, within [0, 1]; 1 holds until reset."""
+        check(lib.gab_meter_set_decay(self._h, float(decay), _stream()))
+
+    def reset(self):
+        """Every carried value zero; the weighting and the decay stay."""
+        check(lib.gab_meter_reset(self._h, _stream()))
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize]; returns the rows [tracks][8]."""
+        assert x.numel() == self.tracks * self.bufsize
+        if out is None:
+            out = torch.empty(self.tracks, len(self.FIELDS), dtype=torch.float32, device=x.device)
+        assert out.numel() == self.tracks * len(self.FIELDS)
+        check(lib.gab_meter_process(self._h, _dev(x), _dev(out), _stream()))
+        return out
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch; returns the rows [n][tracks][8]."""
+        n = _n_buffers(self, xs)
+        if out is None:
+            out = torch.empty(n, self.tracks, len(self.FIELDS), dtype=torch.float32, device=xs.device)
+        assert out.numel() == n * self.tracks * len(self.FIELDS)
+        check(lib.gab_meter_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
+        return out
+
+    def state(self):
+        """Copies of (hist [tracks][16] = the last 11 samples, peak_hold, true_peak_max, 3 zeros; filter
+        [tracks][2][2] = (s1, s2) per section; ring [tracks][window]; pos [tracks] int64)."""
+        h, f, r, p = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib.gab_meter_state(self._h, C.byref(h), C.byref(f), C.byref(r), C.byref(p)))
+        pos = _view(p.value, self.tracks, 1).clone().view(torch.int32).to(torch.int64).view(self.tracks)
+        return (_view(h.value, self.tracks, 16).clone(), _view(f.value, self.tracks, 4).clone().view(self.tracks, 2, 2),
+                _view(r.value, self.tracks, self.window).clone(), pos)
+
+    launch = _launcher("gab_meter_process")
+
+
 def fdtd_default_params(nx, ny=None, nz=None):
     P = FdtdParams()
     check(lib.gab_fdtd_default_params(nx, nx if ny is None else ny, nx if nz is None else nz,

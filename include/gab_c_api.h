@@ -645,6 +645,66 @@ int gab_delay_process_batch(gab_delay_plan* plan, const float* d_in, float* d_ou
 int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_delay_line(gab_delay_plan* plan, float** d_ring, size_t* capacity, unsigned** d_pos);
 
+/* ---- meter: per track and buffer one row of eight levels, with carried state (additive; the reference's gainstats is
+ * one stateless mean and max that also writes a scaled copy of the block) -----------------------------------------
+ * The input ([tracks][bufsize] float32, track-major, any alignment) is never written.  process writes d_rows
+ * [tracks][8], process_batch [n][tracks][8] for n consecutive buffers in one call with the bits of n process calls.
+ * Every field is linear; decibels are the caller's business.  Let w be the track's stream, zero before the first
+ * sample and after a reset, x the buffer, B = bufsize, inv_B = (float)(1.0 / B), inv_W = (float)(1.0 / window).
+ *   0 peak           max |x[s]| by fmaxf, from 0: a NaN is ignored.  Exact.
+ *   1 true_peak      four-times oversampled peak, one polyphase pass of 12 taps per phase.  Taps of phase k = 1, 2, 3:
+ *                    f = k / 4, d = 5 + f - j, h_k[j] = sinc(d) (0.5 + 0.5 cos(pi d / 6.5)), j = 0..11, in float64;
+ *                    each phase divided by its sum (added in ascending j), rounded once to float32 on the host: 36
+ *                    constants, no device division or transcendental function.  For absolute sample n
+ *                      y_k[n] = fmaf(h_k[11], w[n-11], ... fmaf(h_k[1], w[n-1], h_k[0] * w[n]))     (ascending j)
+ *                    and the field is the fmaxf, from 0 and over the buffer's n, of |w[n-5]|, |y_1[n]|, |y_2[n]|,
+ *                    |y_3[n]|.  The reading lags by five samples.  Accuracy: a sine at 0.25 fs reads within 0.2 dB,
+ *                    one at 0.4 fs up to 0.44 dB low, which is the limit of 12 taps.
+ *   2 ms             sum(x^2) * inv_B.  The sum is a tree fixed by bufsize alone: the buffer is cut into segments of 64
+ *                    samples, a short last segment is filled with zeros; in a segment every square is rounded once
+ *                    (p_l = x_l * x_l, l = 0..63), then p_l = p_l + p_(l^32), then ^16, ^8, ^4, ^2, ^1 (all l at once)
+ *                    and the segment's sum is p_0; the segments' sums are added in ascending order from 0.
+ *   3 kms            the same tree over v^2, v being x through the two weighting sections in series.  A section is
+ *                    direct form II transposed on its carried pair (s1, s2):
+ *                      y = fmaf(b0, x, s1);  s1 = fmaf(b1, x, fmaf(-a1, y, s2));  s2 = fmaf(b2, x, (-a2) * y)
+ *                    (the last product rounded once).  The plan runs exactly this ordered recurrence at every bufsize
+ *                    (gab_eq's wave scan of a biquad re-associates too much for these two sections: DESIGN.md 4d).
+ *                    The weighting is the same for every track; the default is the K weighting of ITU-R BS.1770 at
+ *                    48 kHz (+0.691 dB at 997 Hz).
+ *   4 peak_hold      hold = fmaxf(peak, hold * decay), the product rounded once; carried.  decay 1 (the default) holds
+ *                    until reset.
+ *   5 true_peak_max  the running fmaxf of field 1 since the last reset.
+ *   6 kms_window     the mean of kms over the last `window` buffers: the values live in a ring per track, zero after
+ *                    a reset; every buffer the ring is added from the oldest to the newest value in that order, from
+ *                    0, and multiplied by inv_W.  No running sum that drifts.
+ *   7 nonfinite      1.0 if any sample of the buffer was an infinity or a NaN (from the bits), else 0.0.  Such a sample
+ *                    poisons the carried filter state (fields 3 and 6) until reset; the plan does not repair it.
+ *   set_weighting    d_sections: device, [2][5] = {b0, b1, b2, a1, a2} (a0 = 1).  Checked on the device first: every
+ *                    value finite, |a2| < 1, |a1| < 1 + a2.  A violation: GAB_ERR_INVALID_ARG naming the first value
+ *                    in index order (a2 for the first rule, a1 for the second); the plan keeps its weighting.  In
+ *                    force from the next buffer; the filter state is kept.  Synchronous with respect to `stream`.
+ *   set_decay        0 <= decay <= 1, per buffer, in force from the next process call.
+ *   reset            every carried value zero; the weighting and the decay stay.
+ *   state            the plan's own memory, for inspection: d_hist [tracks][16] = the last 11 samples oldest first,
+ *                    peak_hold, true_peak_max, three zeros; d_filter [tracks][2][2] = (s1, s2) per section; d_ring
+ *                    [tracks][window]; d_pos [tracks], the ring index of the next value.
+ * Every field has the bits of this text on every call form, and a shard of tracks as its own plan gives those tracks'
+ * bits.  process and process_batch are one launch each, allocate nothing and wait for nothing; the launch reads the
+ * block once (16-byte loads where d_in is 16-byte aligned and bufsize a multiple of 4) and writes the rows and the
+ * carried state only.  It works in chunks of 64 samples on 64 tracks: a bufsize far below 64 pays for a whole chunk,
+ * and fewer than 64 tracks x 256 use a part of the device.  tracks >= 1, bufsize >= 1, 1 <= window <= 64;
+ * arguments are checked before any device call.  One thread at a time per plan.                                   */
+typedef struct gab_meter_plan gab_meter_plan;
+#define GAB_METER_FIELDS 8
+int gab_meter_create(gab_meter_plan** plan, int tracks, int bufsize, int window);
+int gab_meter_destroy(gab_meter_plan* plan);
+int gab_meter_set_weighting(gab_meter_plan* plan, const float* d_sections, gab_stream_t stream);
+int gab_meter_set_decay(gab_meter_plan* plan, float decay, gab_stream_t stream);
+int gab_meter_reset(gab_meter_plan* plan, gab_stream_t stream);
+int gab_meter_process(gab_meter_plan* plan, const float* d_in, float* d_rows, gab_stream_t stream);
+int gab_meter_process_batch(gab_meter_plan* plan, const float* d_in, float* d_rows, int n_buffers, gab_stream_t stream);
+int gab_meter_state(gab_meter_plan* plan, float** d_hist, float** d_filter, float** d_ring, unsigned** d_pos);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
