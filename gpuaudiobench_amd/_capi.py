@@ -186,6 +186,14 @@ PROTOTYPES = {
     "gab_meter_process": (_I, [_P, _P, _P, _P]),
     "gab_meter_process_batch": (_I, [_P, _P, _P, _I, _P]),
     "gab_meter_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "gab_resample_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I]),
+    "gab_resample_destroy": (_I, [_P]),
+    "gab_resample_shape": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "gab_resample_set_taps": (_I, [_P, _P, _P]),
+    "gab_resample_reset": (_I, [_P, _P]),
+    "gab_resample_process": (_I, [_P, _P, _P, C.POINTER(_I), _P]),
+    "gab_resample_process_batch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
+    "gab_resample_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_longlong)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

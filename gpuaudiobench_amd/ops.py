@@ -729,6 +729,89 @@ class MeterPlan(_Handle, _Prepared):
     launch = _launcher("gab_meter_process")
 
 
+class ResamplePlan(_Handle):
+    """gab_resample_plan: every track's stream from one sample rate to another by up / down (reduced by their gcd), a
+    polyphase FIR of `ntaps` taps per phase with carried history and an exact carried position.  A buffer of `bufsize`
+    input samples gives floor or ceil of bufsize * up / down output samples; `out_capacity` is the ceil, and the rest
+    of a row is zeros.  The counts are host integers; the pattern repeats every `period` buffers.  (No prepare():
+    the position is a launch argument, so a captured process replays one position.)"""
+
+    _destroy = "gab_resample_destroy"
+
+    def __init__(self, tracks, bufsize, up, down, taps=None):
+        if taps is None:
+            taps = self.default_taps(up, down)
+        self.tracks, self.bufsize = tracks, bufsize
+        self._h = C.c_void_p()
+        check(lib.gab_resample_create(C.byref(self._h), tracks, bufsize, up, down, taps))
+        v = [C.c_int(0) for _ in range(5)]
+        check(lib.gab_resample_shape(self._h, *[C.byref(c) for c in v]))
+        self.up, self.down, self.ntaps, self.out_capacity, self.period = (c.value for c in v)
+        self.latency = self.ntaps // 2          # input samples
+
+    @staticmethod
+    def default_taps(up, down):
+        """The smallest multiple of 8 that is at least 32 * max(1, down / up)."""
+        import math
+        g = math.gcd(up, down)
+        L, M = up // g, down // g
+        return 8 * -(-(32 * max(L, M)) // (8 * L))
+
+    @staticmethod
+    def counts(bufsize, up, down, first_buffer, n):
+        """The output counts of buffers first_buffer .. first_buffer + n - 1 since a reset: host integers, no GPU."""
+        import math
+        g = math.gcd(up, down)
+        L, M = up // g, down // g
+        lo = [-(-(k * bufsize * L) // M) for k in range(first_buffer, first_buffer + n + 1)]
+        return [b - a for a, b in zip(lo, lo[1:])]
+
+    def reset(self):
+        """Zero history, position 0; the taps stay."""
+        check(lib.gab_resample_reset(self._h, _stream()))
+
+    def set_taps(self, t):
+        """t: device tensor [up][ntaps]; in force from the next buffer, history and position are kept."""
+        assert t.numel() == self.up * self.ntaps
+        check(lib.gab_resample_set_taps(self._h, _dev(t), _stream()))
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize]; returns (out [tracks][out_capacity], n_out): the first n_out
+        elements of every row are samples, the rest zeros."""
+        assert x.numel() == self.tracks * self.bufsize
+        if out is None:
+            out = torch.empty(self.tracks, self.out_capacity, dtype=torch.float32, device=x.device)
+        assert out.numel() == self.tracks * self.out_capacity
+        n = C.c_int(0)
+        check(lib.gab_resample_process(self._h, _dev(x), _dev(out), C.byref(n), _stream()))
+        return out, n.value
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch; returns (out [n][tracks][out_capacity], counts)."""
+        n = _n_buffers(self, xs)
+        if out is None:
+            out = torch.empty(n, self.tracks, self.out_capacity, dtype=torch.float32, device=xs.device)
+        assert out.numel() == n * self.tracks * self.out_capacity
+        counts = (C.c_int * max(n, 1))()
+        check(lib.gab_resample_process_batch(self._h, _dev(xs), _dev(out), n, counts, _stream()))
+        return out, list(counts[:n])
+
+    def _state(self):
+        h, t, k = C.c_void_p(), C.c_void_p(), C.c_longlong(0)
+        check(lib.gab_resample_state(self._h, C.byref(h), C.byref(t), C.byref(k)))
+        return h.value, t.value, k.value
+
+    def taps(self):
+        """A copy of the table in force, [up][ntaps]."""
+        return _view(self._state()[1], self.up, self.ntaps).clone()
+
+    def state(self):
+        """(a copy of hist [tracks][ntaps-1] = the last ntaps-1 input samples, oldest first; buffers since the reset
+        mod period)."""
+        h, _, k = self._state()
+        return _view(h, self.tracks, self.ntaps - 1).clone(), k
+
+
 def fdtd_default_params(nx, ny=None, nz=None):
     P = FdtdParams()
     check(lib.gab_fdtd_default_params(nx, nx if ny is None else ny, nx if nz is None else nz,

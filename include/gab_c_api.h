@@ -705,6 +705,57 @@ int gab_meter_process(gab_meter_plan* plan, const float* d_in, float* d_rows, ga
 int gab_meter_process_batch(gab_meter_plan* plan, const float* d_in, float* d_rows, int n_buffers, gab_stream_t stream);
 int gab_meter_state(gab_meter_plan* plan, float** d_hist, float** d_filter, float** d_ring, unsigned** d_pos);
 
+/* ---- resample: every track's stream from one sample rate to another by a rational factor, with carried state
+ * (additive; the reference changes no stream's rate) --------------------------------------------------------------
+ * create divides up and down by their gcd; call the reduced pair L and M (shape reports them), K = taps, B = bufsize.
+ * A polyphase FIR: L rows of K taps, made on the host in float64; the device does no division and calls no
+ * transcendental function, and no summation order is left open.  Let w be a track's input stream, zero before the first
+ * sample after a reset.
+ *   position       Output sample m, counted from the reset, lies at input time m M / L:
+ *                    i = floor(m M / L),  p = (m M) mod L                       (exact integers)
+ *                  Buffer k since the reset carries inputs [k B, (k+1) B) and produces exactly the outputs m in
+ *                  [lo(k), lo(k+1)), lo(k) = ceil(k B L / M): all outputs whose newest tap w[i] lies in that buffer.
+ *                  n_out(k) = lo(k+1) - lo(k) is floor(B L / M) or ceil(B L / M) and may be 0;
+ *                  out_capacity = ceil(B L / M).  The pattern repeats with period = M / gcd(B L, M) buffers; the plan
+ *                  carries k mod period on the host in 64-bit arithmetic, so nothing overflows however long the stream
+ *                  runs.  n_out and counts are host integers computed without touching the device.
+ *   value          y[m] = fmaf(h_p[K-1], w[i-K+1], ... fmaf(h_p[1], w[i-1], h_p[0] * w[i]))
+ *                  The product first, then ascending j, one rounding per step (the meter's true-peak chain).  Nothing
+ *                  is re-associated; a NaN or an infinity travels as fmaf carries it.
+ *   taps           For phase p and tap j:  d = j - K/2 + p/L,  c = 0.94 min(1, L/M),  u = d / (K/2),
+ *                    h_p[j] = sinc(c d) (0.35875 + 0.48829 cos(pi u) + 0.14128 cos(2 pi u) + 0.01168 cos(3 pi u))
+ *                  in float64 with libm's sin and cos, sinc(x) = sin(pi x) / (pi x), sinc(0) = 1; each phase row
+ *                  divided by its sum (added in ascending j), rounded once to float32.  The latency is K/2 input
+ *                  samples.  A row's sum is 1 but the sum of its magnitudes reaches about 2.1: an output can exceed the
+ *                  input's peak.
+ *   layout         d_in [tracks][B] float32, track-major, any 4-byte alignment, never written.  d_out
+ *                  [tracks][out_capacity]; elements [n_out, out_capacity) of every row are written as 0.0f, so a whole
+ *                  row is defined.  process_batch takes [n][tracks][B], writes [n][tracks][out_capacity] and counts[n]:
+ *                  one launch with the bits of n process calls.  d_out may not overlap d_in.
+ *   state          d_hist [tracks][K-1]: the last K-1 input samples, oldest first; zero after reset, which also puts k
+ *                  back to 0.  Right when B < K-1 too: the history then spans several buffers and is shifted, not
+ *                  replaced.  d_taps [L][K]: the table in force.  The third value is k mod period.
+ *   set_taps       d_taps: device, [L][K].  Checked on the device first: the first value that is not finite is named as
+ *                  (phase, tap) with GAB_ERR_INVALID_ARG and the plan keeps its table.  Accepted taps are in force from
+ *                  the next buffer; history and position are kept.  Synchronous with respect to `stream`.
+ * A shard of tracks as its own plan gives those tracks' bits.  process and process_batch are one launch each, allocate
+ * nothing and wait for nothing.  The position is a launch argument: a captured process replays one position and is only
+ * meaningful when period == 1.  Arguments are checked before any device call: tracks >= 1, 1 <= bufsize <= 2^20, up
+ * and down in 1..1024, taps even and in 4..256 (GAB_ERR_INVALID_ARG); L K <= 16384 floats, the table that fits 64 KiB
+ * of LDS (else GAB_ERR_UNSUPPORTED).  The launch works on 64 tracks x 64 input samples at a time: fewer than 64 tracks x
+ * 256 use a part of the device.  One thread at a time per plan.                                                     */
+typedef struct gab_resample_plan gab_resample_plan;
+int gab_resample_create(gab_resample_plan** plan, int tracks, int bufsize, int up, int down, int taps);
+int gab_resample_destroy(gab_resample_plan* plan);
+int gab_resample_shape(gab_resample_plan* plan, int* up, int* down, int* taps, int* out_capacity, int* period);
+int gab_resample_set_taps(gab_resample_plan* plan, const float* d_taps, gab_stream_t stream);
+int gab_resample_reset(gab_resample_plan* plan, gab_stream_t stream);
+int gab_resample_process(gab_resample_plan* plan, const float* d_in, float* d_out, int* n_out, gab_stream_t stream);
+int gab_resample_process_batch(gab_resample_plan* plan, const float* d_in, float* d_out, int n_buffers, int* counts,
+                               gab_stream_t stream);
+int gab_resample_state(gab_resample_plan* plan, float** d_hist, float** d_taps,
+                       long long* buffers_since_reset_mod_period);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
