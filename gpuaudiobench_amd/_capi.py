@@ -194,6 +194,16 @@ PROTOTYPES = {
     "gab_resample_process": (_I, [_P, _P, _P, C.POINTER(_I), _P]),
     "gab_resample_process_batch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
     "gab_resample_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_longlong)]),
+    "gab_dyn_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_dyn_destroy": (_I, [_P]),
+    "gab_dyn_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_dyn_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_dyn_reset": (_I, [_P, _P]),
+    "gab_dyn_process": (_I, [_P, _P, _P, _P, _P, _P]),
+    "gab_dyn_process_batch": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "gab_dyn_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_dyn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_dyn_poly": (_I, [C.POINTER(C.POINTER(_F)), C.POINTER(_I), C.POINTER(C.POINTER(_F)), C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

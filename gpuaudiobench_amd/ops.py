@@ -671,6 +671,104 @@ class DelayPlan(_Handle, _Prepared):
     launch = _launcher("gab_delay_process")
 
 
+def dynamics_params(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db=0.0, range_db=None, fs=48000.0):
+    """A row (all arguments scalars) or a table [n][8] float32 of DynamicsPlan parameters {thr, slope, knee, kq, att,
+    rel, makeup, range} from the knobs of a compressor; float64, rounded once.  Levels go from dB to log2 units
+    (6.0206 dB each); knee_db is the knee's whole width; ratio = inf is a limiter; a time of 0 ms is a coefficient
+    of 0, else exp(-1 / (ms fs / 1000)); range_db=None leaves the reduction unbounded (-256 units)."""
+    import numpy as np
+    unit = 20.0 * np.log10(2.0)
+    args = [np.asarray(a, np.float64) for a in (threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db,
+                                                -256.0 * unit if range_db is None else range_db)]
+    scalar = all(a.ndim == 0 for a in args)
+    thr_db, ratio, knee_db, att_ms, rel_ms, makeup_db, range_db = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    if (ratio < 1.0).any() or (knee_db < 0.0).any() or (att_ms < 0.0).any() or (rel_ms < 0.0).any() or (range_db > 0.0).any():
+        raise ValueError("needs ratio >= 1, knee_db >= 0, attack_ms >= 0, release_ms >= 0, range_db <= 0")
+    knee = 0.5 * knee_db / unit
+    with np.errstate(divide="ignore"):
+        kq = np.where(knee > 0.0, 1.0 / (4.0 * np.where(knee > 0.0, knee, 1.0)), 0.0)
+        att = np.where(att_ms > 0.0, np.exp(-1.0 / np.where(att_ms > 0.0, att_ms * fs / 1000.0, 1.0)), 0.0)
+        rel = np.where(rel_ms > 0.0, np.exp(-1.0 / np.where(rel_ms > 0.0, rel_ms * fs / 1000.0, 1.0)), 0.0)
+        slope = 1.0 / ratio - 1.0                                    # inf: -1
+    cap = 1.0 - 2.0 ** -20                                           # the plan's cap on a coefficient: 22 s at 48 kHz
+    table = np.stack([thr_db / unit, slope, knee, kq, np.minimum(att, cap), np.minimum(rel, cap),
+                      10.0 ** (makeup_db / 20.0), np.maximum(range_db / unit, -256.0)], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class DynamicsPlan(_Handle):
+    """gab_dyn_plan: a compressor / limiter per track with a carried smoothed gain.  Parameters per track {thr, slope,
+    knee, kq, att, rel, makeup, range} (dynamics_params makes them from dB, ratio and ms); tracks [g link, (g + 1) link)
+    share one detector.  A new plan is pass-through; new parameters are ramped in over the next buffer unless
+    ramp=False."""
+
+    _destroy = "gab_dyn_destroy"
+    FIELDS = ("thr", "slope", "knee", "kq", "att", "rel", "makeup", "range")
+
+    def __init__(self, tracks, bufsize, link=1):
+        self.tracks, self.bufsize, self.link = tracks, bufsize, link
+        self._h = C.c_void_p()
+        check(lib.gab_dyn_create(C.byref(self._h), tracks, bufsize, link))
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][8], or [n][8] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n, rest = divmod(table.numel(), len(self.FIELDS))
+        if rest or n == 0:
+            raise ValueError("table must hold whole rows of 8 values")
+        if first_track is None:
+            if n != self.tracks:
+                raise ValueError("table must hold a row per track (or give first_track)")
+            check(lib.gab_dyn_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
+        else:
+            check(lib.gab_dyn_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
+
+    def reset(self):
+        """The smoothed gain zero, current := target, a pending ramp dropped."""
+        check(lib.gab_dyn_reset(self._h, _stream()))
+
+    def process(self, x, key=None, out=None, gr=None):
+        """One buffer, track-major [tracks*bufsize]; out may be x itself.  key: the side chain the detector reads instead
+        of x (may not overlap out).  gr: a tensor [tracks] that receives the buffer's smallest smoothed gain."""
+        assert x.numel() == self.tracks * self.bufsize
+        out = torch.empty_like(x) if out is None else out
+        return self._run(lib.gab_dyn_process, x, key, out, gr, 1, ())
+
+    def process_batch(self, xs, key=None, out=None, gr=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch; key the same shape, gr [n][tracks]."""
+        n = _n_buffers(self, xs)
+        out = torch.empty_like(xs) if out is None else out
+        return self._run(lib.gab_dyn_process_batch, xs, key, out, gr, n, (n,))
+
+    def _run(self, fn, x, key, out, gr, n, extra):
+        assert out.numel() == x.numel() and (key is None or key.numel() == x.numel())
+        assert gr is None or gr.numel() == n * self.tracks
+        check(fn(self._h, _dev(x), None if key is None else _dev(key), _dev(out), None if gr is None else _dev(gr),
+                 *extra, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][8]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_dyn_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return _view(a.value, self.tracks, 8).clone(), _view(b.value, self.tracks, 8).clone()
+
+    def state(self):
+        """A copy of the smoothed gain, [tracks], log2 units."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_dyn_state(self._h, C.byref(p), C.byref(n)))
+        return _view(p.value, self.tracks, 1).clone().view(self.tracks)
+
+    def prepare(self, x, out, key=None, gr=None, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  All state that changes is on the device; capture with no ramp pending (which kernel form runs
+        is the host's choice at the call)."""
+        return (self._h, _dev(x), None if key is None else _dev(key), _dev(out), None if gr is None else _dev(gr),
+                _stream(stream))
+
+    launch = _launcher("gab_dyn_process")
+
+
 class MeterPlan(_Handle, _Prepared):
     """gab_meter_plan: one row of eight levels (FIELDS, all linear) per track and buffer, with carried state: the
     true-peak history, the weighting filter's state, the peak hold and a ring of the last `window` weighted mean

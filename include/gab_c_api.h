@@ -756,6 +756,100 @@ int gab_resample_process_batch(gab_resample_plan* plan, const float* d_in, float
 int gab_resample_state(gab_resample_plan* plan, float** d_hist, float** d_taps,
                        long long* buffers_since_reset_mod_period);
 
+/* ---- dynamics: a compressor / limiter per track, with a carried smoothed gain, ramped parameters, linked detectors
+ * and a side chain (additive; the reference has no dynamics) -----------------------------------------------------
+ * The block of a channel strip between the equaliser and the fader.  Level quantities are in log2 units: one unit is
+ * 6.0206 dB.  The contract calls no library transcendental: log2 and exp2 are the two polynomials below, fmaf by
+ * fmaf, so the device can be restated bit for bit.
+ *   parameters     device, [tracks][8] float32 (GAB_DYN_FIELDS):
+ *                    0 thr     threshold, log2 of the linear level           finite, |thr| <= 128
+ *                    1 slope   1 / ratio - 1                                 -1 <= slope <= 0 (0: off, -1: limiter)
+ *                    2 knee    half width of the soft knee                   0 <= knee <= 64
+ *                    3 kq      1 / (4 knee), 0 for a hard knee               finite, >= 0
+ *                    4 att     one-pole coefficient while the reduction grows    0 <= att <= 1 - 2^-20
+ *                    5 rel     the same while it shrinks                     0 <= rel <= 1 - 2^-20
+ *                    6 makeup  linear gain after the reduction               finite
+ *                    7 range   floor of the reduction                        finite, <= 0
+ *                  The plan carries two tables, `current` and `target`; a new plan has {0, 0, 0, 0, 0, 0, 1, -256} in
+ *                  both on every track and a smoothed gain of 0: pass-through bit for bit, for every finite or
+ *                  infinite sample.
+ *     set_params(ramp = 1)  target := the new table, current stays.  On the next processed buffer every one of the
+ *                  eight fields of every track is p[s] = fmaf(target - current, r[s], current), r[s] = (s + 1) /
+ *                  bufsize (the delay plan's table: float64 on the host, rounded once; target - current rounded
+ *                  once); after that buffer current := target by a copy.  Two sets before a buffer: the ramp still
+ *                  starts from current.
+ *     set_params(ramp = 0)  current := target := the new table, at once.
+ *     set_params_tracks     the same for rows [first_track, first_track + n_tracks), d_params [n_tracks][8]; the other
+ *                  rows keep their current and target.
+ *                  The values are checked on the device first, against the column `admitted` above.  A violation:
+ *                  GAB_ERR_INVALID_ARG naming the first (track, field) in index order; the plan keeps what it had.
+ *                  Both calls are synchronous with respect to `stream` and take effect with the next buffer.
+ *                  Why att and rel stop at 1 - 2^-20: a ramped value is the rounding of current + fl(target -
+ *                  current) r with 0 < r <= 1.  fl(target - current) is off by at most 2^-25, the fmaf's rounding of a
+ *                  value below 1 by at most 2^-25 more, so a ramped coefficient can land above the larger of its two
+ *                  ends, but by no more than 2^-24: it stays below 1 - 2^-20 + 2^-24 < 1, and the smoothing below
+ *                  stays a convex combination.  (slope, knee, kq and range cannot leave their sign: for ends of one
+ *                  sign fl(target - current) lies between -current and target by the monotonicity of rounding.)
+ *     reset        the smoothed gain zero, current := target, a pending ramp dropped.
+ *     params       the plan's own two tables, for inspection.
+ *     state        the smoothed gain, [tracks] float32, for inspection.
+ *     poly         host pointers to the pinned coefficients: c0..c6 and d0..d6 below.
+ *   create         tracks >= 1, bufsize >= 1, link a power of two in 1..64 with tracks % link == 0: tracks [g link,
+ *                  (g + 1) link) share one detector (stereo or surround linking); every track keeps its own parameters
+ *                  and its own smoothed gain.  Arguments are checked before any device call.
+ *   process        one buffer.  d_in and d_out track-major [t*B + s]; d_out == d_in is allowed (no other overlap).
+ *                  d_key is null or a block of the same shape that does not overlap d_out (refused): the side chain,
+ *                  which the detector reads instead of d_in (ducking; de-essing behind a gab_eq plan).  d_gr is null or
+ *                  [tracks]: per track the smallest smoothed gain of the buffer, the gain-reduction meter.  Any
+ *                  bufsize, any alignment, any track count: the same bits.
+ *   process_batch  n_buffers buffers back to back in one launch: d_in, d_key, d_out [n][T*B], d_gr [n][T]; a pending
+ *                  ramp runs through the first of them; same bits as n calls of process.  process and process_batch
+ *                  allocate nothing and wait for nothing; the smoothed gain is device state.
+ * The bits of one sample.  On a buffer without a pending ramp p = target, on one with a ramp the formula above.  Every
+ * + - * below is rounded once, fmaf only where written; fmaxf and fminf ignore a NaN operand and order -0 below +0.
+ * For sample n of track j in link group G, x the input, k the key block if one is given, else x, and s the track's
+ * carried smoothed gain (<= 0):
+ *     detector   a  = fmaxf over j' in G of |k[j'][n]|, from 0         (a NaN is ignored, as by the meter's peak)
+ *                v  = fmaxf(a, 2^-96);  u = the bits of v
+ *                e  = (int)(u >> 23) - 127;  m = the float of bits (u & 0x7fffff) | 0x3f800000;  t = m - 1   (exact)
+ *                r  = c6;  r = fmaf(r, t, c5);  ...  r = fmaf(r, t, c0);   L = (float)e + t * r
+ *                (-96 <= L <= 128 + 2^-18; an infinity reads e = 128, t = 0: L = 128)
+ *     computer   over = L - thr;   ok = over + knee
+ *                c  = over <= -knee ? 0 : over >= knee ? over : (ok * ok) * kq
+ *                g  = fmaxf(slope * c, range)
+ *     smoothing  al = (g < s) ? att : rel;   s = fmaf(al, s - g, g)
+ *     gain       sc = fminf(fmaxf(s, -126), 0);  nf = floorf(sc);  f = sc - nf                               (exact)
+ *                q  = d6;  q = fmaf(q, f, d5);  ...  q = fmaf(q, f, d0)
+ *                y  = x * ((q * the float of bits ((int)nf + 127) << 23) * makeup)
+ *     gr         fminf of s over the buffer's samples, from +infinity
+ * The polynomials: log2(1 + t) = t r(t) and exp2(f) = q(f) on [0, 1), degree 6 each, interpolated at Chebyshev nodes in
+ * float64 by tools/dyn_poly.py and rounded once per coefficient.  Worst error of the float32 chains: log2 1.3e-6
+ * absolute (2^-19.6) over all 2^23 mantissas, held to 2^-18 (2.3e-5 dB); exp2 6.5e-8 relative (2^-23.9), held to 2^-22.
+ *     c0..c6 = 0x1.715454p+0  -0x1.7139ccp-1  0x1.e8f4cep-2  -0x1.5a7f8ep-2  0x1.b627dcp-3  -0x1.839766p-4  0x1.47f3eap-6
+ *     d0..d6 = 1  0x1.62e43p-1  0x1.ebfc3ep-3  0x1.c69f98p-5  0x1.3c487cp-7  0x1.4cb7bp-10  0x1.b49554p-13
+ * L is finite for every input, so g and s stay finite whatever the samples are: a NaN or an infinity in x reaches y
+ * (x times a finite gain) and nothing else; a NaN in the key is ignored and an infinity reads as L = 128.  (The meter's
+ * filter state, by contrast, is poisoned by one such sample.)  Nothing else has rounding freedom: every launch form gives
+ * the same bits, and a shard of tracks that is a multiple of link, run as its own plan, gives those tracks' bits.
+ * Look-ahead is not part of the plan: a gab_delay plan in front of d_in, with the undelayed signal as d_key, gives it.
+ * The launch works on 64 tracks x 64 samples per wave: fewer than 64 tracks x 1024 use a part of the device.  One thread
+ * at a time per plan.                                                                                               */
+typedef struct gab_dyn_plan gab_dyn_plan;
+#define GAB_DYN_FIELDS 8
+int gab_dyn_create(gab_dyn_plan** plan, int tracks, int bufsize, int link);
+int gab_dyn_destroy(gab_dyn_plan* plan);
+int gab_dyn_set_params(gab_dyn_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_dyn_set_params_tracks(gab_dyn_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                              gab_stream_t stream);
+int gab_dyn_reset(gab_dyn_plan* plan, gab_stream_t stream);
+int gab_dyn_process(gab_dyn_plan* plan, const float* d_in, const float* d_key, float* d_out, float* d_gr,
+                    gab_stream_t stream);
+int gab_dyn_process_batch(gab_dyn_plan* plan, const float* d_in, const float* d_key, float* d_out, float* d_gr,
+                          int n_buffers, gab_stream_t stream);
+int gab_dyn_params(gab_dyn_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_dyn_state(gab_dyn_plan* plan, float** d_smooth, size_t* n_floats);
+int gab_dyn_poly(const float** log2_coeffs, int* n_log2, const float** exp2_coeffs, int* n_exp2);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
