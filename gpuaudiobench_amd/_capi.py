@@ -204,6 +204,19 @@ PROTOTYPES = {
     "gab_dyn_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_dyn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
     "gab_dyn_poly": (_I, [C.POINTER(C.POINTER(_F)), C.POINTER(_I), C.POINTER(C.POINTER(_F)), C.POINTER(_I)]),
+    "gab_reverb_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I]),
+    "gab_reverb_destroy": (_I, [_P]),
+    "gab_reverb_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_reverb_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_reverb_set_delays": (_I, [_P, _P, _P]),
+    "gab_reverb_set_delays_tracks": (_I, [_P, _P, _I, _I, _P]),
+    "gab_reverb_reset": (_I, [_P, _P]),
+    "gab_reverb_process": (_I, [_P, _P, _P, _P]),
+    "gab_reverb_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_reverb_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_reverb_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "gab_reverb_row_floats": (_I, [_I, _I]),
+    "gab_reverb_gmax": (_F, [_I]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -769,6 +769,149 @@ class DynamicsPlan(_Handle):
     launch = _launcher("gab_dyn_process")
 
 
+_REVERB_SPREAD = 4.65      # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)
+
+
+def _primes_from(lengths):
+    """Per length the smallest prime >= it that no earlier length took (ascending input: ascending, distinct output)."""
+    out, last = [], 1
+    for want in lengths:
+        p = max(int(want), last + 1, 2)
+        while any(p % d == 0 for d in range(2, int(p ** 0.5) + 1)):
+            p += 1
+        out.append(p)
+        last = p
+    return out
+
+
+def reverb_params(rt60_s, rt60_hf_s=None, size_ms=21.5, lines=8, outs=2, wet_db=-6.0, dry_db=0.0, fs=48000.0,
+                  delays=None):
+    """(delays int32 [T][N], table float32 [T][N (3 + outs) + 1]) of ReverbPlan from the knobs of a reverb; every
+    argument a scalar or an array with an entry per track (all scalars: T = 1); float64, rounded once.
+    delays: unless given ([N] or [T][N]), distinct primes ascending from size_ms, the targets spread geometrically up to
+    4.65 times that.  Line i of m samples gets g = 10^(-3 m / (rt60 fs)) / sqrt(N): -60 dB after rt60 seconds round the
+    loop.  rt60_hf_s (<= rt60_s) is the decay time at the Nyquist frequency: with rho the ratio of the two per-pass gains,
+    damp = (1 - rho) / (1 + rho), the one-pole whose Nyquist gain is rho and whose DC gain is 1; None: no damping.
+    b = 1; c[o] = wet / sqrt(N) times row 1 + o of the Hadamard matrix (signs (-1)^popcount(row & i)), so the two
+    outputs decorrelate; dry from dry_db.  g and damp are held to the plan's limits."""
+    import numpy as np
+    N, O = int(lines), int(outs)
+    if N not in (4, 8, 16) or O not in (1, 2):
+        raise ValueError("lines must be 4, 8 or 16 and outs 1 or 2")
+    knobs = [np.atleast_1d(np.asarray(a, np.float64)) for a in
+             (rt60_s, rt60_s if rt60_hf_s is None else rt60_hf_s, size_ms, wet_db, dry_db)]
+    if any(a.ndim != 1 for a in knobs):
+        raise ValueError("a knob is a scalar or has an entry per track")
+    T = max(a.shape[0] for a in knobs)
+    if delays is not None:
+        delays = np.asarray(delays)
+        if delays.ndim == 2:
+            T = max(T, delays.shape[0])
+    rt60, rt60_hf, size, wet_db, dry_db = (np.broadcast_to(a, (T,)) for a in knobs)
+    if (rt60 <= 0.0).any() or (rt60_hf <= 0.0).any() or (rt60_hf > rt60).any() or (size <= 0.0).any() or fs <= 0.0:
+        raise ValueError("needs rt60_s > 0, 0 < rt60_hf_s <= rt60_s, size_ms > 0, fs > 0")
+    if delays is None:
+        steps = _REVERB_SPREAD ** (np.arange(N, dtype=np.float64) / (N - 1))
+        m = np.array([_primes_from(np.rint(size[t] * fs / 1000.0 * steps)) for t in range(T)], np.int64)
+    else:
+        m = np.broadcast_to(delays.astype(np.int64), (T, N))
+    mf = m.astype(np.float64)
+    per_pass = 10.0 ** (-3.0 * mf / (rt60[:, None] * fs))
+    rho = 10.0 ** (-3.0 * mf / (rt60_hf[:, None] * fs)) / per_pass
+    gmax = np.float32(lib.gab_reverb_gmax(N))
+    g = np.minimum((per_pass / np.sqrt(float(N))).astype(np.float32), gmax)
+    damp = np.minimum(((1.0 - rho) / (1.0 + rho)).astype(np.float32), np.float32(1.0 - 2.0 ** -20))
+    i = np.arange(N)
+    signs = [np.array([(-1.0) ** bin((1 + o) & int(k)).count("1") for k in i]) for o in range(O)]
+    wet = 10.0 ** (wet_db / 20.0) / np.sqrt(float(N))
+    c = [(wet[:, None] * s[None, :]).astype(np.float32) for s in signs]
+    dry = (10.0 ** (dry_db / 20.0)).astype(np.float32)[:, None]
+    table = np.concatenate([g, damp, np.ones((T, N), np.float32)] + c + [dry], axis=1).astype(np.float32)
+    return np.ascontiguousarray(m.astype(np.int32)), np.ascontiguousarray(table)
+
+
+class ReverbPlan(_Handle, _Prepared):
+    """gab_reverb_plan: a feedback delay network per track: `lines` (4, 8, 16) delay lines of integer length fed back
+    through a Hadamard matrix with a damping low-pass in the loop, `outs` (1, 2) outputs per track.  Parameters per
+    track {g[N], damp[N], b[N], c[outs][N], dry} (reverb_params makes them from decay times) and a delay per line; a
+    new plan is pass-through; new parameters are ramped in over the next buffer unless ramp=False, new delays act from
+    the next buffer.  The output is [tracks*outs][bufsize], row t*outs + o."""
+
+    _destroy = "gab_reverb_destroy"
+
+    def __init__(self, tracks, bufsize, lines=8, outs=2, max_delay=8192):
+        self.tracks, self.bufsize, self.lines, self.outs, self.max_delay = tracks, bufsize, lines, outs, max_delay
+        self.row_floats = lines * (3 + outs) + 1
+        self._h = C.c_void_p()
+        check(lib.gab_reverb_create(C.byref(self._h), tracks, bufsize, lines, outs, max_delay))
+
+    def _rows(self, t, width, first_track, what):
+        n, rest = divmod(t.numel(), width)
+        if rest or n == 0:
+            raise ValueError("%s must hold whole rows of %d values" % (what, width))
+        if first_track is None and n != self.tracks:
+            raise ValueError("%s must hold a row per track (or give first_track)" % what)
+        return n
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][row_floats], or [n][row_floats] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n = self._rows(table, self.row_floats, first_track, "table")
+        if first_track is None:
+            check(lib.gab_reverb_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
+        else:
+            check(lib.gab_reverb_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
+
+    def set_delays(self, delays, first_track=None):
+        """delays: device int32 tensor [tracks][lines], or [n][lines] for tracks [first_track, first_track + n); they
+        act from the next buffer and the lines keep their contents."""
+        n = self._rows(delays, self.lines, first_track, "delays")
+        if first_track is None:
+            check(lib.gab_reverb_set_delays(self._h, _dev(delays, torch.int32), _stream()))
+        else:
+            check(lib.gab_reverb_set_delays_tracks(self._h, _dev(delays, torch.int32), first_track, n, _stream()))
+
+    def reset(self):
+        """Zero lines, positions and low-pass states, current := target, a pending ramp dropped; the delays stay."""
+        check(lib.gab_reverb_reset(self._h, _stream()))
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize] -> [tracks*outs*bufsize]; out may be x itself when outs == 1."""
+        assert x.numel() == self.tracks * self.bufsize
+        out = x.new_empty(x.numel() * self.outs) if out is None else out
+        assert out.numel() == x.numel() * self.outs
+        check(lib.gab_reverb_process(self._h, _dev(x), _dev(out), _stream()))
+        return out
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] -> [n][tracks*outs*bufsize] in one launch."""
+        n = _n_buffers(self, xs)
+        out = xs.new_empty(xs.numel() * self.outs) if out is None else out
+        assert out.numel() == xs.numel() * self.outs
+        check(lib.gab_reverb_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][row_floats]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_reverb_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return _view(a.value, self.tracks, self.row_floats).clone(), _view(b.value, self.tracks, self.row_floats).clone()
+
+    def state(self):
+        """Copies of (lines [tracks][lines][capacity] float32, write positions [tracks] int64, low-pass states
+        [tracks][lines] float32, delays [tracks][lines] int32)."""
+        r, p, q, d, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_reverb_state(self._h, C.byref(r), C.byref(cap), C.byref(p), C.byref(q), C.byref(d)))
+        T, N = self.tracks, self.lines
+        ring = _view(r.value, T * N, cap.value).clone().view(T, N, cap.value)
+        pos = _view(p.value, T, 1).clone().view(torch.int32).to(torch.int64).view(T)
+        return ring, pos, _view(q.value, T, N).clone(), _view(d.value, T, N).clone().view(torch.int32)
+
+    # prepare(x, out, stream=None): for a loop over the same buffers or a graph capture, with no ramp pending (which
+    # kernel form runs is the host's choice at the call); all state that changes is on the device.
+    launch = _launcher("gab_reverb_process")
+
+
 class MeterPlan(_Handle, _Prepared):
     """gab_meter_plan: one row of eight levels (FIELDS, all linear) per track and buffer, with carried state: the
     true-peak history, the weighting filter's state, the peak hold and a ring of the last `window` weighted mean

@@ -850,6 +850,100 @@ int gab_dyn_params(gab_dyn_plan* plan, float** d_current, float** d_target, size
 int gab_dyn_state(gab_dyn_plan* plan, float** d_smooth, size_t* n_floats);
 int gab_dyn_poly(const float** log2_coeffs, int* n_log2, const float** exp2_coeffs, int* n_exp2);
 
+/* ---- reverb: a feedback delay network per track, with carried lines, a damping low-pass in the loop and ramped
+ * gains (additive; the reference has no reverb) ----------------------------------------------------------------
+ * An algorithmic reverb beside the sampled room of gab_conv (scheme FDL) and the single line of gab_delay: N = `lines`
+ * delay lines per track (4, 8 or 16), fed back through the unnormalised Walsh-Hadamard matrix H (orthogonal up to
+ * sqrt(N)), a one-pole low-pass per line in the loop, O = `outs` outputs per track (1 or 2).
+ *   delays         device, [tracks][N] int32, in samples: GAB_REVERB_MIN_DELAY <= m[i] <= max_delay.  Not ramped: a new
+ *                  set acts from the next processed buffer, and the lines keep their contents (a line's history is
+ *                  simply read further back or less far).  A new plan has max_delay on every line.
+ *   parameters     device, [tracks][P] float32, P = gab_reverb_row_floats(N, O) = N (3 + O) + 1, one row per track:
+ *                    g[N]      the line's loop gain                          finite, |g| <= gab_reverb_gmax(N)
+ *                    damp[N]   the loop low-pass's coefficient               0 <= damp <= 1 - 2^-20
+ *                    b[N]      input gain into the line                      finite
+ *                    c[O][N]   output o's gain from line i, at (3 + o) N + i finite
+ *                    dry       the input's gain into every output            finite
+ *                  The plan carries two tables, `current` and `target`; a new plan has dry = 1 and zeros elsewhere in
+ *                  both on every track, zero lines and a zero low-pass state: pass-through for every finite sample,
+ *                  bit for bit (zeros are added to dry * x; only a -0 input comes out as +0).
+ *     set_params(ramp = 1)  target := the new table, current stays.  On the next processed buffer every field of every
+ *                  track is p[s] = fmaf(target - current, r[s], current), r[s] = (s + 1) / bufsize (the delay plan's
+ *                  table: float64 on the host, rounded once; target - current rounded once); after that buffer
+ *                  current := target by a copy.  Two sets before a buffer: the ramp still starts from current.
+ *     set_params(ramp = 0)  current := target := the new table, at once.
+ *     set_params_tracks     the same for rows [first_track, first_track + n_tracks), d_params [n_tracks][P]; the other
+ *                  rows keep their current and target.
+ *     set_delays, set_delays_tracks   the delays of every track, or of rows [first_track, first_track + n_tracks),
+ *                  d_delays [n_tracks][N].
+ *                  The values are checked on the device first, against the column `admitted` above.  A violation:
+ *                  GAB_ERR_INVALID_ARG naming the first (track, field) or (track, line) in index order; the plan keeps
+ *                  what it had, a pending ramp included.  All four calls are synchronous with respect to `stream` and
+ *                  take effect with the next buffer.
+ *                  Why these limits.  ||H|| = sqrt(N) and the low-pass is a convex combination (its gain never exceeds
+ *                  1), so the loop's gain is at most sqrt(N) max|g|.  gmax(N) is the float32 nearest
+ *                  (1 - 2^-20) / sqrt(N), formed in float64:
+ *                      GAB_REVERB_GMAX_4  = 0x1.ffffep-2f    GAB_REVERB_GMAX_8 = 0x1.6a09dp-2f
+ *                      GAB_REVERB_GMAX_16 = 0x1.ffffep-3f
+ *                  and sqrt(N) gmax(N) < 1 - 2^-21 for all three.  A ramped value is the rounding of current +
+ *                  fl(target - current) r with 0 < r <= 1: it can land beyond the larger of its two ends by no more than
+ *                  2^-24 (dynamics plan, same argument), which carries neither sqrt(N) |g| nor damp to 1.
+ *     reset        lines, write positions and low-pass states zero, current := target, a pending ramp dropped; the
+ *                  delays stay.
+ *     params       the plan's own two tables, for inspection.
+ *     state        for inspection: the lines ([tracks][N][capacity] float32, capacity a power of two >= max_delay +
+ *                  64), the capacity, the write positions ([tracks] unsigned: the ring index of the next sample, the
+ *                  same for every line of a track, a word per track that the kernel updates with ordinary vector
+ *                  stores), the low-pass states q ([tracks][N] float32) and the delays ([tracks][N] int32).
+ *   process        one buffer.  d_in track-major [t*B + s]; d_out [(t*O + o)*B + s]: a track's outputs are neighbouring
+ *                  rows, so a gab_mix plan of tracks*O tracks takes the block as it lies.  d_out == d_in is allowed when
+ *                  outs == 1 and refused when outs == 2 (no other overlap either way).  Any bufsize, any alignment, any
+ *                  track count: the same bits.
+ *   process_batch  n_buffers buffers back to back (d_in [n][T*B], d_out [n][T*O*B]) in one launch; a pending ramp runs
+ *                  through the first of them; same bits as n calls of process.  process and process_batch allocate
+ *                  nothing and wait for nothing; lines, positions and q are device state.
+ * The bits of one sample.  On a buffer without a pending ramp p = target, on one with a ramp the formula above, for
+ * every field.  Every + - * below is rounded once, fmaf only where written, nothing is re-associated, no library
+ * transcendental is called.  For absolute sample n of a track, x the input, line_i the track's i-th line (zero before
+ * the first sample and after a reset), q[i] its carried low-pass state:
+ *     1  s[i] = line_i[n - m[i]]
+ *     2  v[i] = g[i] * s[i]
+ *     3  q[i] = fmaf(damp[i], q[i] - v[i], v[i])            (q - v rounded once; DC gain 1, Nyquist (1 - d) / (1 + d))
+ *     4  u = H q: log2 N butterfly stages h = 1, 2, 4, ..., N / 2 in that order.  Stage h replaces, for every k with
+ *        (k & h) == 0, the pair (a, b) = (u[k], u[k + h]) by (a + b, a - b); u starts as q.
+ *     5  line_i[n] = fmaf(b[i], x[n], u[i])
+ *     6  for each output o: acc = dry * x[n]; acc = fmaf(c[o][i], q[i], acc) for i = 0 .. N-1 in that order;
+ *        y[o][n] = acc                                         (the q of step 3, not u)
+ * Samples that are not finite: a NaN or an infinity in a track's input enters that track's lines through step 5,
+ * comes round through steps 1 to 4 for ever and stays until reset; no other track is touched.  (The dynamics plan, by
+ * contrast, carries nothing that such a sample can reach.)
+ * Nothing else has rounding freedom: every launch form gives the same bits, and a shard of tracks as its own plan gives
+ * those tracks' bits.  The launch gives one wave 64 / N tracks: fewer than 64 / N x 1024 tracks use a part of the
+ * device.  tracks >= 1, bufsize >= 1, GAB_REVERB_MIN_DELAY <= max_delay <= 2^20; arguments are checked before any
+ * device call.  One thread at a time per plan.                                                                      */
+typedef struct gab_reverb_plan gab_reverb_plan;
+#define GAB_REVERB_MIN_DELAY 32
+#define GAB_REVERB_GMAX_4  0x1.ffffep-2f
+#define GAB_REVERB_GMAX_8  0x1.6a09dp-2f
+#define GAB_REVERB_GMAX_16 0x1.ffffep-3f
+int gab_reverb_create(gab_reverb_plan** plan, int tracks, int bufsize, int lines, int outs, int max_delay);
+int gab_reverb_destroy(gab_reverb_plan* plan);
+int gab_reverb_set_params(gab_reverb_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_reverb_set_params_tracks(gab_reverb_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                                 gab_stream_t stream);
+int gab_reverb_set_delays(gab_reverb_plan* plan, const int* d_delays, gab_stream_t stream);
+int gab_reverb_set_delays_tracks(gab_reverb_plan* plan, const int* d_delays, int first_track, int n_tracks,
+                                 gab_stream_t stream);
+int gab_reverb_reset(gab_reverb_plan* plan, gab_stream_t stream);
+int gab_reverb_process(gab_reverb_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_reverb_process_batch(gab_reverb_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_reverb_params(gab_reverb_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_reverb_state(gab_reverb_plan* plan, float** d_lines, size_t* capacity, unsigned** d_pos, float** d_q,
+                     int** d_delays);
+/* N (3 + O) + 1, or 0 for a (lines, outs) the plan does not take; gmax(N), or 0.  Host arithmetic. */
+int gab_reverb_row_floats(int lines, int outs);
+float gab_reverb_gmax(int lines);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
