@@ -42,7 +42,7 @@ static_assert(sizeof(EqRow<1>) == 4 * eq_row_words(1) && sizeof(EqRow<2>) == 4 *
 // The table.  One thread per (track, section) of the range [first_track, first_track + n_tracks).
 //   commit = 0: check only — a section outside the stability triangle (|a2| < 1, |a1| < 1 + a2) or with a value that
 //               is not finite lowers *flag to its index in the range (so the host names the FIRST one);
-//   commit = 1: write the rows (the arithmetic of make_scan_consts, k_recursive.hip, in float64, rounded once).
+//   commit = 1: write the rows (make_scan_consts' arithmetic, k_recursive.hip: float64, the (u, d) basis, rounded once).
 // src: [n_tracks][S][5] = {b0, b1, b2, a1, a2}; null: the identity filter.
 // The matrix powers are NOT formed in the hot kernel by float32 squaring: an error of 2^k eps in A^(M 2^k) multiplies
 // states that a low-frequency section makes hundreds of times larger than the signal.

@@ -11,6 +11,7 @@
 #include <atomic>
 #include <mutex>
 
+#include <cmath>
 #include <cstdint>
 
 #include "gab_common.hpp"
@@ -126,12 +127,23 @@ __global__ __launch_bounds__(256) void iir_biquad_kernel(const float* __restrict
 //   3. w[i] = w_local[i] + (row i of the homogeneous response) . S_l;
 //   4. y[n] = b0 w[n] + b1 w[n-1] + b2 w[n-2] element-wise.
 // 512 samples cost ~130 VALU ops per lane instead of a 512-step serial chain.
-// Rounding differs from the sequential golden by re-association only; the filter's
-// poles (radius sqrt(a2) = 0.41) make A^M tiny, so the result stays within ~1e-7.
+// Rounding differs from the sequential golden by re-association only, which is
+// harmless only in the right basis.  Steps 2 and 3 carry the state not as
+// (z1, z2) but as (u, d) = (z1, z1 - sg z2), sg = +1 for a1 <= 0 and -1 for
+// a1 > 0.  A section with poles near z = 1 has A^n ~ [n+1 -n; n -(n-1)] and
+// z1 ~ z2 hundreds of times the signal, so (n+1) z1 - n z2 in float32 loses
+// n eps |z|; on (z1, z1 - z2) the same map is ~ [1 n; small 1] acting on a
+// large u and a small d, and nothing cancels.  Poles near z = -1 (a1 > 0) are
+// the mirror image, z1 ~ -z2, and the small quantity is z1 + z2.  Steps 1
+// and 4 and the carried state stay on (z1, z2), one rounding per operation as
+// in the ordered kernel; steps 2 and 3, which re-associate anyway, fuse their
+// multiply-adds.  What this is held to, and the figures: tests/test_iir_scan_*.py,
+// profiles/r16_iir_scan_band.txt, DESIGN.md 4a.
 // ---------------------------------------------------------------------------
 struct IirScanConsts {
-    float alpha[16], beta[16];   // w-response of sample i to an incoming state (z1, z2)
-    float p[6][4];               // (A^M)^(2^k), row-major 2x2, acting on (z1, z2)
+    float alpha[16], beta[16];   // w-response of sample i to an incoming state (u, d) = (z1, z1 - sg z2)
+    float p[6][4];               // (A^M)^(2^k), row-major 2x2, acting on (u, d)
+    float sg;                    // +1: poles in the right half plane (a1 <= 0); -1: in the left
 };
 
 // H > 1: the buffer is H segments of 64*M samples scanned one after the other, the state running from one to
@@ -177,15 +189,15 @@ __global__ __launch_bounds__(256) void iir_scan_kernel(const float* __restrict__
             float wv = xs[h][i] - c.a1 * z1 - c.a2 * z2;
             z2 = z1; z1 = wv; w[i] = wv;
         }
-        // 2. inclusive scan of outgoing states: E_l = c_l + A^M E_{l-1}
-        float e1 = z1, e2 = z2;
+        // 2. inclusive scan of outgoing states, as (u, d) = (z1, z1 - sg z2): E_l = c_l + A^M E_{l-1}
+        float e1 = z1, e2 = fmaf(-k.sg, z2, z1);      // sg = +-1: the product is exact
 #pragma unroll
         for (int s = 0; s < 6; ++s) {
             const int d = 1 << s;
             float u1 = __shfl_up(e1, d, 64), u2 = __shfl_up(e2, d, 64);
             if (lane >= d) {
-                e1 += k.p[s][0] * u1 + k.p[s][1] * u2;
-                e2 += k.p[s][2] * u1 + k.p[s][3] * u2;
+                e1 = fmaf(k.p[s][1], u2, fmaf(k.p[s][0], u1, e1));
+                e2 = fmaf(k.p[s][3], u2, fmaf(k.p[s][2], u1, e2));
             }
         }
         // state entering this lane (lane 0 already started from the carried state)
@@ -193,7 +205,7 @@ __global__ __launch_bounds__(256) void iir_scan_kernel(const float* __restrict__
         if (lane == 0) { s1 = 0.0f; s2 = 0.0f; }
         // 3. homogeneous correction
 #pragma unroll
-        for (int i = 0; i < M; ++i) w[i] += k.alpha[i] * s1 + k.beta[i] * s2;
+        for (int i = 0; i < M; ++i) w[i] = fmaf(k.beta[i], s2, fmaf(k.alpha[i], s1, w[i]));
         // 4. output taps need w[n-1], w[n-2]: the previous lane's last two (or the carried state)
         float p1 = __shfl_up(w[M - 1], 1, 64);
         float p2 = (M >= 2) ? __shfl_up(w[M >= 2 ? M - 2 : 0], 1, 64) : __shfl_up(w[0], 2, 64);
@@ -226,28 +238,39 @@ __global__ __launch_bounds__(256) void iir_scan_kernel(const float* __restrict__
     }
 }
 
-// Host: constants of the scan for M samples per lane, computed in float64.
+// Host: constants of the scan for M samples per lane, formed in float64 from the powers of the state map on (z1, z2)
+// and stored as they act on (u, d) = (z1, z1 - sg z2), rounded once (eq_consts_kernel, k_eq.hip, does the same on the
+// device for a table of sections, with sg = 1).  With T = [1 0; 1 -sg], T^-1 = [1 0; sg -sg]: a power P acts as T P T^-1.
 inline IirScanConsts make_scan_consts(const BiquadCoeffs& c, int M) {
     IirScanConsts k{};
+    const double sg = c.a1 > 0.0f ? -1.0 : 1.0;
+    k.sg = (float)sg;
     // state map per sample on (z1, z2): z1' = -a1 z1 - a2 z2 (+x), z2' = z1
-    double A[4] = {-(double)c.a1, -(double)c.a2, 1.0, 0.0};
-    double P[4] = {1, 0, 0, 1};
-    auto mul = [](const double* X, const double* Y, double* Z) {
-        double r[4] = {X[0] * Y[0] + X[1] * Y[2], X[0] * Y[1] + X[1] * Y[3],
-                       X[2] * Y[0] + X[3] * Y[2], X[2] * Y[1] + X[3] * Y[3]};
-        for (int i = 0; i < 4; ++i) Z[i] = r[i];
-    };
-    for (int i = 0; i < M; ++i) {
-        mul(A, P, P);                       // P = A^(i+1); its first row is w[i]'s response
-        k.alpha[i] = (float)P[0];
-        k.beta[i] = (float)P[1];
+    const double A0 = -(double)c.a1, A1 = -(double)c.a2;
+    double P0 = 1.0, P1 = 0.0, P2 = 0.0, P3 = 1.0;
+    for (int i = 0; i < M; ++i) {           // P = A P = A^(i+1); its first row is w[i]'s response to (z1, z2)
+        const double n0 = A0 * P0 + A1 * P2, n1 = A0 * P1 + A1 * P3;
+        P2 = P0; P3 = P1; P0 = n0; P1 = n1;
+        k.alpha[i] = (float)(P0 + sg * P1);      // ... to (u, d): z1 = u, z2 = sg (u - d)
+        k.beta[i] = (float)(-sg * P1);
     }
-    double Q[4] = {P[0], P[1], P[2], P[3]}; // A^M
-    for (int s = 0; s < 6; ++s) {
-        for (int i = 0; i < 4; ++i) k.p[s][i] = (float)Q[i];
-        mul(Q, Q, Q);
+    for (int s = 0; s < 6; ++s) {           // A^M, squared five times
+        k.p[s][0] = (float)(P0 + sg * P1); k.p[s][1] = (float)(-sg * P1);
+        k.p[s][2] = (float)((P0 + sg * P1) - sg * (P2 + sg * P3)); k.p[s][3] = (float)(P3 - sg * P1);
+        const double q0 = P0 * P0 + P1 * P2, q1 = P0 * P1 + P1 * P3, q2 = P2 * P0 + P3 * P2, q3 = P2 * P1 + P3 * P3;
+        P0 = q0; P1 = q1; P2 = q2; P3 = q3;
     }
     return k;
+}
+
+// The scan takes a section that is finite and inside the stability triangle (eq_consts_kernel's check).  Outside it the
+// sixth power overflows and inf * 0 puts a NaN where the golden has a number: such a section takes the ordered kernel.
+inline bool scan_takes(const BiquadCoeffs& c) {
+    const float v[5] = {c.b0, c.b1, c.b2, c.a1, c.a2};
+    for (float f : v)
+        if (!std::isfinite(f)) return false;
+    const double a1 = c.a1, a2 = c.a2;
+    return std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2;
 }
 
 // ---------------------------------------------------------------------------
@@ -976,8 +999,8 @@ int gab_iir(const float* d_in, float* d_out, const float* coeffs, float* d_state
         const bool scan_ok = bufsize % 64 == 0 && (m == 1 || m == 2 || m == 4 || m == 8 || m == 16) &&
                              (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0 &&
                              (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
-        if (!scan_ok) return gab_iir_sequential(d_in, d_out, coeffs, d_state, tracks, bufsize, stream);
         gab::BiquadCoeffs c{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]};
+        if (!scan_ok || !gab::scan_takes(c)) return gab_iir_sequential(d_in, d_out, coeffs, d_state, tracks, bufsize, stream);
         // 512 and 1024 samples, many tracks (bandwidth-bound): segments of 256, one contiguous KiB per load
         // instruction — 65 536 x 512: 43.3 us against 48.0 (0.78 against 0.70 of 8 TB/s); at 8 192 tracks the two
         // scans in a row cost more (10.3 against 10.0 us) than the tidier accesses save, so fewer tracks keep one scan

@@ -126,9 +126,23 @@ int gab_keep_warm_destroy(gab_keep_warm* warm);
  * coeffs = {b0,b1,b2,a1,a2} (HOST pointer, 5 floats), d_state = T x {z1,z2}
  * read and written back.
  * gab_iir: one wavefront per track, wave-level scan of the state recurrence
- * (bufsize in {64,128,256,512,1024}, 16-byte aligned buffers; other shapes take
- * the sequential kernel).  Re-associates the recurrence: within ~1e-7 of the
- * golden, not bit-identical.
+ * (bufsize in {64,128,256,512,1024}, 16-byte aligned buffers).  Re-associates
+ * the recurrence, so not bit-identical to the golden.  The scan carries the
+ * state as (z1, z1 - z2) for a1 <= 0 and (z1, z1 + z2) for a1 > 0, so that
+ * poles next to z = 1 or z = -1 cancel nothing.  Tested, not proven: outputs
+ * and carried state are within max(1e-5, 4 e32) of the float64 filter's peak,
+ * e32 being what the ordered float32 form itself loses against float64 on the
+ * same input, on sixteen sections in every form (tests/test_iir_scan_gpu.py:
+ * high-passes, a shelf, Q 30 bells and notches from 20 Hz to 23 kHz at 48 and
+ * 96 kHz, the mirror image of a 30 Hz high-pass; with the reference's filter
+ * ~1e-7 of the golden).  Not covered: real poles next to BOTH z = 1 and z = -1
+ * (a2 within 1e-4 of -1), where no one basis serves; a CPU restatement of the
+ * scan measures up to 6 e32 there.  At bufsize 512 and 1024 the scan's form,
+ * and with it the last bits of a track, depends on `tracks` (from 16 384 on
+ * the buffer is scanned in 256-sample segments).  Any other bufsize, unaligned
+ * buffers, and a section that is outside the stability triangle (|a2| < 1,
+ * |a1| < 1 + a2) or holds a value that is not finite take gab_iir_sequential's
+ * kernel and give its bits.
  * gab_iir_sequential: one lane per track in the golden's exact operation order,
  * bit-identical to it.                                                        */
 int gab_iir(const float* d_in, float* d_out, const float* coeffs,
