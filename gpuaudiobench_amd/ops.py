@@ -761,8 +761,8 @@ class DynamicsPlan(_Handle):
 
     def prepare(self, x, out, key=None, gr=None, stream=None):
         """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
-        `launch(args)`.  All state that changes is on the device; capture with no ramp pending (which kernel form runs
-        is the host's choice at the call)."""
+        `launch(args)`.  All state that changes is on the device; which kernel form runs (steady, or the ramp form when
+        a ramp is pending) is the host's choice at the call and what a capture replays: gab_c_api.h, "Captured calls"."""
         return (self._h, _dev(x), None if key is None else _dev(key), _dev(out), None if gr is None else _dev(gr),
                 _stream(stream))
 
@@ -907,8 +907,9 @@ class ReverbPlan(_Handle, _Prepared):
         pos = _view(p.value, T, 1).clone().view(torch.int32).to(torch.int64).view(T)
         return ring, pos, _view(q.value, T, N).clone(), _view(d.value, T, N).clone().view(torch.int32)
 
-    # prepare(x, out, stream=None): for a loop over the same buffers or a graph capture, with no ramp pending (which
-    # kernel form runs is the host's choice at the call); all state that changes is on the device.
+    # prepare(x, out, stream=None): for a loop over the same buffers or a graph capture; all state that changes is on the
+    # device, and which kernel form runs (steady, or the ramp form when a ramp is pending) is the host's choice at the
+    # call and what a capture replays: gab_c_api.h, "Captured calls".
     launch = _launcher("gab_reverb_process")
 
 

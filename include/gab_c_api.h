@@ -489,6 +489,34 @@ int gab_fdtd_strip(gab_fdtd_plan* plan, float** d_strip, int* capacity);
 /* Copy the plan's own pressure planes (nx*ny*(z_end-z_begin) floats, x fastest) to d_dst. */
 int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t stream);
 
+/* ---- Captured calls: what a stream capture of the plans below bakes in -----------------------------------------
+ * The process calls of the eq, mix, delay, meter, resample, dynamics and reverb plans allocate nothing and wait for
+ * nothing, so they can be recorded into a graph (hipStreamBeginCapture), one behind the other on one stream, as the
+ * blocks of a channel strip.  A capture records the launches without running them: no state moves.  All state that a
+ * buffer changes is on the device and is read and written by every replay.  What the HOST decides at the call is fixed
+ * by the capture, and a replay repeats it whatever the host has been told since:
+ *   pending / kernel form   dynamics, delay, reverb, mix: whether a ramp is pending picks the kernel form.  Captured
+ *                       with none pending, every replay runs the steady form: it reads `target` alone, so values set
+ *                       with ramp = 0 are in force from the next replay and values set with ramp = 1 too, at once and
+ *                       without their ramp (`current` is never brought up to them).  Captured with a ramp pending,
+ *                       every replay runs the ramp form, g = fmaf(target - current, r[s], current) read from the
+ *                       device's tables at the replay, and the current := target copy behind it is in the graph.  So
+ *                       the first replay is the ramp buffer; behind it target - current is +0 and fmaf(+0, r, c) is c
+ *                       for every c but -0.0 (which comes out as +0.0): later replays give the steady form's bits as
+ *                       long as no table holds a -0.0; and a set with ramp = 1 between two replays is ramped in by the
+ *                       next replay, as between two plain calls.  The call that was captured also cleared the host's
+ *                       flag, as if the ramp had run.
+ *   mix's ramp_first    the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
+ *                       one that takes the ramp form.
+ *   meter's decay       a launch argument: set_decay after the capture does not reach the replays.
+ *   alignment           eq picks the scan or the sequential kernel, mix, dynamics and meter the width of their loads,
+ *                       from the 16-byte alignment of the pointers given: the pointers are the graph's in any case.
+ *   resample's position a launch argument, (k mod period) at the capture: every replay resamples from that position.
+ *                       The captured call also advanced the host's k by its buffers, as a call that ran; with
+ *                       period == 1 both are without effect and the replays are the stream's next buffers.
+ * set_* calls and reset synchronise or belong to the host and stay outside a capture.  Held by
+ * tests/test_strip_gpu.py for the whole strip in one graph and for every plan alone. */
+
 /* ---- biquad cascades: a parametric equaliser per track (additive; no counterpart in the reference, whose
  * IIRFilterKernel runs ONE biquad shared by every track) --------------------------------------------------
  * `tracks` channels, `sections` second-order sections in series on each (1..16), every (track, section) with its
@@ -754,7 +782,8 @@ int gab_meter_state(gab_meter_plan* plan, float** d_hist, float** d_filter, floa
  *                  the next buffer; history and position are kept.  Synchronous with respect to `stream`.
  * A shard of tracks as its own plan gives those tracks' bits.  process and process_batch are one launch each, allocate
  * nothing and wait for nothing.  The position is a launch argument: a captured process replays one position and is only
- * meaningful when period == 1.  Arguments are checked before any device call: tracks >= 1, 1 <= bufsize <= 2^20, up
+ * meaningful when period == 1; the captured call also advances the host's k, as a call that ran ("Captured calls",
+ * above).  Arguments are checked before any device call: tracks >= 1, 1 <= bufsize <= 2^20, up
  * and down in 1..1024, taps even and in 4..256 (GAB_ERR_INVALID_ARG); L K <= 16384 floats, the table that fits 64 KiB
  * of LDS (else GAB_ERR_UNSUPPORTED).  The launch works on 64 tracks x 64 input samples at a time: fewer than 64 tracks x
  * 256 use a part of the device.  One thread at a time per plan.                                                     */

@@ -12,46 +12,13 @@ import numpy as np
 import pytest
 
 from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
-from test_delay_host import (INTERPS, Line, capacity, delay_mix, delay_reference_f32, min_delay, mix_ramp, noise,
-                             table)
+from test_delay_host import (INTERPS, Twin, capacity, delay_mix, min_delay, noise, table)
 
 pytestmark = pytest.mark.gpu
 
 # (tracks, bufsize, max_delay, buffers).  2 * capacity / B + 2 buffers where the wrap is the point (capacity 256 and 2048),
 # three or four where the capacity is large (a steady buffer, the ramp buffer, the steady buffer behind it).
 SHAPES = [(5, 100, 37, 8), (64, 64, 1000, 66), (130, 512, 4096, 4), (4100, 512, 600, 3), (3, 2048, 70000, 3), (1, 1, 2, 20)]
-
-
-class Twin:
-    """The plan's state machine on the host: current, target, a pending ramp, the lines; process() is
-    delay_reference_f32."""
-
-    def __init__(self, T, B, max_delay, interp):
-        self.T, self.B, self.M, self.interp = T, B, max_delay, interp
-        self.cur = table(T, min_delay(interp), 0.0, 0.0, 1.0)
-        self.tgt = self.cur.copy()
-        self.pending = False
-        self.line = Line(T, max_delay)
-
-    def set_params(self, p, ramp=True, first_track=0):
-        n = p.shape[0]
-        self.tgt[first_track:first_track + n] = p
-        if ramp:
-            self.pending = True
-        else:
-            self.cur[first_track:first_track + n] = p
-
-    def reset(self):
-        self.line = Line(self.T, self.M)
-        self.cur[:] = self.tgt
-        self.pending = False
-
-    def process(self, x):
-        y = delay_reference_f32(x, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.line, self.interp)
-        if self.pending:
-            self.cur[:] = self.tgt
-            self.pending = False
-        return y
 
 
 def run(plan, x):

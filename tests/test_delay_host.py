@@ -153,6 +153,38 @@ def delay_reference_f64(x, cur, tgt, ramp, line, interp):
     return _run(x, cur, tgt, ramp, line, interp, True)
 
 
+class Twin:
+    """The plan's state machine on the host: current, target, a pending ramp, the lines; process() is
+    delay_reference_f32."""
+
+    def __init__(self, T, B, max_delay, interp):
+        self.T, self.B, self.M, self.interp = T, B, max_delay, interp
+        self.cur = table(T, min_delay(interp), 0.0, 0.0, 1.0)
+        self.tgt = self.cur.copy()
+        self.pending = False
+        self.line = Line(T, max_delay)
+
+    def set_params(self, p, ramp=True, first_track=0):
+        n = p.shape[0]
+        self.tgt[first_track:first_track + n] = p
+        if ramp:
+            self.pending = True
+        else:
+            self.cur[first_track:first_track + n] = p
+
+    def reset(self):
+        self.line = Line(self.T, self.M)
+        self.cur[:] = self.tgt
+        self.pending = False
+
+    def process(self, x):
+        y = delay_reference_f32(x, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.line, self.interp)
+        if self.pending:
+            self.cur[:] = self.tgt
+            self.pending = False
+        return y
+
+
 def delay_bound(interp, F, W, wet=1.0, out_peak=0.0):
     """(bound on |w32 - w64|, bound on |y32 - y64|): the derivation in the module's docstring."""
     lam, k = (1.0, 3.0) if interp == "linear" else (1.25, 11.0)

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
-from test_dynamics_host import IDENTITY, dyn_mix, dyn_reference_f32, mix_ramp, noise, row
+from test_dynamics_host import IDENTITY, Twin, dyn_mix, noise, row
 from test_mix_host import fma32  # noqa: F401 (the restatement's fmaf)
 
 pytestmark = pytest.mark.gpu
@@ -25,39 +25,6 @@ pytestmark = pytest.mark.gpu
 # of tracks 64..71 starts a wave, 256..263 is a last wave of eight tracks)
 SHAPES = [(1, 1, 1), (2, 3, 2), (63, 65, 1), (64, 64, 64), (65, 200, 1), (130, 512, 2), (264, 200, 8), (128, 65, 64),
           (64, 3, 8)]
-
-
-class Twin:
-    """The plan's state machine on the host: current, target, a pending ramp, the smoothed gain; process() is
-    dyn_reference_f32."""
-
-    def __init__(self, T, B, link=1):
-        self.T, self.B, self.link = T, B, link
-        self.cur = np.tile(IDENTITY, (T, 1))
-        self.tgt = self.cur.copy()
-        self.pending = False
-        self.s = np.zeros(T, np.float32)
-
-    def set_params(self, p, ramp=True, first_track=0):
-        n = p.shape[0]
-        self.tgt[first_track:first_track + n] = p
-        if ramp:
-            self.pending = True
-        else:
-            self.cur[first_track:first_track + n] = p
-
-    def reset(self):
-        self.s = np.zeros(self.T, np.float32)
-        self.cur[:] = self.tgt
-        self.pending = False
-
-    def process(self, x, key=None):
-        y, gr, self.s = dyn_reference_f32(x, key, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.s,
-                                          self.link)
-        if self.pending:
-            self.cur[:] = self.tgt
-            self.pending = False
-        return y, gr
 
 
 def same(a, b):

@@ -173,6 +173,39 @@ def dyn_reference_f64(x, key, cur, tgt, ramp, s, link=1):
     return y, gr, s
 
 
+class Twin:
+    """The plan's state machine on the host: current, target, a pending ramp, the smoothed gain; process() is
+    dyn_reference_f32."""
+
+    def __init__(self, T, B, link=1):
+        self.T, self.B, self.link = T, B, link
+        self.cur = np.tile(IDENTITY, (T, 1))
+        self.tgt = self.cur.copy()
+        self.pending = False
+        self.s = np.zeros(T, np.float32)
+
+    def set_params(self, p, ramp=True, first_track=0):
+        n = p.shape[0]
+        self.tgt[first_track:first_track + n] = p
+        if ramp:
+            self.pending = True
+        else:
+            self.cur[first_track:first_track + n] = p
+
+    def reset(self):
+        self.s = np.zeros(self.T, np.float32)
+        self.cur[:] = self.tgt
+        self.pending = False
+
+    def process(self, x, key=None):
+        y, gr, self.s = dyn_reference_f32(x, key, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.s,
+                                          self.link)
+        if self.pending:
+            self.cur[:] = self.tgt
+            self.pending = False
+        return y, gr
+
+
 def dyn_bound(Lmax, Tmax, K, S, G, A):
     """The bound on |s32 - s64| of the module's docstring, in log2 units."""
     dL = 2.0 ** -18 + EPS * Lmax

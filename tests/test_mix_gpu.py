@@ -12,6 +12,7 @@ import pytest
 from plan_helpers import bits, dev, gab, host  # noqa: F401 (gab: the fixture)
 from test_mix_host import (EPS, gains, mix_ramp, mix_reference_f32, noise, one_hot_case, small_integer_case,
                            tree_bound)
+from test_mix_host import Twin as HostTwin
 
 pytestmark = pytest.mark.gpu
 
@@ -30,34 +31,9 @@ def run(plan, x, layout="track"):
     return host(plan.process(arrange(x, layout), layout=layout)).reshape(plan.buses, plan.bufsize)
 
 
-class Twin:
-    """The plan's state machine on the host: current, target, a pending ramp; process() is mix_reference_f32."""
-
-    def __init__(self, plan):
-        self.T, self.B, self.M = plan.tracks, plan.bufsize, plan.buses
-        self.L, self.G = plan.form
-        self.cur = np.zeros((self.T, self.M), np.float32)
-        self.tgt = np.zeros((self.T, self.M), np.float32)
-        self.pending = False
-
-    def set_gains(self, g, ramp=True, first=0):
-        n = g.shape[0]
-        self.tgt[first:first + n] = g
-        if ramp:
-            self.pending = True
-        else:
-            self.cur[first:first + n] = g
-
-    def reset(self):
-        self.cur[:] = self.tgt
-        self.pending = False
-
-    def process(self, x):
-        y = mix_reference_f32(x, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.L, self.G)
-        if self.pending:
-            self.cur[:] = self.tgt
-            self.pending = False
-        return y
+def Twin(plan):
+    """The host twin (tests/test_mix_host.py) of this plan's shape, given the form the plan reports."""
+    return HostTwin(plan.tracks, plan.bufsize, plan.buses, *plan.form)
 
 
 def same_gains(plan, twin):

@@ -105,6 +105,37 @@ def mix_reference_f32(x, current, target, r, leaf_tracks, group_leaves):
     return out
 
 
+class Twin:
+    """The plan's state machine on the host: current, target, a pending ramp; process() is mix_reference_f32 with the
+    form (leaf_tracks, group_leaves) it is given, which a device test holds against plan.form."""
+
+    def __init__(self, tracks, bufsize, buses, leaf_tracks, group_leaves):
+        self.T, self.B, self.M = tracks, bufsize, buses
+        self.L, self.G = leaf_tracks, group_leaves
+        self.cur = np.zeros((self.T, self.M), np.float32)
+        self.tgt = np.zeros((self.T, self.M), np.float32)
+        self.pending = False
+
+    def set_gains(self, g, ramp=True, first=0):
+        n = g.shape[0]
+        self.tgt[first:first + n] = g
+        if ramp:
+            self.pending = True
+        else:
+            self.cur[first:first + n] = g
+
+    def reset(self):
+        self.cur[:] = self.tgt
+        self.pending = False
+
+    def process(self, x):
+        y = mix_reference_f32(x, self.cur, self.tgt, mix_ramp(self.B) if self.pending else None, self.L, self.G)
+        if self.pending:
+            self.cur[:] = self.tgt
+            self.pending = False
+        return y
+
+
 def mix_gains_f64(current, target, r):
     cur, tgt = np.asarray(current, np.float32).astype(np.float64), np.asarray(target, np.float32).astype(np.float64)
     if r is None:
