@@ -502,7 +502,8 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       every replay runs the ramp form, g = fmaf(target - current, r[s], current) read from the
  *                       device's tables at the replay, and the current := target copy behind it is in the graph.  So
  *                       the first replay is the ramp buffer; behind it target - current is +0 and fmaf(+0, r, c) is c
- *                       for every c but -0.0 (which comes out as +0.0): later replays give the steady form's bits as
+ *                       for every c but -0.0 (which comes out as +0.0; "Values at the edges of float32", below): later
+ *                       replays give the steady form's bits as
  *                       long as no table holds a -0.0; and a set with ramp = 1 between two replays is ramped in by the
  *                       next replay, as between two plain calls.  The call that was captured also cleared the host's
  *                       flag, as if the ramp had run.
@@ -516,6 +517,27 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       period == 1 both are without effect and the replays are the stream's next buffers.
  * set_* calls and reset synchronise or belong to the host and stay outside a capture.  Held by
  * tests/test_strip_gpu.py for the whole strip in one graph and for every plan alone. */
+
+/* ---- Values at the edges of float32: what the ordered forms of the plans below do there ---------------------------
+ * The mix, delay, meter, resample, dynamics and reverb plans, and the equaliser's and gab_iir's sequential forms, state
+ * their bits as a sequence of float32 operations rounded once each.  That sentence holds over the whole of float32:
+ *   subnormals     are kept.  No operation flushes an operand or a result to zero, fmaxf / fminf / floorf included: a
+ *                  tail that dies away walks its carried state down through the subnormals to zero exactly as IEEE 754
+ *                  arithmetic does, and a product that underflows is rounded once, to a subnormal or to a zero of the
+ *                  product's sign.
+ *   overflow       is IEEE 754's: a result beyond FLT_MAX after its one rounding is an infinity of its sign (FLT_MAX +
+ *                  2^102 is FLT_MAX, FLT_MAX + 2^103 is +inf; fmaf(FLT_MAX, 2, -FLT_MAX) is FLT_MAX, the product is
+ *                  never rounded alone); inf - inf and 0 * inf are NaN.  Finite samples can therefore put an infinity
+ *                  or a NaN into whatever a plan carries; each plan's section says how long such a value stays.  The
+ *                  meter's nonfinite field speaks of the samples, not of what its own arithmetic overflowed to.
+ *   NaN            which NaN comes out (sign, payload) is unspecified; that it is a NaN is not.
+ *   zeros          have the sign that the stated sequence of operations gives: x * y has the product of the signs, an
+ *                  exact zero sum is +0 unless both addends are -0.  So fmaf(+0, r, c) is c for every c but -0.0: a
+ *                  table value of -0.0 is a -0.0 on a buffer without a ramp and a +0.0 on a ramp buffer on which its
+ *                  row did not move.  A mix bus sums from +0.0 and never gives -0.0.
+ * Held by tests/test_edges_host.py (the restatements against exact rational arithmetic, and that the cases reach
+ * these values) and tests/test_edges_gpu.py (the kernels against the restatements bit for bit, every carried state
+ * included).  The scan forms of the equaliser and of gab_iir are held to float64 by a bound, not to this. */
 
 /* ---- biquad cascades: a parametric equaliser per track (additive; no counterpart in the reference, whose
  * IIRFilterKernel runs ONE biquad shared by every track) --------------------------------------------------
@@ -665,6 +687,9 @@ int gab_mix_form(const gab_mix_plan* plan, int* leaf_tracks, int* group_leaves);
  *     (fr == 0: hm, h1, h2 are zeros and h0 is exactly 1, so v == w[n-i].)
  *     w[n] = fmaf(feedback, v, x[n])                                what enters the line
  *     y[n] = fmaf(wet, v, dry * x[n])                               the output (dry * x[n] rounded once)
+ * Samples that are not finite: a NaN or an infinity in a track's input enters that track's line and stays until reset,
+ * whatever the feedback: with feedback 0 too, since w[n] = fmaf(0, v, x[n]) is a NaN when the tap v is a NaN or an
+ * infinity, so the value comes round once per delay for good.  No other track is touched.
  * Nothing else has rounding freedom: every launch form gives the same bits, and a shard of tracks as its own plan gives
  * those tracks' bits.  Precision: delay is a float32, so a delay near 2^17 samples resolves 2^-7 of a sample.
  * Stability: |feedback| < 1 bounds a linear line (its two weights are non-negative and sum to 1, loop gain |feedback|).

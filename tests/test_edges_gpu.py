@@ -1,0 +1,288 @@
+"""The six bit-exact plans on the device at the edges of float32: tails that die through the subnormals, sums across
+FLT_MAX, signed zeros, NaN and infinity containment, and one strip case.
+
+Every case is a row of tests/test_edges_host.py's CASES.  Its tape of calls, recorded while the float32 twin ran it, is
+replayed on the real plan; every buffer's outputs (meter rows, gain reduction and counts among them) and at the end every
+carried state the plan exposes must be the twin's under same(): equal bits, two NaNs counting as equal whatever their
+payload.  Each tape runs twice, by per-buffer calls and with every run of consecutive buffers as one process_batch; the
+cases marked `offset` pass every block through a pointer 4 bytes off 16-byte alignment.  That the cases hold subnormals,
+infinities, NaNs and -0.0 at all is established on the host (test_the_cases_reach_the_edge); nothing here asserts it.
+"""
+import numpy as np
+import pytest
+
+from plan_helpers import dev, gab, host  # noqa: F401 (gab: the fixture)
+from strip_helpers import DeviceStrip, differing as strip_differing, same, schedule, states_differing
+from test_delay_host import capacity as delay_capacity
+from test_edges_host import CASES, case_id, differing, mix_form, play, reference, strip_tail
+
+pytestmark = pytest.mark.gpu
+
+
+def sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+class Blocks:
+    """Device blocks, 16-byte aligned or (offset) 4 bytes past that."""
+
+    def __init__(self, offset):
+        self.offset = 1 if offset else 0
+
+    def put(self, a, dtype=np.float32):
+        import torch
+        a = np.ascontiguousarray(a, dtype).ravel()
+        big = torch.zeros(a.size + 4, dtype=torch.float32, device="cuda")
+        assert big.data_ptr() % 16 == 0
+        t = big[self.offset:self.offset + a.size]
+        t.copy_(torch.from_numpy(a.copy()))
+        return t
+
+    def blank(self, n):
+        import torch
+        big = torch.full((n + 4,), 7.0, device="cuda")
+        return big[self.offset:self.offset + n]
+
+
+class Dev:
+    """What the device actors share: run() is a process call, run_batch() one process_batch over the buffers."""
+
+    def __init__(self, gab, offset):
+        self.gab, self.mem = gab, Blocks(offset)
+
+    def run(self, x, key=None):
+        return self.launch([x], [key], False)[0]
+
+    def run_batch(self, xs, keys):
+        return self.launch(xs, keys, True)
+
+    def reset(self):
+        self.p.reset()
+
+    def params(self, p, ramp):
+        self.p.set_params(dev(p), ramp=ramp)
+
+    def close(self):
+        self.p.close()
+
+
+class DevMix(Dev):
+    def __init__(self, gab, offset, T, B, M, layout="track"):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape, self.layout = gab.MixPlan(T, B, M), (M, B), layout
+        assert self.p.form == mix_form(M)                          # the form the twin was given
+
+    def gains(self, g, ramp):
+        self.p.set_gains(dev(g), ramp=ramp)
+
+    def launch(self, xs, keys, batch):
+        n, (M, B) = len(xs), self.shape
+        xs = np.stack(xs)
+        x = self.mem.put(xs.transpose(0, 2, 1) if self.layout == "sample" else xs)
+        out = self.mem.blank(n * M * B)
+        (self.p.process_batch if batch else self.p.process)(x, out=out, layout=self.layout)
+        return [{"y": y} for y in host(out).reshape(n, M, B)]
+
+    def state(self, twin):
+        cur, tgt = self.p.gains()
+        return {"current": host(cur), "target": host(tgt)}
+
+
+class DevDelay(Dev):
+    def __init__(self, gab, offset, T, B, M, interp):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.DelayPlan(T, B, M, interp), (T, B, M)
+
+    def launch(self, xs, keys, batch):
+        n, (T, B, M) = len(xs), self.shape
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * B)
+        (self.p.process_batch if batch else self.p.process)(x, out=out)
+        return [{"y": y} for y in host(out).reshape(n, T, B)]
+
+    def state(self, twin):
+        T, B, M = self.shape
+        (cur, tgt), (ring, pos) = self.p.params(), self.p.line()
+        ring, line = host(ring), twin.twin.line
+        cap, H = ring.shape[1], line.hist.shape[1]
+        assert cap == delay_capacity(B, M)
+        return {"current": host(cur), "target": host(tgt), "pos": host(pos),
+                "line": ring[:, (line.count - H + np.arange(H)) % cap]}        # the newest max_delay + 3 words
+
+
+class DevMeter(Dev):
+    def __init__(self, gab, offset, T, B, W):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.MeterPlan(T, B, W), (T, B)
+
+    def decay(self, v):
+        self.p.set_decay(v)
+
+    def launch(self, xs, keys, batch):
+        n, (T, B) = len(xs), self.shape
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * 8)
+        (self.p.process_batch if batch else self.p.process)(x, out=out)
+        return [{"rows": r} for r in host(out).reshape(n, T, 8)]
+
+    def state(self, twin):
+        hist, filt, ring, pos = (host(t) for t in self.p.state())
+        assert not hist[:, 13:].any()
+        return {"hist": hist[:, :11], "hold": hist[:, 11], "true_peak_max": hist[:, 12], "filter": filt, "ring": ring,
+                "pos": pos}
+
+
+class DevResample(Dev):
+    def __init__(self, gab, offset, T, B, up, down, K):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.ResamplePlan(T, B, up, down, K), (T, B)
+        assert self.p.ntaps == K
+
+    def launch(self, xs, keys, batch):
+        n, (T, B), OC = len(xs), self.shape, self.p.out_capacity
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * OC)
+        if batch:
+            counts = self.p.process_batch(x, out=out)[1]
+        else:
+            counts = [self.p.process(x, out=out)[1]]
+        return [{"y": y, "count": np.array([c], np.int64)} for y, c in zip(host(out).reshape(n, T, OC), counts)]
+
+    def state(self, twin):
+        hist, k = self.p.state()
+        return {"hist": host(hist), "k": np.array([k], np.int64)}
+
+
+class DevDyn(Dev):
+    def __init__(self, gab, offset, T, B, link, keyed):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.DynamicsPlan(T, B, link), (T, B)
+
+    def launch(self, xs, keys, batch):
+        n, (T, B) = len(xs), self.shape
+        assert all(k is None for k in keys) or all(k is not None for k in keys)
+        x, out, gr = self.mem.put(np.stack(xs)), self.mem.blank(n * T * B), self.mem.blank(n * T)
+        key = None if keys[0] is None else self.mem.put(np.stack(keys))
+        (self.p.process_batch if batch else self.p.process)(x, key=key, out=out, gr=gr)
+        return [{"y": y, "gr": g} for y, g in zip(host(out).reshape(n, T, B), host(gr).reshape(n, T))]
+
+    def state(self, twin):
+        cur, tgt = self.p.params()
+        return {"current": host(cur), "target": host(tgt), "s": host(self.p.state())}
+
+
+class DevReverb(Dev):
+    def __init__(self, gab, offset, T, B, N, O, M):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.ReverbPlan(T, B, lines=N, outs=O, max_delay=M), (T, B, O, M)
+
+    def delays(self, d):
+        self.p.set_delays(dev(d))
+
+    def launch(self, xs, keys, batch):
+        n, (T, B, O, M) = len(xs), self.shape
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * O * B)
+        (self.p.process_batch if batch else self.p.process)(x, out=out)
+        return [{"y": y} for y in host(out).reshape(n, T * O, B)]
+
+    def state(self, twin):
+        T, B, O, M = self.shape
+        (cur, tgt), (ring, pos, q, delays) = self.p.params(), self.p.state()
+        ring, rv = host(ring), twin.twin
+        cap = ring.shape[2]
+        assert cap == rv.cap
+        return {"current": host(cur), "target": host(tgt), "q": host(q), "pos": host(pos), "delays": host(delays),
+                "lines": ring[:, :, (rv.pos - M + np.arange(M)) & (cap - 1)]}   # the newest max_delay words
+
+
+DEVS = {"mix": DevMix, "delay": DevDelay, "meter": DevMeter, "resample": DevResample, "dyn": DevDyn, "reverb": DevReverb}
+
+
+def run_on_device(gab, case, ops, batch):
+    """(outputs per buffer, the carried state at the end) of the tape on a new plan."""
+    twin = reference(case)[3]
+    actor = DEVS[case.plan](gab, case.offset, *case.shape)
+    outs = play(ops, actor, batch=batch)
+    sync()
+    state = actor.state(twin)
+    actor.close()
+    return outs, state
+
+
+# ---- a, b, c, d: every case against its twin -------------------------------------------------------------------------
+@pytest.mark.parametrize("batch", [False, True], ids=["per-buffer", "batched"])
+@pytest.mark.parametrize("case", CASES, ids=case_id)
+def test_the_plan_is_its_twin_at_the_edge(gab, case, batch):
+    ops, want, want_state, _ = reference(case)
+    got, state = run_on_device(gab, case, ops, batch)
+    assert differing(got, want) == []
+    assert differing([state], [want_state]) == []
+
+
+# ---- d. containment: the clean run beside the dirty one ----------------------------------------------------------------
+@pytest.mark.parametrize("case", [c for c in CASES if c.regime.startswith("contain")], ids=case_id)
+def test_a_nan_and_an_infinity_stay_where_the_twin_has_them(gab, case):
+    """Mix: the buffers before the one that holds the samples are the clean run's (and so are those behind it: a mix
+    carries nothing).  Delay: every other track's bits are the clean run's in every buffer.  The clean run is the clean
+    twin's; the dirty run against the dirty twin is test_the_plan_is_its_twin_at_the_edge."""
+    T = case.shape[0]
+    ops_d, want_d, _, _ = reference(case)
+    ops_c, want_c, state_c, _ = reference(case, dirty=False)
+    dirty, _ = run_on_device(gab, case, ops_d, False)
+    clean, state = run_on_device(gab, case, ops_c, False)
+    assert differing(clean, want_c) == [] and differing([state], [state_c]) == []
+    assert differing(dirty, want_d) == []
+    if case.plan == "mix":
+        assert differing(dirty[:1], clean[:1]) == [] and differing(dirty[2:], clean[2:]) == []
+        assert not same(dirty[1]["y"], clean[1]["y"])
+    else:
+        others = np.ones(T, bool)
+        others[[64, T - 1]] = False
+        for k, (d, c) in enumerate(zip(dirty, clean)):
+            assert same(d["y"][others], c["y"][others]), k
+            assert np.array_equal(np.isfinite(d["y"]), np.isfinite(want_d[k]["y"])), k
+        assert same(dirty[-1]["y"], clean[-1]["y"])                 # behind the reset
+
+
+# ---- e. one strip case ---------------------------------------------------------------------------------------------
+def test_the_strips_tail_plain(gab):
+    """The existing schedule on one loud buffer and silence behind it, scaled so that the composed restatement walks into
+    the subnormals within the schedule's seven buffers: every output and every carried state."""
+    sc, want, twin = strip_tail(True)
+    strip = DeviceStrip(gab, sc, sequential=True)
+    assert strip.mix.form == sc.mix_form
+    strip.run()
+    sync()
+    assert strip_differing(strip.outputs(), want) == []
+    assert states_differing(strip, twin) == []
+    strip.close()
+
+
+def test_the_strips_tail_in_one_captured_graph(gab):
+    """The same tail with buffer 0's tables alone at 2/1 (a captured resampler replays one position): buffer 0 by plain
+    calls, then one graph of a buffer's nine launches replayed on the silence behind it."""
+    import torch
+    sc, want, twin = strip_tail(False)
+    strip = DeviceStrip(gab, sc)
+    assert strip.resample.period == 1 and strip.eq.form == (0, 0)       # bufsize 100: the ordered equaliser
+    schedule(strip, sc, 0)
+    strip.process(0)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        launch = strip.prepare(1)
+        with torch.cuda.graph(graph, stream=side):
+            count = launch()
+    torch.cuda.current_stream().wait_stream(side)
+    sync()
+    xs, keys = dev(sc.xs.reshape(sc.n, -1)), dev(sc.keys.reshape(sc.n, -1))
+    for k in range(1, sc.n):
+        strip.buf[1].copy_(xs[k])
+        strip.key[1].copy_(keys[k])
+        graph.replay()
+        sync()
+        got = strip.outputs(1)
+        bad = [name for name in sorted(got) if not same(got[name], want[name][k])]
+        assert bad == [] and count == want["counts"][k], k
+    assert states_differing(strip, twin) == []
+    del graph
+    strip.close()

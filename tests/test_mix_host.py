@@ -31,18 +31,20 @@ EPS = 2.0 ** -24
 
 def fma32(a, b, c):
     a, b, c = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32))
-    p = a.astype(np.float64) * b.astype(np.float64)          # exact
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    e = (p - (s - bb)) + (c - bb)                            # p + c = s + e exactly
-    r = s.astype(np.float32)                                 # nearest-even on s
-    diff = s - r.astype(np.float64)                          # exact
-    other = np.nextafter(r, np.where(diff > 0, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
     with np.errstate(invalid="ignore", over="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)      # exact
+        c = c.astype(np.float64)
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)                        # p + c = s + e exactly
+        r = s.astype(np.float32)                             # nearest-even on s
+        diff = s - r.astype(np.float64)                      # exact
+        other = np.nextafter(r, np.where(diff > 0, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
         half = (diff != 0) & (s == (r.astype(np.float64) + other.astype(np.float64)) * 0.5)
         beyond = half & (e != 0) & ((e > 0) == (diff > 0))   # the true sum is past the half-way point
-    return np.where(beyond, other, r).astype(np.float32)
+    # An operand that is not finite makes s an infinity or a NaN, which is fmaf's own answer; the residual means nothing
+    # there (inf - inf), and without this line fma32(+inf, 1, 0) came out as FLT_MAX (tests/test_edges_host.py).
+    return np.where(np.isfinite(s) & beyond, other, r).astype(np.float32)
 
 
 def fma32_double_rounded(a, b, c):
