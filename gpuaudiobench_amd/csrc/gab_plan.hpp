@@ -1,7 +1,10 @@
-// gab_plan.hpp — what the host halves of the eq, mix and delay plans share: who owns device memory,
-// "check, then commit" for a set of parameters, and the table that is ramped from current to target over one buffer.
+// gab_plan.hpp — what the host halves of the plans share: eq, mix, delay, meter, resample, dynamics and
+// reverb, and the fdl convolution for its memory.  Who owns device memory; "check, then commit" for a set of parameters
+// (one check kernel, a rule per plan); the entries of a ranged set; the table that is ramped from current to target
+// over one buffer.
 #pragma once
 
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -31,16 +34,28 @@ private:
 };
 
 // ---- check, then commit: the check ----
-// A plan's check kernel lowers *flag (atomicMin) to the index of every value it refuses, so the host can name the FIRST.
-// The flag starts as all ones, which therefore no index may be: a set of more than kMaxChecked values is refused unread.
+// The check kernel lowers *flag (atomicMin) to the index of every value the plan's rule refuses, so the host can name
+// the FIRST.  The flag starts as all ones, which therefore no index may be: a set of more than kMaxChecked values is
+// refused unread.
 constexpr unsigned kNoneRefused = 0xffffffffu;
 constexpr size_t kMaxChecked = 0xfffffff0u;
 
 // An infinity or a NaN, from the value's bits (__float_as_uint): the integer test, whatever the compiler knows of the float.
 __device__ __forceinline__ bool not_finite(unsigned float_bits) { return (float_bits & 0x7f800000u) == 0x7f800000u; }
 
-// launch_check() launches the plan's check kernel on s.  *first: the smallest refused index, or kNoneRefused.  The stream
-// has been synchronised when this returns GAB_OK; the caller writes its tables only after it has looked at *first.
+// A Rule is a small trivially copyable struct, passed by value, that holds the plan's few numbers and has
+//   __device__ bool refuses(const T* src, size_t i) const    is src[i] outside the contract?  (src, not the value: a rule
+//                                                            may read a neighbour of the value it judges)
+//   std::string refusal(unsigned i, int first_track) const   the text behind "<who>: " for a refused index i (host)
+template <class T, class Rule>
+__global__ __launch_bounds__(256) void check_kernel(const T* __restrict__ src, unsigned* __restrict__ flag, size_t n,
+                                                   Rule rule) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && rule.refuses(src, i)) atomicMin(flag, (unsigned)i);
+}
+
+// launch_check() launches a check kernel on s.  *first: the smallest refused index, or kNoneRefused.  The stream has been
+// synchronised when this returns GAB_OK; the caller writes its tables only after it has looked at *first.
 template <class F>
 int first_refused(const DeviceBuf<unsigned>& flag, hipStream_t s, const char* kernel, F&& launch_check, unsigned* first) {
     GAB_HIP_CHECK(hipMemsetAsync(flag.get(), 0xff, sizeof(unsigned), s));
@@ -51,8 +66,51 @@ int first_refused(const DeviceBuf<unsigned>& flag, hipStream_t s, const char* ke
     return GAB_OK;
 }
 
+// check, then commit: n values at d_src against the rule on s; commit() only if none is refused.  A refused set has
+// touched nothing but the flag, and the stream is synchronised.  commit() synchronises too: d_src is the caller's again.
+template <class T, class Rule, class Commit>
+int check_then(const DeviceBuf<unsigned>& flag, hipStream_t s, const char* who, const T* d_src, size_t n,
+               const Rule& rule, int first_track, Commit&& commit) {
+    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
+    unsigned first_bad = kNoneRefused;
+    if (int rc = first_refused(flag, s, "check_kernel", [&] {
+            check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_src, flag.get(), n, rule);
+        }, &first_bad))
+        return rc;
+    if (first_bad != kNoneRefused) {
+        set_last_error(std::string(who) + ": " + rule.refusal(first_bad, first_track));
+        return GAB_ERR_INVALID_ARG;
+    }
+    commit();
+    return GAB_OK;
+}
+
+// ---- the entries ----
 inline bool track_range_ok(int plan_tracks, int first_track, int n_tracks) {
     return !(first_track < 0 || n_tracks <= 0 || first_track > plan_tracks - n_tracks);
+}
+
+// The body of gab_X_set_* (whole: every track of the plan) and of gab_X_set_*_tracks (tracks [first_track, first_track +
+// n_tracks)): null pointers, then the range, then the plan's set(plan, d_src, first_track, n_tracks, who, rest...).
+template <class F, class P, class S, class... A>
+int set_entry(const char* who, F set, P* plan, const S* d_src, bool whole, int first_track, int n_tracks, A... rest) {
+    return guarded([&]() -> int {
+        if (!plan || !d_src) return bad_arg((std::string(who) + ": null pointer").c_str());
+        if (whole) return set(plan, d_src, 0, plan->tracks, who, rest...);
+        if (!track_range_ok(plan->tracks, first_track, n_tracks))
+            return bad_arg((std::string(who) + ": the track range is outside the plan").c_str());
+        return set(plan, d_src, first_track, n_tracks, who, rest...);
+    });
+}
+
+// The body of gab_X_destroy; text: what a null plan is answered with.
+template <class P>
+int destroy_plan(P* plan, const char* text) {
+    return guarded([&]() -> int {
+        if (!plan) return bad_arg(text);
+        delete plan;
+        return GAB_OK;
+    });
 }
 
 // ---- the ramped table ----
@@ -71,6 +129,22 @@ struct RampedTable {
         std::vector<float> r((size_t)bufsize);
         for (int s = 0; s < bufsize; ++s) r[(size_t)s] = (float)(((double)s + 1.0) / (double)bufsize);
         GAB_HIP_CHECK(hipMemcpy(ramp.get(), r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+
+    // `row` on every one of `tracks` tracks, in current and in target: what a new plan holds.
+    void fill(const std::vector<float>& row, int tracks) {
+        std::vector<float> init;
+        init.reserve(row.size() * (size_t)tracks);
+        for (int t = 0; t < tracks; ++t) init.insert(init.end(), row.begin(), row.end());
+        GAB_HIP_CHECK(hipMemcpy(current.get(), init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemcpy(target.get(), init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+
+    // for gab_X_params / gab_mix_gains: the tables themselves, not copies
+    void expose(float** d_current, float** d_target, size_t* n_floats) const {
+        *d_current = current.get();
+        *d_target = target.get();
+        *n_floats = current.size();
     }
 
     // The commit, for values that passed the check: n floats at `offset` of target; of current too unless they are

@@ -28,11 +28,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <stdexcept>
 #include <type_traits>
 
-#include "gab_common.hpp"
 #include "gab_fft.hpp"
+#include "gab_plan.hpp"
 #include "k_conv_fdl.hpp"
 
 namespace gab {
@@ -297,11 +298,11 @@ struct Plan {
     bool spread = false;
     int cur = 0;                // prev[cur] holds the previous block
     const cf* tw = nullptr;
-    cf* H = nullptr;            // [K][plane]
-    cf* X = nullptr;            // [ring][plane]
-    cf* Xs = nullptr;           // [plane]: a stateless call's spectrum (the delay line is not touched)
-    cf* Y = nullptr;            // [spread ? G : 1][kChunk][plane]
-    float* prev[2] = {nullptr, nullptr};   // [T][B], taken in turn
+    DeviceBuf<cf> H;            // [K][plane]
+    DeviceBuf<cf> X;            // [ring][plane]
+    DeviceBuf<cf> Xs;           // [plane]: a stateless call's spectrum (the delay line is not touched)
+    DeviceBuf<cf> Y;            // [spread ? G : 1][kChunk][plane]
+    DeviceBuf<float> prev[2];   // [T][B], taken in turn
 };
 
 bool shape_ok(int tracks, int bufsize, int ir_len) {
@@ -309,53 +310,43 @@ bool shape_ok(int tracks, int bufsize, int ir_len) {
            ir_len >= 1 && ir_len <= (1 << 21);
 }
 
-void destroy(Plan* f) {
-    if (!f) return;
-    for (void* ptr : {(void*)f->H, (void*)f->X, (void*)f->Xs, (void*)f->Y, (void*)f->prev[0], (void*)f->prev[1]})
-        if (ptr) (void)hipFree(ptr);
-    delete f;
-}
+void destroy(Plan* f) { delete f; }
 
 Plan* create(int tracks, int bufsize, int ir_len) {
     if (!shape_ok(tracks, bufsize, ir_len)) throw std::invalid_argument("the fdl scheme: unsupported shape");
-    Plan* f = new Plan;
-    try {
-        f->T = tracks; f->B = bufsize; f->L = ir_len;
-        f->pairs = (tracks + 1) / 2;
-        f->bins = bufsize + 1;
-        f->K = (ir_len + bufsize - 1) / bufsize;
-        f->G = (f->K + kGroup - 1) / kGroup;
-        f->plane = (size_t)tracks * f->bins;
-        f->ring = (unsigned)(f->K + kChunk - 1);
-        f->spread = f->G > 1 && f->plane < kSpreadBelow;
-        f->tw = fft::device_twiddles();
-        const size_t sp = sizeof(cf) * f->plane;
-        GAB_HIP_CHECK(hipMalloc(&f->H, sp * f->K));
-        GAB_HIP_CHECK(hipMalloc(&f->X, sp * f->ring));
-        GAB_HIP_CHECK(hipMalloc(&f->Xs, sp));
-        GAB_HIP_CHECK(hipMalloc(&f->Y, sp * kChunk * (f->spread ? f->G : 1)));
-        for (float*& pv : f->prev) GAB_HIP_CHECK(hipMalloc(&pv, sizeof(float) * (size_t)tracks * bufsize));
-        GAB_HIP_CHECK(hipMemset(f->X, 0, sp * f->ring));
-        for (float* pv : f->prev) GAB_HIP_CHECK(hipMemset(pv, 0, sizeof(float) * (size_t)tracks * bufsize));
-        GAB_HIP_CHECK(hipMemset(f->H, 0, sp * f->K));
-    } catch (...) {
-        destroy(f);
-        throw;
-    }
-    return f;
+    auto f = std::make_unique<Plan>();      // a throw below frees what has been allocated
+    f->T = tracks; f->B = bufsize; f->L = ir_len;
+    f->pairs = (tracks + 1) / 2;
+    f->bins = bufsize + 1;
+    f->K = (ir_len + bufsize - 1) / bufsize;
+    f->G = (f->K + kGroup - 1) / kGroup;
+    f->plane = (size_t)tracks * f->bins;
+    f->ring = (unsigned)(f->K + kChunk - 1);
+    f->spread = f->G > 1 && f->plane < kSpreadBelow;
+    f->tw = fft::device_twiddles();
+    f->H.alloc(f->plane * f->K);
+    f->X.alloc(f->plane * f->ring);
+    f->Xs.alloc(f->plane);
+    f->Y.alloc(f->plane * kChunk * (f->spread ? f->G : 1));
+    for (auto& pv : f->prev) pv.alloc((size_t)tracks * bufsize);
+    GAB_HIP_CHECK(hipMemset(f->X.get(), 0, sizeof(cf) * f->X.size()));
+    for (auto& pv : f->prev) GAB_HIP_CHECK(hipMemset(pv.get(), 0, sizeof(float) * pv.size()));
+    GAB_HIP_CHECK(hipMemset(f->H.get(), 0, sizeof(cf) * f->H.size()));
+    return f.release();
 }
 
 void set_ir(Plan* f, const float* d_ir, hipStream_t s) {
     with_n(f->B, [&](auto nc) {
         constexpr int N = decltype(nc)::value;
-        fdl_ir_spectra_kernel<N><<<dim3(f->pairs, f->K), dim3(N / Radix<N>::R), 0, s>>>(d_ir, f->H, f->tw, f->T, f->L, f->plane);
+        fdl_ir_spectra_kernel<N><<<dim3(f->pairs, f->K), dim3(N / Radix<N>::R), 0, s>>>(d_ir, f->H.get(), f->tw, f->T, f->L,
+                                                                                        f->plane);
     });
     check_launch("fdl_ir_spectra_kernel");
 }
 
 void reset(Plan* f, hipStream_t s) {
-    GAB_HIP_CHECK(hipMemsetAsync(f->X, 0, sizeof(cf) * f->plane * f->ring, s));
-    for (float* pv : f->prev) GAB_HIP_CHECK(hipMemsetAsync(pv, 0, sizeof(float) * (size_t)f->T * f->B, s));
+    GAB_HIP_CHECK(hipMemsetAsync(f->X.get(), 0, sizeof(cf) * f->plane * f->ring, s));
+    for (auto& pv : f->prev) GAB_HIP_CHECK(hipMemsetAsync(pv.get(), 0, sizeof(float) * (size_t)f->T * f->B, s));
     f->pos = 0;
     f->cur = 0;
 }
@@ -366,29 +357,31 @@ namespace {
 // in Xs, partition 0 only.
 void run_chunk(Plan* f, const float* in, float* out, int n, bool stateless, hipStream_t s) {
     MacArgs a;
-    a.H = f->H;
+    a.H = f->H.get();
     a.plane = f->plane;
     a.n = n;
     if (stateless) {
-        a.X = f->Xs; a.Y = f->Y; a.K = 1; a.G = 1; a.ring = 1; a.slot0 = 0; a.spread = 0;
+        a.X = f->Xs.get(); a.Y = f->Y.get(); a.K = 1; a.G = 1; a.ring = 1; a.slot0 = 0; a.spread = 0;
     } else {
-        a.X = f->X; a.Y = f->Y; a.K = f->K; a.G = f->G; a.ring = f->ring; a.slot0 = f->pos; a.spread = f->spread ? 1 : 0;
+        a.X = f->X.get(); a.Y = f->Y.get(); a.K = f->K; a.G = f->G; a.ring = f->ring; a.slot0 = f->pos;
+        a.spread = f->spread ? 1 : 0;
     }
     const int parts = a.spread ? a.G : 1;
     with_n(f->B, [&](auto nc) {
         constexpr int N = decltype(nc)::value;
         const dim3 grid(f->pairs, n), block(N / Radix<N>::R);
         if (stateless)
-            fdl_forward_kernel<N><<<grid, block, 0, s>>>(in, nullptr, nullptr, f->Xs, f->tw, f->T, 0u, 1u, f->plane);
+            fdl_forward_kernel<N><<<grid, block, 0, s>>>(in, nullptr, nullptr, f->Xs.get(), f->tw, f->T, 0u, 1u,
+                                                         f->plane);
         else
-            fdl_forward_kernel<N><<<grid, block, 0, s>>>(in, f->prev[f->cur], f->prev[f->cur ^ 1], f->X, f->tw, f->T,
-                                                         f->pos, f->ring, f->plane);
+            fdl_forward_kernel<N><<<grid, block, 0, s>>>(in, f->prev[f->cur].get(), f->prev[f->cur ^ 1].get(),
+                                                         f->X.get(), f->tw, f->T, f->pos, f->ring, f->plane);
         check_launch("fdl_forward_kernel");
         const dim3 mgrid((unsigned)((f->plane + kMacThreads - 1) / kMacThreads), parts);
         if (n == 1) fdl_mac_kernel<1><<<mgrid, dim3(kMacThreads), 0, s>>>(a);
         else fdl_mac_kernel<kChunk><<<mgrid, dim3(kMacThreads), 0, s>>>(a);
         check_launch("fdl_mac_kernel");
-        fdl_inverse_kernel<N><<<grid, block, 0, s>>>(f->Y, out, f->tw, f->T, parts, n, f->plane);
+        fdl_inverse_kernel<N><<<grid, block, 0, s>>>(f->Y.get(), out, f->tw, f->T, parts, n, f->plane);
         check_launch("fdl_inverse_kernel");
     });
     if (!stateless) {

@@ -9,7 +9,8 @@
 //                            for Lagrange), m the smallest integer delay of the segment: a chunk's taps end before the
 //                            chunk begins, so its lanes are independent; the chunks follow each other in order.
 //                            m >= the segment: one chunk.  m = 1: one sample at a time.
-//   delay_check_kernel       refuses a parameter row outside the contract, naming the first.
+//   DelayRule                refuses a parameter row outside the contract, naming the first (gab_plan.hpp's check
+//                            kernel).
 //
 // The sequence of roundings per sample is the header's; nothing here re-associates.  What the cut decides is only where
 // a value is fetched from, so every launch form gives the same bits.
@@ -241,18 +242,27 @@ __global__ __launch_bounds__(kDelayWaves * 64) void delay_kernel(const float* in
     if (lane == 0) pos[t] = P;
 }
 
-// src: [n_rows][4].  The smallest index of a value the contract refuses.
-__global__ __launch_bounds__(256) void delay_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag,
-                                                         size_t n, float dmin, float dmax) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = src[i];
-    const int field = (int)(i & 3);
-    bool bad = not_finite(__float_as_uint(v));
-    if (field == 0) bad = bad || !(v >= dmin && v <= dmax);
-    if (field == 1) bad = bad || !(fabsf(v) < 1.0f);
-    if (bad) atomicMin(flag, (unsigned)i);
-}
+const char* const kDelayFields[4] = {"delay", "feedback", "wet", "dry"};
+
+// src: [n_rows][4]
+struct DelayRule {
+    float dmin, dmax;
+    __device__ bool refuses(const float* src, size_t i) const {
+        const float v = src[i];
+        const int field = (int)(i & 3);
+        bool bad = not_finite(__float_as_uint(v));
+        if (field == 0) bad = bad || !(v >= dmin && v <= dmax);
+        if (field == 1) bad = bad || !(fabsf(v) < 1.0f);
+        return bad;
+    }
+    std::string refusal(unsigned i, int first_track) const {
+        const int field = (int)(i & 3u);
+        const char* rule = field == 0 ? "must be finite and within [min_delay, max_delay]"
+                                      : (field == 1 ? "must be finite and below 1 in magnitude" : "must be finite");
+        return "track " + std::to_string(first_track + (int)(i / 4u)) + " field " + std::to_string(field) + " (" +
+               kDelayFields[field] + ") " + rule + "; the plan keeps its parameters";
+    }
+};
 
 }  // namespace
 }  // namespace gab
@@ -268,8 +278,6 @@ struct gab_delay_plan {
 
 namespace gab {
 namespace {
-
-const char* const kDelayFields[4] = {"delay", "feedback", "wet", "dry"};
 
 // n buffers in one launch; then, if a ramp ran through the first of them, current := target.  Nothing is allocated and
 // nothing waits here.
@@ -294,27 +302,11 @@ int delay_process(gab_delay_plan* p, const float* d_in, float* d_out, int n_buff
 }
 
 // check, then commit (gab_plan.hpp): a refused set leaves both tables and a pending ramp as they were.
-int delay_set_range(gab_delay_plan* p, const float* d_params, int first_track, int n_tracks, int ramp, hipStream_t s,
-                    const char* who) {
+int delay_set_range(gab_delay_plan* p, const float* d_params, int first_track, int n_tracks, const char* who, int ramp,
+                    hipStream_t s) {
     const size_t n = (size_t)n_tracks * 4;
-    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = kNoneRefused;
-    if (int rc = first_refused(p->flag, s, "delay_check_kernel", [&] {
-            delay_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_params, p->flag.get(), n,
-                                                                                 (float)p->min_delay, (float)p->max_delay);
-        }, &first_bad))
-        return rc;
-    if (first_bad != kNoneRefused) {
-        const int field = (int)(first_bad & 3u);
-        const char* rule = field == 0 ? "must be finite and within [min_delay, max_delay]"
-                                      : (field == 1 ? "must be finite and below 1 in magnitude" : "must be finite");
-        set_last_error(std::string(who) + ": track " + std::to_string(first_track + (int)(first_bad / 4u)) + " field " +
-                       std::to_string(field) + " (" + kDelayFields[field] + ") " + rule +
-                       "; the plan keeps its parameters");
-        return GAB_ERR_INVALID_ARG;
-    }
-    p->params.commit(d_params, (size_t)first_track * 4, n, ramp != 0, s);
-    return GAB_OK;
+    return check_then(p->flag, s, who, d_params, n, DelayRule{(float)p->min_delay, (float)p->max_delay}, first_track,
+                      [&] { p->params.commit(d_params, (size_t)first_track * 4, n, ramp != 0, s); });
 }
 
 }  // namespace
@@ -339,19 +331,12 @@ int gab_delay_create(gab_delay_plan** out, int tracks, int bufsize, int max_dela
         auto p = std::make_unique<gab_delay_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->max_delay = max_delay; p->interp = interp;
         p->min_delay = min_delay; p->capacity = cap;
-        const size_t n = (size_t)tracks * 4;
-        p->params.create(n, bufsize);
+        p->params.create((size_t)tracks * 4, bufsize);
         p->ring.alloc((size_t)tracks * cap);
         p->pos.alloc((size_t)tracks);
         p->flag.alloc(1);
         // pass-through: {min_delay, 0, 0, 1} on every track, an empty line
-        std::vector<float> init(n);
-        for (int t = 0; t < tracks; ++t) {
-            init[(size_t)t * 4 + 0] = (float)min_delay; init[(size_t)t * 4 + 1] = 0.0f;
-            init[(size_t)t * 4 + 2] = 0.0f;             init[(size_t)t * 4 + 3] = 1.0f;
-        }
-        GAB_HIP_CHECK(hipMemcpy(p->params.current.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemcpy(p->params.target.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        p->params.fill({(float)min_delay, 0.0f, 0.0f, 1.0f}, tracks);
         GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, (size_t)tracks * cap * sizeof(float)));
         GAB_HIP_CHECK(hipMemset(p->pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
         *out = p.release();
@@ -359,31 +344,17 @@ int gab_delay_create(gab_delay_plan** out, int tracks, int bufsize, int max_dela
     });
 }
 
-int gab_delay_destroy(gab_delay_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_delay_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_delay_destroy(gab_delay_plan* plan) { return gab::destroy_plan(plan, "gab_delay_destroy: null pointer"); }
 
 int gab_delay_set_params(gab_delay_plan* plan, const float* d_params, int ramp, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_delay_set_params: null pointer");
-        return gab::delay_set_range(plan, d_params, 0, plan->tracks, ramp, gab::as_stream(stream),
-                                    "gab_delay_set_params");
-    });
+    return gab::set_entry("gab_delay_set_params", gab::delay_set_range, plan, d_params, true, 0, 0, ramp,
+                          gab::as_stream(stream));
 }
 
 int gab_delay_set_params_tracks(gab_delay_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
                                 gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_delay_set_params_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_delay_set_params_tracks: the track range is outside the plan");
-        return gab::delay_set_range(plan, d_params, first_track, n_tracks, ramp, gab::as_stream(stream),
-                                    "gab_delay_set_params_tracks");
-    });
+    return gab::set_entry("gab_delay_set_params_tracks", gab::delay_set_range, plan, d_params, false, first_track, n_tracks,
+                          ramp, gab::as_stream(stream));
 }
 
 int gab_delay_reset(gab_delay_plan* plan, gab_stream_t stream) {
@@ -415,9 +386,7 @@ int gab_delay_process_batch(gab_delay_plan* plan, const float* d_in, float* d_ou
 int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_delay_params: null pointer");
-        *d_current = plan->params.current.get();
-        *d_target = plan->params.target.get();
-        *n_floats = plan->params.current.size();
+        plan->params.expose(d_current, d_target, n_floats);
         return GAB_OK;
     });
 }

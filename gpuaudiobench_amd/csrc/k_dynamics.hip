@@ -14,7 +14,8 @@
 //                               The block is read once and written once; nothing leaves the wave, so there is no
 //                               workgroup barrier.  A link group is at most 64 tracks and tracks % link == 0, so a
 //                               group never straddles two waves.
-//   dyn_check_kernel            refuses a parameter row outside the contract, naming the first.
+//   DynRule                     refuses a parameter row outside the contract, naming the first (gab_plan.hpp's check
+//                               kernel).
 //
 // log2 and exp2 are the two pinned polynomials below (tools/dyn_poly.py fits and measures them); no library
 // transcendental is called.  The sequence of roundings per sample is the header's; the cut decides only where a value
@@ -334,22 +335,32 @@ __global__ __launch_bounds__(64) void dyn_kernel(const float* in, const float* k
     if (owner) smooth[track] = w.s;
 }
 
-// src: [n_rows][8].  The smallest index of a value the contract refuses (a NaN fails every comparison).
-__global__ __launch_bounds__(256) void dyn_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag,
-                                                       size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = src[i];
-    const int field = (int)(i & 7);
-    bool bad = not_finite(__float_as_uint(v));
-    if (field == 0) bad = bad || !(fabsf(v) <= 128.0f);
-    if (field == 1) bad = bad || !(v >= -1.0f && v <= 0.0f);
-    if (field == 2) bad = bad || !(v >= 0.0f && v <= 64.0f);
-    if (field == 3) bad = bad || !(v >= 0.0f);
-    if (field == 4 || field == 5) bad = bad || !(v >= 0.0f && v <= 0x1.ffffep-1f);   // 1 - 2^-20
-    if (field == 7) bad = bad || !(v <= 0.0f);
-    if (bad) atomicMin(flag, (unsigned)i);
-}
+const char* const kDynFields[GAB_DYN_FIELDS] = {"thr", "slope", "knee", "kq", "att", "rel", "makeup", "range"};
+const char* const kDynRules[GAB_DYN_FIELDS] = {
+    "must be finite and within [-128, 128]", "must be within [-1, 0]", "must be within [0, 64]",
+    "must be finite and >= 0", "must be within [0, 1 - 2^-20]", "must be within [0, 1 - 2^-20]", "must be finite",
+    "must be finite and <= 0"};
+
+// src: [n_rows][8] (a NaN fails every comparison)
+struct DynRule {
+    __device__ bool refuses(const float* src, size_t i) const {
+        const float v = src[i];
+        const int field = (int)(i & 7);
+        bool bad = not_finite(__float_as_uint(v));
+        if (field == 0) bad = bad || !(fabsf(v) <= 128.0f);
+        if (field == 1) bad = bad || !(v >= -1.0f && v <= 0.0f);
+        if (field == 2) bad = bad || !(v >= 0.0f && v <= 64.0f);
+        if (field == 3) bad = bad || !(v >= 0.0f);
+        if (field == 4 || field == 5) bad = bad || !(v >= 0.0f && v <= 0x1.ffffep-1f);   // 1 - 2^-20
+        if (field == 7) bad = bad || !(v <= 0.0f);
+        return bad;
+    }
+    std::string refusal(unsigned i, int first_track) const {
+        const int field = (int)(i % GAB_DYN_FIELDS);
+        return "track " + std::to_string(first_track + (int)(i / GAB_DYN_FIELDS)) + " field " + std::to_string(field) +
+               " (" + kDynFields[field] + ") " + kDynRules[field] + "; the plan keeps its parameters";
+    }
+};
 
 }  // namespace
 }  // namespace gab
@@ -363,12 +374,6 @@ struct gab_dyn_plan {
 
 namespace gab {
 namespace {
-
-const char* const kDynFields[GAB_DYN_FIELDS] = {"thr", "slope", "knee", "kq", "att", "rel", "makeup", "range"};
-const char* const kDynRules[GAB_DYN_FIELDS] = {
-    "must be finite and within [-128, 128]", "must be within [-1, 0]", "must be within [0, 64]",
-    "must be finite and >= 0", "must be within [0, 1 - 2^-20]", "must be within [0, 1 - 2^-20]", "must be finite",
-    "must be finite and <= 0"};
 
 bool dyn_overlap(const float* a, const float* b, size_t n) {
     const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
@@ -406,24 +411,11 @@ int dyn_process(gab_dyn_plan* p, const float* d_in, const float* d_key, float* d
 }
 
 // check, then commit (gab_plan.hpp): a refused set leaves both tables and a pending ramp as they were.
-int dyn_set_range(gab_dyn_plan* p, const float* d_params, int first_track, int n_tracks, int ramp, hipStream_t s,
-                  const char* who) {
+int dyn_set_range(gab_dyn_plan* p, const float* d_params, int first_track, int n_tracks, const char* who, int ramp,
+                  hipStream_t s) {
     const size_t n = (size_t)n_tracks * GAB_DYN_FIELDS;
-    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = kNoneRefused;
-    if (int rc = first_refused(p->flag, s, "dyn_check_kernel", [&] {
-            dyn_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_params, p->flag.get(), n);
-        }, &first_bad))
-        return rc;
-    if (first_bad != kNoneRefused) {
-        const int field = (int)(first_bad % GAB_DYN_FIELDS);
-        set_last_error(std::string(who) + ": track " + std::to_string(first_track + (int)(first_bad / GAB_DYN_FIELDS)) +
-                       " field " + std::to_string(field) + " (" + kDynFields[field] + ") " + kDynRules[field] +
-                       "; the plan keeps its parameters");
-        return GAB_ERR_INVALID_ARG;
-    }
-    p->params.commit(d_params, (size_t)first_track * GAB_DYN_FIELDS, n, ramp != 0, s);
-    return GAB_OK;
+    return check_then(p->flag, s, who, d_params, n, DynRule{}, first_track,
+                      [&] { p->params.commit(d_params, (size_t)first_track * GAB_DYN_FIELDS, n, ramp != 0, s); });
 }
 
 }  // namespace
@@ -442,48 +434,27 @@ int gab_dyn_create(gab_dyn_plan** out, int tracks, int bufsize, int link) {
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_dyn_create")) return rc;
         auto p = std::make_unique<gab_dyn_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->link = link;
-        const size_t n = (size_t)tracks * GAB_DYN_FIELDS;
-        p->params.create(n, bufsize);
+        p->params.create((size_t)tracks * GAB_DYN_FIELDS, bufsize);
         p->smooth.alloc((size_t)tracks);
         p->flag.alloc(1);
         // pass-through: {0, 0, 0, 0, 0, 0, 1, -256} on every track, a smoothed gain of 0
-        std::vector<float> init(n, 0.0f);
-        for (int t = 0; t < tracks; ++t) {
-            init[(size_t)t * GAB_DYN_FIELDS + 6] = 1.0f;
-            init[(size_t)t * GAB_DYN_FIELDS + 7] = -256.0f;
-        }
-        GAB_HIP_CHECK(hipMemcpy(p->params.current.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemcpy(p->params.target.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        p->params.fill({0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, -256.0f}, tracks);
         GAB_HIP_CHECK(hipMemset(p->smooth.get(), 0, (size_t)tracks * sizeof(float)));
         *out = p.release();
         return GAB_OK;
     });
 }
 
-int gab_dyn_destroy(gab_dyn_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_dyn_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_dyn_destroy(gab_dyn_plan* plan) { return gab::destroy_plan(plan, "gab_dyn_destroy: null pointer"); }
 
 int gab_dyn_set_params(gab_dyn_plan* plan, const float* d_params, int ramp, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_dyn_set_params: null pointer");
-        return gab::dyn_set_range(plan, d_params, 0, plan->tracks, ramp, gab::as_stream(stream), "gab_dyn_set_params");
-    });
+    return gab::set_entry("gab_dyn_set_params", gab::dyn_set_range, plan, d_params, true, 0, 0, ramp, gab::as_stream(stream));
 }
 
 int gab_dyn_set_params_tracks(gab_dyn_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
                               gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_dyn_set_params_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_dyn_set_params_tracks: the track range is outside the plan");
-        return gab::dyn_set_range(plan, d_params, first_track, n_tracks, ramp, gab::as_stream(stream),
-                                  "gab_dyn_set_params_tracks");
-    });
+    return gab::set_entry("gab_dyn_set_params_tracks", gab::dyn_set_range, plan, d_params, false, first_track, n_tracks, ramp,
+                          gab::as_stream(stream));
 }
 
 int gab_dyn_reset(gab_dyn_plan* plan, gab_stream_t stream) {
@@ -517,9 +488,7 @@ int gab_dyn_process_batch(gab_dyn_plan* plan, const float* d_in, const float* d_
 int gab_dyn_params(gab_dyn_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_dyn_params: null pointer");
-        *d_current = plan->params.current.get();
-        *d_target = plan->params.target.get();
-        *n_floats = plan->params.current.size();
+        plan->params.expose(d_current, d_target, n_floats);
         return GAB_OK;
     });
 }

@@ -363,7 +363,7 @@ bool eq_aligned(const void* a, const void* b) {
 }
 
 // check, then commit (gab_plan.hpp): a refused set leaves the table as it was.  src null: the identity filter.
-int eq_set_range(gab_eq_plan* p, const float* d_coeffs, int first_track, int n_tracks, hipStream_t s, const char* who) {
+int eq_set_range(gab_eq_plan* p, const float* d_coeffs, int first_track, int n_tracks, const char* who, hipStream_t s) {
     const int S = p->sections;
     const long long n = (long long)n_tracks * S;
     auto launch = [&](int commit) {
@@ -407,34 +407,21 @@ int gab_eq_create(gab_eq_plan** out, int tracks, int bufsize, int sections) {
         p->state.alloc(n * 2);
         p->flag.alloc(1);
         GAB_HIP_CHECK(hipMemset(p->state.get(), 0, n * 2 * sizeof(float)));
-        if (int rc = gab::eq_set_range(p.get(), nullptr, 0, tracks, nullptr, "gab_eq_create")) return rc;   // identity
+        if (int rc = gab::eq_set_range(p.get(), nullptr, 0, tracks, "gab_eq_create", nullptr)) return rc;   // identity
         *out = p.release();
         return GAB_OK;
     });
 }
 
-int gab_eq_destroy(gab_eq_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_eq_destroy: null plan");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_eq_destroy(gab_eq_plan* plan) { return gab::destroy_plan(plan, "gab_eq_destroy: null plan"); }
 
 int gab_eq_set_coeffs_tracks(gab_eq_plan* plan, const float* d_coeffs, int first_track, int n_tracks, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_coeffs) return gab::bad_arg("gab_eq_set_coeffs_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_eq_set_coeffs_tracks: the track range is outside the plan");
-        return gab::eq_set_range(plan, d_coeffs, first_track, n_tracks, gab::as_stream(stream), "gab_eq_set_coeffs_tracks");
-    });
+    return gab::set_entry("gab_eq_set_coeffs_tracks", gab::eq_set_range, plan, d_coeffs, false, first_track, n_tracks,
+                          gab::as_stream(stream));
 }
 
 int gab_eq_set_coeffs(gab_eq_plan* plan, const float* d_coeffs, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_coeffs) return gab::bad_arg("gab_eq_set_coeffs: null pointer");
-        return gab::eq_set_range(plan, d_coeffs, 0, plan->tracks, gab::as_stream(stream), "gab_eq_set_coeffs");
-    });
+    return gab::set_entry("gab_eq_set_coeffs", gab::eq_set_range, plan, d_coeffs, true, 0, 0, gab::as_stream(stream));
 }
 
 int gab_eq_reset(gab_eq_plan* plan, gab_stream_t stream) {

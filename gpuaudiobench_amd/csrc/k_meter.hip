@@ -9,7 +9,7 @@
 //                         rows in turn, a lane per sample, for peak, true peak, the sum of squares and the non-finite
 //                         flag.  A row of the tile carries the track's last 11 samples in front of the chunk, so the
 //                         true-peak taps read one contiguous run.  Buffers of a batch are more chunks of the same loop.
-//   meter_check_kernel    refuses a weighting outside the contract, naming the first value.
+//   MeterRule             refuses a weighting outside the contract, naming the first value (gab_plan.hpp's check kernel).
 //
 // The K filter has no scan form: eq_scan_kernel's wave scan, restated for the two K sections, missed the bound the issue
 // set per track and buffer at every buffer size (profiles/r11_meter.txt), so the ordered form runs at
@@ -216,25 +216,32 @@ __global__ __launch_bounds__(256) void meter_kernel(const float* __restrict__ in
     }
 }
 
-// src: [2][5].  The smallest index of a value the contract refuses: a value that is not finite; a2 with |a2| >= 1; a1
-// with |a1| >= 1 + a2 (asked only of a finite a2, which then is the value named).
-__global__ __launch_bounds__(64) void meter_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag) {
-    const int i = threadIdx.x;
-    if (i >= 10) return;
-    const int sec = i / 5, field = i % 5;
-    const float v = src[i];
-    bool bad = not_finite(__float_as_uint(v));
-    const float a2f = src[sec * 5 + 4];
-    const double a1 = src[sec * 5 + 3], a2 = a2f;
-    if (field == 4) bad = bad || !(fabs(a2) < 1.0);
-    if (field == 3 && !not_finite(__float_as_uint(a2f))) bad = bad || !(fabs(a1) < 1.0 + a2);
-    if (bad) atomicMin(flag, (unsigned)i);
-}
+const char* const kMeterCoeff[5] = {"b0", "b1", "b2", "a1", "a2"};
+
+// src: [2][5].  Refused: a value that is not finite; a2 with |a2| >= 1; a1 with |a1| >= 1 + a2 (asked only of a finite
+// a2, which then is the value named).
+struct MeterRule {
+    __device__ bool refuses(const float* src, size_t i) const {
+        const int sec = (int)(i / 5), field = (int)(i % 5);
+        const float v = src[i];
+        bool bad = not_finite(__float_as_uint(v));
+        const float a2f = src[sec * 5 + 4];
+        const double a1 = src[sec * 5 + 3], a2 = a2f;
+        if (field == 4) bad = bad || !(fabs(a2) < 1.0);
+        if (field == 3 && !not_finite(__float_as_uint(a2f))) bad = bad || !(fabs(a1) < 1.0 + a2);
+        return bad;
+    }
+    std::string refusal(unsigned i, int) const {
+        const int field = (int)(i % 5u);
+        return "section " + std::to_string((int)(i / 5u)) + " value " + std::to_string(field) + " (" + kMeterCoeff[field] +
+               ") is not finite or outside the stability triangle (needs |a2| < 1 and |a1| < 1 + a2)"
+               "; the plan keeps its weighting";
+    }
+};
 
 // ITU-R BS.1770's K weighting at 48 kHz
 const float kMeterDefault[10] = {1.53512485958697f, -2.69169618940638f, 1.19839281085285f, -1.69065929318241f,
                                  0.73248077421585f, 1.0f, -2.0f, 1.0f, -1.99004745483398f, 0.99007225036621f};
-const char* const kMeterCoeff[5] = {"b0", "b1", "b2", "a1", "a2"};
 
 }  // namespace
 }  // namespace gab
@@ -264,14 +271,6 @@ int meter_launch(gab_meter_plan* p, const float* d_in, float* d_rows, int n_buff
     if (vec) GAB_METER(true); else GAB_METER(false);
 #undef GAB_METER
     return launch_status("meter_kernel");
-}
-
-// ten checked coefficients on the device into the plan's constants; synchronises
-int meter_commit(gab_meter_plan* p, const float* d_sections, hipStream_t s) {
-    GAB_HIP_CHECK(hipMemcpyAsync(p->consts.get() + kMeterTapWords, d_sections, 10 * sizeof(float),
-                                 hipMemcpyDeviceToDevice, s));
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
-    return GAB_OK;
 }
 
 void meter_clear(gab_meter_plan* p, hipStream_t s) {
@@ -327,33 +326,18 @@ int gab_meter_create(gab_meter_plan** out, int tracks, int bufsize, int window) 
     });
 }
 
-int gab_meter_destroy(gab_meter_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_meter_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_meter_destroy(gab_meter_plan* plan) { return gab::destroy_plan(plan, "gab_meter_destroy: null pointer"); }
 
 // check, then commit (gab_plan.hpp): a refused set leaves the rows as they were
 int gab_meter_set_weighting(gab_meter_plan* plan, const float* d_sections, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_sections) return gab::bad_arg("gab_meter_set_weighting: null pointer");
         hipStream_t s = gab::as_stream(stream);
-        unsigned first_bad = gab::kNoneRefused;
-        if (int rc = gab::first_refused(plan->flag, s, "meter_check_kernel", [&] {
-                gab::meter_check_kernel<<<1, 64, 0, s>>>(d_sections, plan->flag.get());
-            }, &first_bad))
-            return rc;
-        if (first_bad != gab::kNoneRefused) {
-            const int field = (int)(first_bad % 5u);
-            gab::set_last_error("gab_meter_set_weighting: section " + std::to_string((int)(first_bad / 5u)) + " value " +
-                                std::to_string(field) + " (" + gab::kMeterCoeff[field] +
-                                ") is not finite or outside the stability triangle (needs |a2| < 1 and |a1| < 1 + a2)"
-                                "; the plan keeps its weighting");
-            return GAB_ERR_INVALID_ARG;
-        }
-        return gab::meter_commit(plan, d_sections, s);
+        return gab::check_then(plan->flag, s, "gab_meter_set_weighting", d_sections, 10, gab::MeterRule{}, 0, [&] {
+            GAB_HIP_CHECK(hipMemcpyAsync(plan->consts.get() + gab::kMeterTapWords, d_sections, 10 * sizeof(float),
+                                         hipMemcpyDeviceToDevice, s));
+            GAB_HIP_CHECK(hipStreamSynchronize(s));
+        });
     });
 }
 

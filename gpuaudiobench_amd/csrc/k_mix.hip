@@ -8,7 +8,7 @@
 //                           through a 256-track x 64-sample LDS tile first, then the same chains.
 //   mix_groups_kernel       the final pass: the groups' partial sums, fetched side by side, added in ascending order (not launched when the
 //                           plan has one group: the workgroup's sums are the outputs).
-//   mix_check_kernel        refuses a gain that is not finite, naming the first.
+//   MixRule                 refuses a gain that is not finite, naming the first (gab_plan.hpp's check kernel).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -239,12 +239,15 @@ __global__ __launch_bounds__(1024) void mix_groups_kernel(const float* __restric
     if (w == 0 && valid) out[e] = sum;
 }
 
-__global__ __launch_bounds__(256) void mix_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag,
-                                                       size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (not_finite(__float_as_uint(src[i]))) atomicMin(flag, (unsigned)i);
-}
+// src: [n_rows][buses]
+struct MixRule {
+    unsigned buses;                 // for the text only
+    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
+    std::string refusal(unsigned i, int first_track) const {
+        return "the gain of track " + std::to_string(first_track + (int)(i / buses)) + " bus " +
+               std::to_string((int)(i % buses)) + " is not finite; the plan keeps its gains";
+    }
+};
 
 }  // namespace
 }  // namespace gab
@@ -347,24 +350,11 @@ int mix_process(gab_mix_plan* p, const float* d_in, float* d_out, int n_buffers,
 }
 
 // check, then commit (gab_plan.hpp): a refused set leaves both matrices and a pending ramp as they were.
-int mix_set_range(gab_mix_plan* p, const float* d_gains, int first_track, int n_tracks, int ramp, hipStream_t s,
-                  const char* who) {
-    const int M = p->buses;
-    const size_t n = (size_t)n_tracks * M;
-    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = kNoneRefused;
-    if (int rc = first_refused(p->flag, s, "mix_check_kernel", [&] {
-            mix_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_gains, p->flag.get(), n);
-        }, &first_bad))
-        return rc;
-    if (first_bad != kNoneRefused) {
-        set_last_error(std::string(who) + ": the gain of track " + std::to_string(first_track + (int)(first_bad / (unsigned)M)) +
-                       " bus " + std::to_string((int)(first_bad % (unsigned)M)) +
-                       " is not finite; the plan keeps its gains");
-        return GAB_ERR_INVALID_ARG;
-    }
-    p->gains.commit(d_gains, (size_t)first_track * M, n, ramp != 0, s);
-    return GAB_OK;
+int mix_set_range(gab_mix_plan* p, const float* d_gains, int first_track, int n_tracks, const char* who, int ramp,
+                  hipStream_t s) {
+    const size_t M = (size_t)p->buses, n = (size_t)n_tracks * M;
+    return check_then(p->flag, s, who, d_gains, n, MixRule{(unsigned)M}, first_track,
+                      [&] { p->gains.commit(d_gains, (size_t)first_track * M, n, ramp != 0, s); });
 }
 
 }  // namespace
@@ -386,8 +376,7 @@ int gab_mix_create(gab_mix_plan** out, int tracks, int bufsize, int buses) {
         p->tracks = tracks; p->bufsize = bufsize; p->buses = buses;
         gab::mix_pick_form(bufsize, buses, &p->leaf_tracks, &p->group_leaves);
         p->n_groups = (int)n_groups;
-        const size_t n = (size_t)tracks * buses;
-        p->gains.create(n, bufsize);
+        p->gains.create((size_t)tracks * buses, bufsize);
         p->flag.alloc(1);
         // The workspace of the final pass: as many buffers' partial sums as fit 32 MiB, at least one and at most
         // kMixBatchChunk.  A longer batch is that many buffers per launch, one launch after the other.
@@ -396,37 +385,22 @@ int gab_mix_create(gab_mix_plan** out, int tracks, int bufsize, int buses) {
         chunk = chunk < 1 ? 1 : (chunk > (size_t)gab::kMixBatchChunk ? (size_t)gab::kMixBatchChunk : chunk);
         p->part_buffers = p->n_groups > 1 ? (int)chunk : gab::kMixBatchChunk;
         if (p->n_groups > 1) p->part.alloc(chunk * per_buffer / sizeof(float));
-        GAB_HIP_CHECK(hipMemset(p->gains.current.get(), 0, n * sizeof(float)));
-        GAB_HIP_CHECK(hipMemset(p->gains.target.get(), 0, n * sizeof(float)));
+        p->gains.fill(std::vector<float>((size_t)buses, 0.0f), tracks);      // silence
         *out = p.release();
         return GAB_OK;
     });
 }
 
-int gab_mix_destroy(gab_mix_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_mix_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_mix_destroy(gab_mix_plan* plan) { return gab::destroy_plan(plan, "gab_mix_destroy: null pointer"); }
 
 int gab_mix_set_gains(gab_mix_plan* plan, const float* d_gains, int ramp, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_gains) return gab::bad_arg("gab_mix_set_gains: null pointer");
-        return gab::mix_set_range(plan, d_gains, 0, plan->tracks, ramp, gab::as_stream(stream), "gab_mix_set_gains");
-    });
+    return gab::set_entry("gab_mix_set_gains", gab::mix_set_range, plan, d_gains, true, 0, 0, ramp, gab::as_stream(stream));
 }
 
 int gab_mix_set_gains_tracks(gab_mix_plan* plan, const float* d_gains, int first_track, int n_tracks, int ramp,
                              gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_gains) return gab::bad_arg("gab_mix_set_gains_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_mix_set_gains_tracks: the track range is outside the plan");
-        return gab::mix_set_range(plan, d_gains, first_track, n_tracks, ramp, gab::as_stream(stream),
-                                  "gab_mix_set_gains_tracks");
-    });
+    return gab::set_entry("gab_mix_set_gains_tracks", gab::mix_set_range, plan, d_gains, false, first_track, n_tracks, ramp,
+                          gab::as_stream(stream));
 }
 
 int gab_mix_reset(gab_mix_plan* plan, gab_stream_t stream) {
@@ -460,9 +434,7 @@ int gab_mix_process_batch(gab_mix_plan* plan, const float* d_in, float* d_out, i
 int gab_mix_gains(gab_mix_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_mix_gains: null pointer");
-        *d_current = plan->gains.current.get();
-        *d_target = plan->gains.target.get();
-        *n_floats = plan->gains.current.size();
+        plan->gains.expose(d_current, d_target, n_floats);
         return GAB_OK;
     });
 }

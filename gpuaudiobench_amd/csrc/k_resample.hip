@@ -10,7 +10,8 @@
 //                          K samples come from the lane's own tile row, two to an 8-byte LDS read.  All four waves walk
 //                          the positions (scalar arithmetic); wave w computes every fourth output.  Outputs are turned
 //                          through a second tile, 64 at a time, so that a row is stored 64 consecutive floats at once.
-//   resample_check_kernel  refuses a tap table with a value that is not finite, naming the first.
+//   ResampleRule           refuses a tap table with a value that is not finite, naming the first (gab_plan.hpp's check
+//                          kernel).
 //
 // The position of the next output, (i - first sample of the chunk, p), is carried in 32-bit integers by adding
 // (M / L, M mod L) with a carry: no division on the device.  The host passes the position of the launch's first output;
@@ -151,12 +152,15 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
         for (int c = lane; c < H; c += 64) hist[(size_t)(t0 + r) * H + c] = tile[r * pitch + 1 + c];
 }
 
-// src: [n].  The smallest index of a value that is not finite.
-__global__ __launch_bounds__(256) void resample_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag,
-                                                            int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n && not_finite(__float_as_uint(src[i]))) atomicMin(flag, (unsigned)i);
-}
+// src: [phases][taps]
+struct ResampleRule {
+    unsigned taps;                  // for the text only
+    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
+    std::string refusal(unsigned i, int) const {
+        return "phase " + std::to_string(i / taps) + " tap " + std::to_string(i % taps) +
+               " is not finite; the plan keeps its taps";
+    }
+};
 
 int gcd_int(int a, int b) {
     while (b) { const int t = a % b; a = b; b = t; }
@@ -272,11 +276,7 @@ int gab_resample_create(gab_resample_plan** out, int tracks, int bufsize, int up
 }
 
 int gab_resample_destroy(gab_resample_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_resample_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
+    return gab::destroy_plan(plan, "gab_resample_destroy: null pointer");
 }
 
 int gab_resample_shape(gab_resample_plan* plan, int* up, int* down, int* taps, int* out_capacity, int* period) {
@@ -293,21 +293,12 @@ int gab_resample_set_taps(gab_resample_plan* plan, const float* d_taps, gab_stre
     return gab::guarded([&]() -> int {
         if (!plan || !d_taps) return gab::bad_arg("gab_resample_set_taps: null pointer");
         hipStream_t s = gab::as_stream(stream);
-        const int n = plan->L * plan->K;
-        unsigned first_bad = gab::kNoneRefused;
-        if (int rc = gab::first_refused(plan->flag, s, "resample_check_kernel", [&] {
-                gab::resample_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_taps, plan->flag.get(), n);
-            }, &first_bad))
-            return rc;
-        if (first_bad != gab::kNoneRefused) {
-            gab::set_last_error("gab_resample_set_taps: phase " + std::to_string(first_bad / (unsigned)plan->K) +
-                                " tap " + std::to_string(first_bad % (unsigned)plan->K) +
-                                " is not finite; the plan keeps its taps");
-            return GAB_ERR_INVALID_ARG;
-        }
-        GAB_HIP_CHECK(hipMemcpyAsync(plan->taps.get(), d_taps, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        GAB_HIP_CHECK(hipStreamSynchronize(s));
-        return GAB_OK;
+        const size_t n = (size_t)plan->L * plan->K;
+        const gab::ResampleRule rule{(unsigned)plan->K};
+        return gab::check_then(plan->flag, s, "gab_resample_set_taps", d_taps, n, rule, 0, [&] {
+            GAB_HIP_CHECK(hipMemcpyAsync(plan->taps.get(), d_taps, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            GAB_HIP_CHECK(hipStreamSynchronize(s));
+        });
     });
 }
 

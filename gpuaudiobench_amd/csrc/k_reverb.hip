@@ -13,7 +13,8 @@
 //                                 3. lanes along time, per owned track: the N values of a column, the butterflies in
 //                                    registers, N coalesced line stores, the outputs' ordered sums and their stores.
 //                               Only step 2 is serial in time.  Nothing leaves the wave: no workgroup barrier.
-//   reverb_check_kernel         refuses a parameter row outside the contract, naming the first value.
+//   ReverbRule, ReverbDelayRule refuse a parameter row, a delay, outside the contract, naming the first value
+//                               (gab_plan.hpp's check kernel).
 //   reverb_check_delays_kernel  the same for a set of delays.
 //
 // The sequence of roundings per sample is the header's; the cut decides only where a value is held, so every launch
@@ -255,27 +256,41 @@ __global__ __launch_bounds__(kRevChains) void reverb_kernel(const float* in, flo
     }
 }
 
-// src: [n_rows][row].  The smallest index of a value the contract refuses.
-__global__ __launch_bounds__(256) void reverb_check_kernel(const float* __restrict__ src, unsigned* __restrict__ flag,
-                                                          size_t n, int row, int lines, float gmax) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = src[i];
-    const int field = (int)(i % (size_t)row);
-    bool bad = not_finite(__float_as_uint(v));
-    if (field < lines) bad = bad || !(fabsf(v) <= gmax);
-    else if (field < 2 * lines) bad = bad || !(v >= 0.0f && v <= 0x1.ffffep-1f);
-    if (bad) atomicMin(flag, (unsigned)i);
-}
+// src: [n_rows][row]
+struct ReverbRule {
+    int row, lines;
+    float gmax;
+    __device__ bool refuses(const float* src, size_t i) const {
+        const float v = src[i];
+        const int field = (int)(i % (size_t)row);
+        bool bad = not_finite(__float_as_uint(v));
+        if (field < lines) bad = bad || !(fabsf(v) <= gmax);
+        else if (field < 2 * lines) bad = bad || !(v >= 0.0f && v <= 0x1.ffffep-1f);
+        return bad;
+    }
+    std::string refusal(unsigned i, int first_track) const {
+        const int field = (int)(i % (unsigned)row), N = lines;
+        const char* name = field < N ? "g" : (field < 2 * N ? "damp" : (field < 3 * N ? "b" : (field < row - 1 ? "c" : "dry")));
+        const char* rule = field < N ? "must be finite and at most gab_reverb_gmax(lines) in magnitude"
+                                     : (field < 2 * N ? "must be within [0, 1 - 2^-20]" : "must be finite");
+        return "track " + std::to_string(first_track + (int)(i / (unsigned)row)) + " field " + std::to_string(field) +
+               " (" + name + ") " + rule + "; the plan keeps its parameters";
+    }
+};
 
-__global__ __launch_bounds__(256) void reverb_check_delays_kernel(const int* __restrict__ src,
-                                                                 unsigned* __restrict__ flag, size_t n, int lo,
-                                                                 int hi) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int v = src[i];
-    if (v < lo || v > hi) atomicMin(flag, (unsigned)i);
-}
+// src: [n_rows][lines]
+struct ReverbDelayRule {
+    int lo, hi;
+    unsigned lines;                 // for the text only
+    __device__ bool refuses(const int* src, size_t i) const {
+        const int v = src[i];
+        return v < lo || v > hi;
+    }
+    std::string refusal(unsigned i, int first_track) const {
+        return "track " + std::to_string(first_track + (int)(i / lines)) + " line " + std::to_string((int)(i % lines)) +
+               " must be within [GAB_REVERB_MIN_DELAY, max_delay]; the plan keeps its delays";
+    }
+};
 
 }  // namespace
 }  // namespace gab
@@ -329,49 +344,22 @@ int reverb_process(gab_reverb_plan* p, const float* d_in, float* d_out, int n_bu
 }
 
 // check, then commit (gab_plan.hpp): a refused set leaves both tables and a pending ramp as they were.
-int reverb_set_range(gab_reverb_plan* p, const float* d_params, int first_track, int n_tracks, int ramp, hipStream_t s,
-                     const char* who) {
-    const size_t n = (size_t)n_tracks * (size_t)p->row;
-    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = kNoneRefused;
-    if (int rc = first_refused(p->flag, s, "reverb_check_kernel", [&] {
-            reverb_check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_params, p->flag.get(), n, p->row,
-                                                                                  p->lines, reverb_gmax(p->lines));
-        }, &first_bad))
-        return rc;
-    if (first_bad != kNoneRefused) {
-        const int field = (int)(first_bad % (unsigned)p->row), N = p->lines;
-        const char* name = field < N ? "g" : (field < 2 * N ? "damp" : (field < 3 * N ? "b" : (field < p->row - 1 ? "c" : "dry")));
-        const char* rule = field < N ? "must be finite and at most gab_reverb_gmax(lines) in magnitude"
-                                     : (field < 2 * N ? "must be within [0, 1 - 2^-20]" : "must be finite");
-        set_last_error(std::string(who) + ": track " + std::to_string(first_track + (int)(first_bad / (unsigned)p->row)) +
-                       " field " + std::to_string(field) + " (" + name + ") " + rule + "; the plan keeps its parameters");
-        return GAB_ERR_INVALID_ARG;
-    }
-    p->params.commit(d_params, (size_t)first_track * (size_t)p->row, n, ramp != 0, s);
-    return GAB_OK;
+int reverb_set_range(gab_reverb_plan* p, const float* d_params, int first_track, int n_tracks, const char* who, int ramp,
+                     hipStream_t s) {
+    const size_t row = (size_t)p->row, n = (size_t)n_tracks * row;
+    return check_then(p->flag, s, who, d_params, n, ReverbRule{p->row, p->lines, reverb_gmax(p->lines)}, first_track,
+                      [&] { p->params.commit(d_params, (size_t)first_track * row, n, ramp != 0, s); });
 }
 
-int reverb_set_delay_range(gab_reverb_plan* p, const int* d_delays, int first_track, int n_tracks, hipStream_t s,
-                           const char* who) {
-    const size_t n = (size_t)n_tracks * (size_t)p->lines;
-    if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
-    unsigned first_bad = kNoneRefused;
-    if (int rc = first_refused(p->flag, s, "reverb_check_delays_kernel", [&] {
-            reverb_check_delays_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(
-                d_delays, p->flag.get(), n, GAB_REVERB_MIN_DELAY, p->max_delay);
-        }, &first_bad))
-        return rc;
-    if (first_bad != kNoneRefused) {
-        set_last_error(std::string(who) + ": track " + std::to_string(first_track + (int)(first_bad / (unsigned)p->lines)) +
-                       " line " + std::to_string((int)(first_bad % (unsigned)p->lines)) +
-                       " must be within [GAB_REVERB_MIN_DELAY, max_delay]; the plan keeps its delays");
-        return GAB_ERR_INVALID_ARG;
-    }
-    GAB_HIP_CHECK(hipMemcpyAsync(p->delays.get() + (size_t)first_track * (size_t)p->lines, d_delays, n * sizeof(int),
-                                 hipMemcpyDeviceToDevice, s));
-    GAB_HIP_CHECK(hipStreamSynchronize(s));
-    return GAB_OK;
+int reverb_set_delay_range(gab_reverb_plan* p, const int* d_delays, int first_track, int n_tracks, const char* who,
+                           hipStream_t s) {
+    const size_t N = (size_t)p->lines, n = (size_t)n_tracks * N;
+    return check_then(p->flag, s, who, d_delays, n, ReverbDelayRule{GAB_REVERB_MIN_DELAY, p->max_delay, (unsigned)N},
+                      first_track, [&] {
+        GAB_HIP_CHECK(hipMemcpyAsync(p->delays.get() + (size_t)first_track * N, d_delays, n * sizeof(int),
+                                     hipMemcpyDeviceToDevice, s));
+        GAB_HIP_CHECK(hipStreamSynchronize(s));
+    });
 }
 
 }  // namespace
@@ -401,19 +389,18 @@ int gab_reverb_create(gab_reverb_plan** out, int tracks, int bufsize, int lines,
         auto p = std::make_unique<gab_reverb_plan>();
         p->tracks = tracks; p->bufsize = bufsize; p->lines = lines; p->outs = outs; p->max_delay = max_delay;
         p->row = lines * (3 + outs) + 1; p->capacity = cap;
-        const size_t n = (size_t)tracks * (size_t)p->row, chains = (size_t)tracks * (size_t)lines;
-        p->params.create(n, bufsize);
+        const size_t chains = (size_t)tracks * (size_t)lines;
+        p->params.create((size_t)tracks * (size_t)p->row, bufsize);
         p->ring.alloc(chains * cap);
         p->pos.alloc((size_t)tracks);
         p->q.alloc(chains);
         p->delays.alloc(chains);
         p->flag.alloc(1);
         // pass-through: dry = 1, everything else 0, every delay max_delay, empty lines
-        std::vector<float> init(n, 0.0f);
-        for (int t = 0; t < tracks; ++t) init[(size_t)t * p->row + p->row - 1] = 1.0f;
+        std::vector<float> init((size_t)p->row, 0.0f);
+        init.back() = 1.0f;
+        p->params.fill(init, tracks);
         const std::vector<int> m(chains, max_delay);
-        GAB_HIP_CHECK(hipMemcpy(p->params.current.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemcpy(p->params.target.get(), init.data(), n * sizeof(float), hipMemcpyHostToDevice));
         GAB_HIP_CHECK(hipMemcpy(p->delays.get(), m.data(), chains * sizeof(int), hipMemcpyHostToDevice));
         GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, chains * cap * sizeof(float)));
         GAB_HIP_CHECK(hipMemset(p->pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
@@ -423,50 +410,28 @@ int gab_reverb_create(gab_reverb_plan** out, int tracks, int bufsize, int lines,
     });
 }
 
-int gab_reverb_destroy(gab_reverb_plan* plan) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_reverb_destroy: null pointer");
-        delete plan;
-        return GAB_OK;
-    });
-}
+int gab_reverb_destroy(gab_reverb_plan* plan) { return gab::destroy_plan(plan, "gab_reverb_destroy: null pointer"); }
 
 int gab_reverb_set_params(gab_reverb_plan* plan, const float* d_params, int ramp, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_reverb_set_params: null pointer");
-        return gab::reverb_set_range(plan, d_params, 0, plan->tracks, ramp, gab::as_stream(stream),
-                                     "gab_reverb_set_params");
-    });
+    return gab::set_entry("gab_reverb_set_params", gab::reverb_set_range, plan, d_params, true, 0, 0, ramp,
+                          gab::as_stream(stream));
 }
 
 int gab_reverb_set_params_tracks(gab_reverb_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
                                  gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_params) return gab::bad_arg("gab_reverb_set_params_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_reverb_set_params_tracks: the track range is outside the plan");
-        return gab::reverb_set_range(plan, d_params, first_track, n_tracks, ramp, gab::as_stream(stream),
-                                     "gab_reverb_set_params_tracks");
-    });
+    return gab::set_entry("gab_reverb_set_params_tracks", gab::reverb_set_range, plan, d_params, false, first_track,
+                          n_tracks, ramp, gab::as_stream(stream));
 }
 
 int gab_reverb_set_delays(gab_reverb_plan* plan, const int* d_delays, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_delays) return gab::bad_arg("gab_reverb_set_delays: null pointer");
-        return gab::reverb_set_delay_range(plan, d_delays, 0, plan->tracks, gab::as_stream(stream),
-                                           "gab_reverb_set_delays");
-    });
+    return gab::set_entry("gab_reverb_set_delays", gab::reverb_set_delay_range, plan, d_delays, true, 0, 0,
+                          gab::as_stream(stream));
 }
 
 int gab_reverb_set_delays_tracks(gab_reverb_plan* plan, const int* d_delays, int first_track, int n_tracks,
                                  gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_delays) return gab::bad_arg("gab_reverb_set_delays_tracks: null pointer");
-        if (!gab::track_range_ok(plan->tracks, first_track, n_tracks))
-            return gab::bad_arg("gab_reverb_set_delays_tracks: the track range is outside the plan");
-        return gab::reverb_set_delay_range(plan, d_delays, first_track, n_tracks, gab::as_stream(stream),
-                                           "gab_reverb_set_delays_tracks");
-    });
+    return gab::set_entry("gab_reverb_set_delays_tracks", gab::reverb_set_delay_range, plan, d_delays, false, first_track,
+                          n_tracks, gab::as_stream(stream));
 }
 
 int gab_reverb_reset(gab_reverb_plan* plan, gab_stream_t stream) {
@@ -500,9 +465,7 @@ int gab_reverb_process_batch(gab_reverb_plan* plan, const float* d_in, float* d_
 int gab_reverb_params(gab_reverb_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
     return gab::guarded([&]() -> int {
         if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_reverb_params: null pointer");
-        *d_current = plan->params.current.get();
-        *d_target = plan->params.target.get();
-        *n_floats = plan->params.current.size();
+        plan->params.expose(d_current, d_target, n_floats);
         return GAB_OK;
     });
 }
