@@ -1,9 +1,10 @@
-// gab_plan.hpp — what the host halves of the plans share: eq, mix, delay, meter, resample, dynamics and
-// reverb, and the fdl convolution for its memory.  Who owns device memory; "check, then commit" for a set of parameters
-// (one check kernel, a rule per plan); the entries of a ranged set; the table that is ramped from current to target
-// over one buffer.
+// gab_plan.hpp — what the host halves of the plans share.  Who owns device memory, pinned memory,
+// events and streams: every plan.  For eq, mix, delay, meter, resample, dynamics and reverb also "check, then commit"
+// for a set of parameters (one check kernel, a rule per plan); the entries of a ranged set; the table that is ramped
+// from current to target over one buffer.
 #pragma once
 
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -12,25 +13,106 @@
 
 namespace gab {
 
-// The owner of one hipMalloc allocation.  A plan holds these as members, so deleting the plan (or a create that throws
-// half-way, the plan in a unique_ptr) frees every buffer it has.
+// ---- the owners ----
+// Every GPU resource of a plan is a member of one of these four kinds, so deleting the plan (or a create that throws
+// half-way, the plan in a unique_ptr) gives back all of it and no destroy lists what to free.  Move-only; get() is the
+// raw handle for kernels and the runtime; made once, or again behind a release().
+inline void refuse_live(const void* live, const char* who) {
+    if (live) throw std::logic_error(std::string(who) + ": made again without a release() between");
+}
+
+// One device allocation (hipFree).  The contents are whatever the memory held.
 template <class T>
 class DeviceBuf {
 public:
     DeviceBuf() = default;
-    DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-    DeviceBuf& operator=(DeviceBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }
-    ~DeviceBuf() { if (p_) (void)hipFree(p_); }
-    void alloc(size_t n) {              // once per buffer; the contents are whatever the memory held
-        GAB_HIP_CHECK(hipMalloc(&p_, n * sizeof(T)));
+    DeviceBuf(DeviceBuf&& o) noexcept { swap(o); }
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept { swap(o); return *this; }     // (what this held goes with o)
+    ~DeviceBuf() { release(); }
+    void alloc(size_t n) { refuse_live(p_, "DeviceBuf"); GAB_HIP_CHECK(hipMalloc(&p_, n * sizeof(T))); n_ = n; }
+    // flags: hipDeviceMallocFinegrained (a copy engine fills it while a kernel reads it) or hipDeviceMallocDefault
+    void alloc_with_flags(size_t n, unsigned flags) {
+        refuse_live(p_, "DeviceBuf");
+        GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p_), n * sizeof(T), flags));
         n_ = n;
     }
+    void release() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }         // (for another size: release, then alloc)
+    void swap(DeviceBuf& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); }
     T* get() const { return p_; }
     size_t size() const { return n_; }  // elements
+    explicit operator bool() const { return p_ != nullptr; }
 
 private:
     T* p_ = nullptr;
     size_t n_ = 0;
+};
+
+// Pinned host memory (hipHostMalloc, hipHostFree), zeroed; the host reads and writes it in place.
+template <class T>
+class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept { swap(o); }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { swap(o); return *this; }
+    ~PinnedBuf() { release(); }
+    void alloc(size_t n) {
+        refuse_live(p_, "PinnedBuf");
+        GAB_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p_), n * sizeof(T), hipHostMallocDefault));
+        for (n_ = 0; n_ < n; ++n_) p_[n_] = T();
+    }
+    void release() { if (p_) (void)hipHostFree(p_); p_ = nullptr; n_ = 0; }
+    void swap(PinnedBuf& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); }
+    T* get() const { return p_; }
+    T& operator[](size_t i) const { return p_[i]; }
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// An event without timing.
+class Event {
+public:
+    Event() = default;
+    Event(Event&& o) noexcept { swap(o); }
+    Event& operator=(Event&& o) noexcept { swap(o); return *this; }
+    ~Event() { release(); }
+    void create() { refuse_live(e_, "Event"); GAB_HIP_CHECK(hipEventCreateWithFlags(&e_, hipEventDisableTiming)); }
+    void release() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
+    void swap(Event& o) noexcept { std::swap(e_, o.e_); }
+    hipEvent_t get() const { return e_; }
+    explicit operator bool() const { return e_ != nullptr; }
+
+private:
+    hipEvent_t e_ = nullptr;
+};
+
+// A stream of the plan's own.
+class Stream {
+public:
+    Stream() = default;
+    Stream(Stream&& o) noexcept { swap(o); }
+    Stream& operator=(Stream&& o) noexcept { swap(o); return *this; }
+    ~Stream() { release(); }
+    void create(unsigned flags) { refuse_live(s_, "Stream"); GAB_HIP_CHECK(hipStreamCreateWithFlags(&s_, flags)); }
+    // Non-blocking, at the HIGHEST priority: the runtime maps streams onto a few hardware queues per priority, and streams
+    // of the default priority never share a queue with this one (an upload beside the caller's launch; a resident launch)
+    static Stream highest_priority() {
+        Stream s;
+        int lo = 0, hi = 0;             // (numerically lower = higher priority)
+        GAB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        GAB_HIP_CHECK(hipStreamCreateWithPriority(&s.s_, hipStreamNonBlocking, hi));
+        return s;
+    }
+    void release() { if (s_) (void)hipStreamDestroy(s_); s_ = nullptr; }
+    void swap(Stream& o) noexcept { std::swap(s_, o.s_); }
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+
+private:
+    hipStream_t s_ = nullptr;
 };
 
 // ---- check, then commit: the check ----
@@ -74,7 +156,7 @@ int check_then(const DeviceBuf<unsigned>& flag, hipStream_t s, const char* who, 
     if (n > kMaxChecked) return bad_arg((std::string(who) + ": the range is too large for one call").c_str());
     unsigned first_bad = kNoneRefused;
     if (int rc = first_refused(flag, s, "check_kernel", [&] {
-            check_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, s>>>(d_src, flag.get(), n, rule);
+            hipLaunchKernelGGL((check_kernel<T, Rule>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_src, flag.get(), n, rule);
         }, &first_bad))
         return rc;
     if (first_bad != kNoneRefused) {

@@ -12,6 +12,7 @@
 #include <memory>
 
 #include "gab_common.hpp"
+#include "gab_plan.hpp"
 
 namespace gab {
 namespace {
@@ -424,12 +425,12 @@ int gab_datatransfer(const float* d_in, float* d_out, int in_size, int out_size,
 struct gab_link_plan {
     int max_in = 0;
     int workgroups = 256;
-    unsigned* stage = nullptr;        // fine-grained device memory, max_in words
-    unsigned* counter = nullptr;      // device
-    unsigned* words = nullptr;        // pinned: [0] done, [16] landed, [32] error
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copy_ev = nullptr;
-    hipEvent_t done_ev = nullptr;      // the launch's own completion (hipExtLaunchKernelGGL's stop event)
+    gab::DeviceBuf<unsigned> stage;   // fine-grained device memory, max_in words
+    gab::DeviceBuf<unsigned> counter; // device
+    gab::PinnedBuf<unsigned> words;   // pinned: [0] done, [16] landed, [32] error
+    gab::Stream copy_stream;
+    gab::Event copy_ev;
+    gab::Event done_ev;                // the launch's own completion (hipExtLaunchKernelGGL's stop event)
     unsigned epoch = 0;
     const void* checked_out = nullptr;
     // input words an earlier call uploaded but did not consume (its input was longer than its output): they hold
@@ -437,19 +438,9 @@ struct gab_link_plan {
     int stale_lo[2] = {0, 0}, stale_hi[2] = {0, 0};     // (per staging buffer)
     size_t side_words = 0;              // words per staging buffer: the plan holds TWO (stage, consumed), taken in turn by call parity, so that
                                         // no call waits for the check launch of the call before it
-    unsigned* consumed = nullptr;       // device: the words as the kernel took them (checked against the completed upload)
-    hipEvent_t check_ev[2] = {nullptr, nullptr};      // behind datatransfer_round_trip_check_kernel, per staging buffer (verdicts: words[48], words[56])
+    gab::DeviceBuf<unsigned> consumed;  // device: the words as the kernel took them (checked against the completed upload)
+    gab::Event check_ev[2];             // behind datatransfer_round_trip_check_kernel, per staging buffer (verdicts: words[48], words[56])
     bool check_pending[2] = {false, false};
-    ~gab_link_plan() {
-        if (consumed) (void)hipFree(consumed);
-        for (hipEvent_t e : check_ev) if (e) (void)hipEventDestroy(e);
-        if (stage) (void)hipFree(stage);
-        if (counter) (void)hipFree(counter);
-        if (words) (void)hipHostFree(words);
-        if (copy_ev) (void)hipEventDestroy(copy_ev);
-        if (done_ev) (void)hipEventDestroy(done_ev);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    }
 };
 
 int gab_link_plan_create(int max_in_size, gab_link_plan** out) {
@@ -461,21 +452,18 @@ int gab_link_plan_create(int max_in_size, gab_link_plan** out) {
         p->max_in = max_in_size;
         const size_t n = (size_t)std::max(max_in_size, 4);
         p->side_words = (n + 63) & ~(size_t)63;
-        GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->stage), 2 * p->side_words * 4, hipDeviceMallocFinegrained));
-        GAB_HIP_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->stage), (int)gab::kLinkSentinel, 2 * p->side_words));
-        GAB_HIP_CHECK(hipMalloc(&p->consumed, 2 * p->side_words * 4));
-        for (hipEvent_t& e : p->check_ev) GAB_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        GAB_HIP_CHECK(hipMalloc(&p->counter, 128));
-        GAB_HIP_CHECK(hipMemset(p->counter, 0, 128));
-        GAB_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p->words), 64 * sizeof(unsigned), hipHostMallocDefault));
-        for (int i = 0; i < 64; ++i) p->words[i] = 0;
-        {   // (the upload's stream at the highest priority: never on a hardware queue with the caller's — k_conv_accel.hip, gab_conv_round_trip_init)
-            int lo = 0, hi = 0;
-            GAB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            GAB_HIP_CHECK(hipStreamCreateWithPriority(&p->copy_stream, hipStreamNonBlocking, hi));
-        }
-        GAB_HIP_CHECK(hipEventCreateWithFlags(&p->copy_ev, hipEventDisableTiming));
-        GAB_HIP_CHECK(hipEventCreateWithFlags(&p->done_ev, hipEventDisableTiming));
+        // (the upload set-up of the conv round trip, k_conv_accel.hip ConvRoundTripState, over again: written out in both,
+        // because this one makes its counter between the check events and the pinned words and the other does not)
+        p->stage.alloc_with_flags(2 * p->side_words, hipDeviceMallocFinegrained);
+        GAB_HIP_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->stage.get()), (int)gab::kLinkSentinel, 2 * p->side_words));
+        p->consumed.alloc(2 * p->side_words);
+        for (gab::Event& e : p->check_ev) e.create();
+        p->counter.alloc(32);
+        GAB_HIP_CHECK(hipMemset(p->counter.get(), 0, 128));
+        p->words.alloc(64);
+        p->copy_stream = gab::Stream::highest_priority();   // the upload's stream: never on a hardware queue with the caller's
+        p->copy_ev.create();
+        p->done_ev.create();
 #ifdef GAB_ABLATE
         if (getenv("GAB_LINK_WGS")) p->workgroups = std::max(1, atoi(getenv("GAB_LINK_WGS")));
 #endif
@@ -495,7 +483,7 @@ static int gab_link_finish_check(gab_link_plan* p, int b, bool wait, const char*
     if (!p->check_pending[b]) return GAB_OK;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 0;;) {
-        const hipError_t q = hipEventQuery(p->check_ev[b]);
+        const hipError_t q = hipEventQuery(p->check_ev[b].get());
         if (q == hipSuccess) break;
         (void)hipGetLastError();
         if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -537,8 +525,8 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
             const int rb = gab_link_finish_check(p, buf ^ 1, false, "gab_datatransfer_round_trip (the previous call)");
             if (ra || rb) return ra ? ra : rb;
         }
-        unsigned* const stage = p->stage + (size_t)buf * p->side_words;
-        unsigned* const consumed = p->consumed + (size_t)buf * p->side_words;
+        unsigned* const stage = p->stage.get() + (size_t)buf * p->side_words;
+        unsigned* const consumed = p->consumed.get() + (size_t)buf * p->side_words;
         int& stale_lo = p->stale_lo[buf];
         int& stale_hi = p->stale_hi[buf];
         if (in_size < 0 || out_size < 0) return gab::bad_arg("gab_datatransfer_round_trip: negative size");
@@ -558,9 +546,9 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
             // this call reads words an earlier one left unconsumed: the sentinel goes back, ahead of the upload on its
             // stream, and the kernel's stream waits for it (steady repeats of one shape never come here)
             GAB_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(stage + stale_lo), (int)gab::kLinkSentinel,
-                                            (size_t)(stale_hi - stale_lo), p->copy_stream));
-            GAB_HIP_CHECK(hipEventRecord(p->copy_ev, p->copy_stream));
-            GAB_HIP_CHECK(hipStreamWaitEvent(s, p->copy_ev, 0));
+                                            (size_t)(stale_hi - stale_lo), p->copy_stream.get()));
+            GAB_HIP_CHECK(hipEventRecord(p->copy_ev.get(), p->copy_stream.get()));
+            GAB_HIP_CHECK(hipStreamWaitEvent(s, p->copy_ev.get(), 0));
             stale_lo = stale_hi = 0;
         }
         bool upload = in_size > 0;
@@ -586,35 +574,36 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
                 for (size_t off = 0; off < bytes;) {
                     const size_t n = off >= watched ? bytes - off : std::min(piece, bytes - off);
                     GAB_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(stage) + off, reinterpret_cast<const char*>(h_in) + off, n,
-                                                 hipMemcpyHostToDevice, p->copy_stream));
+                                                 hipMemcpyHostToDevice, p->copy_stream.get()));
                     off += n;
                 }
             }
-            if (!streamed) GAB_HIP_CHECK(hipStreamSynchronize(p->copy_stream));
+            if (!streamed) GAB_HIP_CHECK(hipStreamSynchronize(p->copy_stream.get()));
         }
         if (in_size > out_size) {
             stale_lo = stale_hi > stale_lo ? std::min(stale_lo, out_size) : out_size;
             stale_hi = std::max(stale_hi, in_size);
         }
         if (out_size == 0) {                            // nothing comes back: the call is the upload
-            GAB_HIP_CHECK(hipStreamSynchronize(p->copy_stream));
+            GAB_HIP_CHECK(hipStreamSynchronize(p->copy_stream.get()));
             return GAB_OK;
         }
         const unsigned epoch = p->epoch + 1;            // moves only when a launch has really been made (the device counter runs on)
-        volatile unsigned* const done = p->words;
-        unsigned* const landed = p->words + 16;
-        volatile unsigned* const error = p->words + 32;
-        gab::LinkRoundTrip rt{stage, h_out, p->counter, p->words, p->words + 16, p->words + 32, consumed, epoch, in_size, out_size};
+        unsigned* const words = p->words.get();
+        volatile unsigned* const done = words;
+        unsigned* const landed = words + 16;
+        volatile unsigned* const error = words + 32;
+        gab::LinkRoundTrip rt{stage, h_out, p->counter.get(), words, words + 16, words + 32, consumed, epoch, in_size, out_size};
         // the launch carries its own stop event: what the call returns on (k_conv_accel.hip, kRtCompletion: the cheapest of
         // the stated ways to learn that a launch has ended, profiles/r05_roundtrip_completion.txt)
-        hipExtLaunchKernelGGL(gab::datatransfer_round_trip_kernel, dim3(p->workgroups), dim3(gab::kBlock), 0, s, nullptr, p->done_ev, 0, rt);
+        hipExtLaunchKernelGGL(gab::datatransfer_round_trip_kernel, dim3(p->workgroups), dim3(gab::kBlock), 0, s, nullptr, p->done_ev.get(), 0, rt);
         int rc = gab::launch_status("datatransfer_round_trip_kernel");
         // after a wait that ran out (or a launch that was not made), words may sit in the stage without a consumer: the
         // launch bounds its own waits, so let it end, then start the next call from an all-sentinel stage
         auto repoison = [&]() {
             (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(p->copy_stream);
-            (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->stage), (int)gab::kLinkSentinel, 2 * p->side_words);
+            (void)hipStreamSynchronize(p->copy_stream.get());
+            (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->stage.get()), (int)gab::kLinkSentinel, 2 * p->side_words);
             p->words[48] = p->words[56] = 0;               // (check launches over words that never landed say nothing)
             p->check_pending[0] = p->check_pending[1] = false;
             (void)hipDeviceSynchronize();
@@ -625,15 +614,15 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
             return rc;
         }
         p->epoch = epoch;
-        if (upload && streamed) GAB_HIP_CHECK(hipEventRecord(p->copy_ev, p->copy_stream));
+        if (upload && streamed) GAB_HIP_CHECK(hipEventRecord(p->copy_ev.get(), p->copy_stream.get()));
         // The check launch: queued behind the main launch on its stream by the HOST, once the host has seen the upload's completion
         // event (k_conv_accel.hip, gab_conv_round_trip: no wait for that event is ever put into a stream)
         auto queue_check = [&]() {
             if (!(upload && dep > 0)) return;
             gab::datatransfer_round_trip_check_kernel<<<dim3(std::min(256, (dep + gab::kBlock - 1) / gab::kBlock)), dim3(gab::kBlock), 0, s>>>(
-                stage, consumed, p->words + 48 + 8 * buf, dep);
+                stage, consumed, words + 48 + 8 * buf, dep);
             if (gab::launch_status("datatransfer_round_trip_check_kernel")) throw std::runtime_error(gab::last_error());
-            GAB_HIP_CHECK(hipEventRecord(p->check_ev[buf], s));
+            GAB_HIP_CHECK(hipEventRecord(p->check_ev[buf].get(), s));
             p->check_pending[buf] = true;
         };
         if (upload && !streamed) queue_check();            // (an upload that was complete before the launch)
@@ -647,7 +636,7 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
         unsigned spins = 0;
         bool ended = false;
         while (*done != epoch || !told) {
-            if (!told && hipEventQuery(p->copy_ev) == hipSuccess) { __atomic_store_n(landed, epoch, __ATOMIC_RELEASE); told = true; queue_check(); }
+            if (!told && hipEventQuery(p->copy_ev.get()) == hipSuccess) { __atomic_store_n(landed, epoch, __ATOMIC_RELEASE); told = true; queue_check(); }
             if ((++spins & 1023u) == 0) {
                 if (told && hipStreamQuery(s) == hipSuccess) { ended = true; break; }
                 if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 4.0) {
@@ -662,7 +651,7 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
             GAB_HIP_CHECK(hipStreamSynchronize(s));
         } else {
             for (spins = 0;;) {
-                const hipError_t q = hipEventQuery(p->done_ev);
+                const hipError_t q = hipEventQuery(p->done_ev.get());
                 if (q == hipSuccess) break;
                 (void)hipGetLastError();
                 if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -685,10 +674,11 @@ int gab_datatransfer_round_trip(gab_link_plan* p, const float* h_in, float* h_ou
 
 // ---- keep-warm ---------------------------------------------------------------------------------------------------
 struct gab_keep_warm {
-    hipStream_t stream = nullptr;      // its own, highest priority: a resident launch holds its hardware queue, and streams
-                                       // of the default priority never share one with it (profiles/r05_incident_engine_queue_sharing.txt)
-    unsigned* words = nullptr;         // pinned host: [0] the kick count / stop word, [16] set by the launch as it ends,
+    // (in this order: behind the destructor's wait the stream goes first, then the words its launch wrote to)
+    gab::PinnedBuf<unsigned> words;    // pinned host: [0] the kick count / stop word, [16] set by the launch as it ends,
                                        // [32 + 2 b], [33 + 2 b] where workgroup b's wave landed (HW_ID, XCC_ID | 1 << 31)
+    gab::Stream stream;                // its own, highest priority: a resident launch holds its hardware queue, and streams
+                                       // of the default priority never share one with it (profiles/r05_incident_engine_queue_sharing.txt)
     unsigned count = 0;
     int workgroups = 1;
     int device = 0;
@@ -699,8 +689,7 @@ struct gab_keep_warm {
     ~gab_keep_warm() {
         gab::resident_remove(this);
         if (words && launched) __atomic_store_n(&words[0], gab::kKeepWarmStop, __ATOMIC_RELEASE);
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        if (words) (void)hipHostFree(words);
+        if (stream) (void)hipStreamSynchronize(stream.get());
     }
 };
 
@@ -715,13 +704,9 @@ int gab_keep_warm_create(gab_keep_warm** out, int workgroups, double idle_second
 #ifdef GAB_ABLATE
         if (getenv("GAB_KEEP_WARM_NAPS")) k->naps = std::max(1, atoi(getenv("GAB_KEEP_WARM_NAPS")));   // diagnostic builds: how often the waves look
 #endif
-        int lo = 0, hi = 0;
         GAB_HIP_CHECK(hipGetDevice(&k->device));
-        GAB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        GAB_HIP_CHECK(hipStreamCreateWithPriority(&k->stream, hipStreamNonBlocking, hi));
-        const int words = gab::kKeepWarmWords + 2 * workgroups;
-        GAB_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&k->words), words * sizeof(unsigned), hipHostMallocDefault));
-        for (int i = 0; i < words; ++i) k->words[i] = 0;
+        k->stream = gab::Stream::highest_priority();
+        k->words.alloc((size_t)(gab::kKeepWarmWords + 2 * workgroups));
         gab::resident_add(k.get(), k->device, gab::kResidentKeepWarm,
                           [](const void* o) { return static_cast<const gab_keep_warm*>(o)->running(); });
         *out = k.release();
@@ -746,12 +731,12 @@ int gab_keep_warm_kick(gab_keep_warm* k) {
         if (k->launched) {
             // workgroup 0 said the launch was ending: the stop word makes every straggler leave at its next look
             __atomic_store_n(&k->words[0], gab::kKeepWarmStop, __ATOMIC_RELEASE);
-            GAB_HIP_CHECK(hipStreamSynchronize(k->stream));
+            GAB_HIP_CHECK(hipStreamSynchronize(k->stream.get()));
         }
         for (int i = 0; i < 2 * k->workgroups; ++i) k->words[gab::kKeepWarmWords + i] = 0;
         __atomic_store_n(&k->words[0], k->count, __ATOMIC_RELEASE);
         __atomic_store_n(&k->words[16], 0u, __ATOMIC_RELEASE);
-        gab::keep_warm_kernel<<<dim3(k->workgroups), dim3(64), 0, k->stream>>>(k->words, k->words + 16, k->words + gab::kKeepWarmWords,
+        gab::keep_warm_kernel<<<dim3(k->workgroups), dim3(64), 0, k->stream.get()>>>(k->words.get(), k->words.get() + 16, k->words.get() + gab::kKeepWarmWords,
                                                                                (unsigned long long)(k->idle_seconds * 1e8), k->naps);
         int rc = gab::launch_status("keep_warm_kernel");
         if (rc) return rc;

@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -46,6 +47,7 @@
 
 #include "gab_common.hpp"
 #include "gab_fft.hpp"
+#include "gab_plan.hpp"
 #include "k_conv_fdl.hpp"
 
 namespace gab {
@@ -2331,6 +2333,49 @@ __global__ void conv_newest_block_kernel(const float* __restrict__ hist, float* 
     }
 }
 
+// What gab_conv_round_trip keeps (classic cut).  gab_conv_round_trip_state() returns it finished or throws: the plan
+// holds either all of it or none.
+struct ConvRoundTripState {
+    gab::DeviceBuf<unsigned> stage;     // fine-grained device memory the upload lands in: TWO buffers [2][T*B], taken in turn (call parity) — the
+                                        // check launch behind call k re-arms buffer k & 1 while call k + 1 is already filling the other
+    gab::DeviceBuf<float> park;         // device: outputs until their channel group is complete
+    gab::DeviceBuf<unsigned> counters;  // device: per-group arrivals, groups drained
+    gab::PinnedBuf<unsigned> words;     // pinned host: [0] done, [16] landed, [32] error, [48] the check launch's verdict (a 64-byte line each)
+    gab::Event check_ev[2];             // behind conv_round_trip_check_kernel, per staging buffer (verdicts: words[48], words[56])
+    bool check_pending[2] = {false, false};           // a check launch has been queued and its verdict not yet read
+    gab::Stream copy_stream;
+    gab::Event copy_ev;
+    gab::Event done_ev;                 // the launch's own completion (what gab_conv_round_trip returns on)
+    unsigned epoch = 0;
+    int groups = 0;
+    unsigned bound[gab::kRtMaxGroups + 1] = {};
+    const void* checked_out = nullptr;
+};
+
+// What the doorbell-fed engine keeps (split cut).  The launch's stream and event are made with the object and stay; the
+// rings are made anew when their length changes; `started` and `link` are each made whole at their first use.
+struct ConvEngineState {
+    ConvEngineState() : own_stream(gab::Stream::highest_priority()) { ev.create(); }
+    gab::Stream own_stream;             // at the HIGHEST priority: anything that shares a hardware queue with a resident launch stands behind it
+                                        // until the stop (round 5: a copy on the default stream did, and the engine starved for its own doorbell)
+    gab::Event ev;
+    gab::DeviceBuf<float> in;           // [ring][T*B], the producer writes it while the launch runs
+    gab::DeviceBuf<float> out;          // [ring][B*T]
+    int ring = 0;                       // buffers per ring; 0: there are no rings
+    struct Started {                    // gab_conv_engine_start, the first one
+        explicit Started(size_t prog_words) { done.alloc(prog_words); words.alloc(64); }
+        gab::DeviceBuf<unsigned> done;  // device: buffers finished per inverse wave [2 x workgroups]
+        gab::PinnedBuf<unsigned> words; // pinned host: [0] doorbell, [16] completed, [32] error, [48] first workgroup runs, [49] all of them do
+    };
+    std::unique_ptr<Started> started;
+    struct Link {                       // gab_conv_engine_round_trip: the two link legs (engine copies)
+        Link() { copy_stream.create(hipStreamNonBlocking); copy_ev.create(); }
+        gab::Stream copy_stream;
+        gab::Event copy_ev;
+    };
+    std::unique_ptr<Link> link;
+};
+
 struct gab_conv_plan {
     int tracks = 0, bufsize = 0, ir_len = 0;
     int pairs = 0;
@@ -2338,11 +2383,10 @@ struct gab_conv_plan {
     bool fused = false;      // bufsize == 512 && ir_len <= 4096
     bool tail = false;       // ir_len > 512 (partition B present)
     bool ir_set = false;
-    float4* pmA = nullptr;
-    float4* pmB = nullptr;
-    float* hist = nullptr;   // fused: [pairs][8 slots][512] complex (ch a, ch b); fallback: two linear [T][hlen]
-    float* hist_alt = nullptr;
-    float* ir_copy = nullptr;   // fallback path keeps the time-domain taps
+    gab::DeviceBuf<float4> pmA, pmB;
+    gab::DeviceBuf<float> hist;     // fused: [pairs][8 slots][512] complex (ch a, ch b); fallback: two linear [T][hlen]
+    gab::DeviceBuf<float> hist_alt;
+    gab::DeviceBuf<float> ir_copy;  // fallback path keeps the time-domain taps
     int hlen = 0;
     size_t spectra_bytes = 0, history_bytes = 0;
     const gab::fft::cf* tw = nullptr;
@@ -2350,65 +2394,41 @@ struct gab_conv_plan {
     // taps from its first buffer to the next reset: every streaming entry (one buffer, a batch, pinned
     // host buffers) launches that cut.
     bool split = false;
-    float4* pmA2 = nullptr;
-    float4* pmF = nullptr;
-    gab::fft::cf* carry = nullptr;
+    gab::DeviceBuf<float4> pmA2, pmF;
+    gab::DeviceBuf<gab::fft::cf> carry;
     size_t carry_bytes = 0;
     bool fresh = true;        // nothing has run since the last reset
-    // gab_conv_round_trip (classic cut): created at its first call
-    unsigned* rt_stage = nullptr;       // fine-grained device memory the upload lands in: TWO buffers [2][T*B], taken in turn (call parity) — the
-                                        // check launch behind call k re-arms buffer k & 1 while call k + 1 is already filling the other
-    float* rt_park = nullptr;           // device: outputs until their channel group is complete
-    unsigned* rt_counters = nullptr;    // device: per-group arrivals, groups drained
-    unsigned* rt_words = nullptr;       // pinned host: [0] done, [16] landed, [32] error, [48] the check launch's verdict (a 64-byte line each)
-    hipEvent_t rt_check_ev[2] = {nullptr, nullptr};   // behind conv_round_trip_check_kernel, per staging buffer (verdicts: rt_words[48], rt_words[56])
-    bool rt_check_pending[2] = {false, false};        // a check launch has been queued and its verdict not yet read
+    // gab_conv_round_trip (classic cut): made whole at its first call (gab_conv_round_trip_state), null until then
+    std::unique_ptr<ConvRoundTripState> rt;
     int rt_check_mode = 1;              // gab_conv_round_trip_set_check: 0 the verdict is ignored (the check launch still puts the sentinel back), 1 read at the next call, 2 read in the call
-    hipStream_t rt_copy_stream = nullptr;
-    hipEvent_t rt_copy_ev = nullptr;
-    hipEvent_t rt_done_ev = nullptr;      // the launch's own completion (what gab_conv_round_trip returns on)
     gab_keep_warm* warm = nullptr;        // gab_conv_round_trip_keep_warm: kicked at the end of every round trip while warm_on
     bool warm_on = false;
-    unsigned rt_epoch = 0;
-    int rt_groups = 0;
-    unsigned rt_bound[gab::kRtMaxGroups + 1] = {};
-    const void* rt_checked_out = nullptr;
-    // gab_conv_engine_* (split cut): one resident launch fed through a doorbell
-    float* eng_in = nullptr;            // fine-grained device memory: [ring][T*B], the producer writes it while the launch runs
-    float* eng_out = nullptr;           // [ring][B*T]
-    unsigned* eng_done = nullptr;       // device: buffers finished per inverse wave [2 x workgroups]
-    unsigned* eng_words = nullptr;      // pinned host: [0] doorbell, [16] completed, [32] error, [48] first workgroup runs, [49] all of them do
-    int eng_ring = 0;
+    // gab_conv_engine_* (split cut): one resident launch fed through a doorbell; made at the first gab_conv_engine_rings
+    std::unique_ptr<ConvEngineState> eng;
     double eng_idle_seconds = gab::kEngineIdleSeconds;   // gab_conv_engine_set_idle_limit
-    hipStream_t eng_copy_stream = nullptr;   // gab_conv_engine_round_trip: the two link legs (engine copies)
-    hipEvent_t eng_copy_ev = nullptr;
     bool eng_running = false;
     unsigned eng_published = 0;
     unsigned eng_seen_completed = 0;
-    hipStream_t eng_stream = nullptr;    // the stream the resident launch is on: the plan's own (below)
-    hipStream_t eng_own_stream = nullptr; // created at the first start, at the HIGHEST priority: the runtime maps streams onto a few hardware
-                                          // queues per priority, and anything that shares a queue with a resident launch stands behind it until
-                                          // the stop (round 5: a copy on the default stream did, and the engine starved for its own doorbell)
-    hipEvent_t eng_ev = nullptr;
+    hipStream_t eng_stream = nullptr;    // the stream the resident launch is on: eng->own_stream
     // uniform partitions (conv_uniform_kernel): other power-of-two buffer sizes / longer responses
     bool uniform = false;
     int uJ = 0, uS = 0, ring_len = 0;
     unsigned upos = 0;
-    float4* pmU = nullptr;
-    gab::fft::cf* ring = nullptr;
+    gab::DeviceBuf<float4> pmU;
+    gab::DeviceBuf<gab::fft::cf> ring;
     // the fdl scheme (k_conv_fdl.hip, gab_conv_create_scheme): a plan of its own kind; every supported entry hands it on
-    gab::fdl::Plan* fdl = nullptr;
+    std::unique_ptr<gab::fdl::Plan, void (*)(gab::fdl::Plan*)> fdl{nullptr, gab::fdl::destroy};
     // Ordering between gab_conv_reset (memsets on the caller's stream) and launches on OTHER streams
     // (channel ranges): the reset waits for every stream that launched since the previous reset, and
     // a stream's first launch after a reset waits for the reset's event.
     int device = 0;
-    hipEvent_t reset_ev = nullptr;
+    gab::Event reset_ev;
     hipStream_t reset_stream = nullptr;
     bool reset_recorded = false;
     std::vector<hipStream_t> used_streams;      // launched on since the last reset
     std::vector<hipStream_t> ordered_streams;   // already wait for reset_ev
     std::mutex order_mu;
-    hipEvent_t ir_ev = nullptr;                  // gab_conv_set_ir's waits (reset_ev stays the reset's)
+    gab::Event ir_ev;                            // gab_conv_set_ir's waits (reset_ev stays the reset's)
 
     // Before anything on `s` rewrites state that launches still in flight on other streams read (the reset's memsets,
     // set_ir's spectra): `s` waits for every stream launched on since the last reset, through `ev`.
@@ -2431,86 +2451,94 @@ struct gab_conv_plan {
         if (std::find(used_streams.begin(), used_streams.end(), s) == used_streams.end()) used_streams.push_back(s);
         if (!reset_recorded || s == reset_stream) return;
         if (std::find(ordered_streams.begin(), ordered_streams.end(), s) != ordered_streams.end()) return;
-        GAB_HIP_CHECK(hipStreamWaitEvent(s, reset_ev, 0));
+        GAB_HIP_CHECK(hipStreamWaitEvent(s, reset_ev.get(), 0));
         ordered_streams.push_back(s);
     }
 };
 
 extern "C" {
 
+// The members every plan has, whatever its scheme.
+static std::unique_ptr<gab_conv_plan> gab_conv_new_plan(int tracks, int bufsize, int ir_len) {
+    std::unique_ptr<gab_conv_plan> p(new gab_conv_plan);
+    p->tracks = tracks; p->bufsize = bufsize; p->ir_len = ir_len;
+    p->pairs = (tracks + 1) / 2;
+    GAB_HIP_CHECK(hipGetDevice(&p->device));
+    p->reset_ev.create();
+    p->ir_ev.create();
+    return p;
+}
+
+// The plan is whole: the registry of resident launches learns of it, and only then the caller.
+static int gab_conv_publish(std::unique_ptr<gab_conv_plan> p, gab_conv_plan** out) {
+    gab::resident_add(p.get(), p->device, gab::kResidentEngine,
+                      [](const void* o) { return static_cast<const gab_conv_plan*>(o)->eng_running; });
+    *out = p.release();
+    return GAB_OK;
+}
+
 int gab_conv_create(gab_conv_plan** out, int tracks, int bufsize, int ir_len) {
     return gab::guarded([&]() -> int {
         if (!out) return gab::bad_arg("gab_conv_create: null plan pointer");
+        *out = nullptr;
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_conv_create")) return rc;
         if (tracks <= 0 || bufsize <= 0 || ir_len <= 0)
             return gab::bad_arg("gab_conv_create: tracks, bufsize and ir_len must be > 0");
-        auto* p = new gab_conv_plan;
-        p->tracks = tracks; p->bufsize = bufsize; p->ir_len = ir_len;
-        p->pairs = (tracks + 1) / 2;
-        GAB_HIP_CHECK(hipGetDevice(&p->device));
-        GAB_HIP_CHECK(hipEventCreateWithFlags(&p->reset_ev, hipEventDisableTiming));
-        GAB_HIP_CHECK(hipEventCreateWithFlags(&p->ir_ev, hipEventDisableTiming));
+        std::unique_ptr<gab_conv_plan> p = gab_conv_new_plan(tracks, bufsize, ir_len);
         p->fused = (bufsize == gab::kB && ir_len <= gab::kNB);
         p->tail = ir_len > gab::kB;
         const bool pow2 = (bufsize & (bufsize - 1)) == 0;
         p->uniform = !p->fused && pow2 && bufsize >= 32 && bufsize <= 2048 && ir_len <= 16384;
-        try {
-            if (p->uniform) {
-                p->tw = gab::fft::device_twiddles();
-                p->uS = gab::kNB - bufsize;
-                p->uJ = 1 + (ir_len > bufsize ? (ir_len - bufsize + p->uS - 1) / p->uS : 0);
-                // oldest sample any window reaches, plus the slot the new block is written to
-                int need = gab::kNB + bufsize + (p->uJ > 1 ? bufsize + (p->uJ - 2) * p->uS : 0);
-                p->ring_len = gab::kNB;
-                while (p->ring_len < need) p->ring_len *= 2;
-                p->spectra_bytes = sizeof(float4) * (size_t)p->uJ * p->pairs * gab::kBinsB;
-                p->history_bytes = sizeof(gab::fft::cf) * (size_t)p->pairs * p->ring_len;
-                GAB_HIP_CHECK(hipMalloc(&p->pmU, p->spectra_bytes));
-                GAB_HIP_CHECK(hipMalloc(&p->ring, p->history_bytes));
-                GAB_HIP_CHECK(hipMemset(p->ring, 0, p->history_bytes));
-            } else if (p->fused) {
-                p->tw = gab::fft::device_twiddles();
-                size_t a = sizeof(float4) * (size_t)p->pairs * gab::kBinsA;
-                size_t b = p->tail ? sizeof(float4) * (size_t)p->pairs * gab::kBinsB : 0;
-                GAB_HIP_CHECK(hipMalloc(&p->pmA, a));
-                if (b) GAB_HIP_CHECK(hipMalloc(&p->pmB, b));
-                p->spectra_bytes = a + b;
-                p->history_bytes = sizeof(float) * (size_t)p->pairs * 2 * gab::kSlots * gab::kB;
-                GAB_HIP_CHECK(hipMalloc(&p->hist, p->history_bytes));
-                GAB_HIP_CHECK(hipMemset(p->hist, 0, p->history_bytes));
-                const bool can_split = ir_len > 2 * gab::kB && (tracks % 4) == 0;
-                p->split = can_split;                  // gab_conv_set_scheme picks the classic cut
-                if (can_split) {
-                    GAB_HIP_CHECK(hipMalloc(&p->pmA2, a));
-                    GAB_HIP_CHECK(hipMalloc(&p->pmF, b));
-                    p->carry_bytes = sizeof(gab::fft::cf) * (size_t)p->pairs * gab::kCarrySlots * gab::kB;
-                    GAB_HIP_CHECK(hipMalloc(&p->carry, p->carry_bytes));
-                    GAB_HIP_CHECK(hipMemset(p->carry, 0, p->carry_bytes));
-                }
-            } else {
-                int blocks = (ir_len - 1 + bufsize - 1) / bufsize;
-                p->hlen = (blocks < 1 ? 1 : blocks) * bufsize;
-                p->history_bytes = sizeof(float) * (size_t)tracks * p->hlen;
-                p->spectra_bytes = sizeof(float) * (size_t)tracks * ir_len;
-                GAB_HIP_CHECK(hipMalloc(&p->hist, p->history_bytes));
-                GAB_HIP_CHECK(hipMalloc(&p->hist_alt, p->history_bytes));
-                GAB_HIP_CHECK(hipMalloc(&p->ir_copy, p->spectra_bytes));
-                GAB_HIP_CHECK(hipMemset(p->hist, 0, p->history_bytes));
+        if (p->uniform) {
+            p->tw = gab::fft::device_twiddles();
+            p->uS = gab::kNB - bufsize;
+            p->uJ = 1 + (ir_len > bufsize ? (ir_len - bufsize + p->uS - 1) / p->uS : 0);
+            // oldest sample any window reaches, plus the slot the new block is written to
+            int need = gab::kNB + bufsize + (p->uJ > 1 ? bufsize + (p->uJ - 2) * p->uS : 0);
+            p->ring_len = gab::kNB;
+            while (p->ring_len < need) p->ring_len *= 2;
+            p->pmU.alloc((size_t)p->uJ * p->pairs * gab::kBinsB);
+            p->ring.alloc((size_t)p->pairs * p->ring_len);
+            p->spectra_bytes = sizeof(float4) * p->pmU.size();
+            p->history_bytes = sizeof(gab::fft::cf) * p->ring.size();
+            GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, p->history_bytes));
+        } else if (p->fused) {
+            p->tw = gab::fft::device_twiddles();
+            const size_t a = (size_t)p->pairs * gab::kBinsA;                  // float4 each
+            const size_t b = p->tail ? (size_t)p->pairs * gab::kBinsB : 0;
+            p->pmA.alloc(a);
+            if (b) p->pmB.alloc(b);
+            p->spectra_bytes = sizeof(float4) * (a + b);
+            p->hist.alloc((size_t)p->pairs * 2 * gab::kSlots * gab::kB);
+            p->history_bytes = sizeof(float) * p->hist.size();
+            GAB_HIP_CHECK(hipMemset(p->hist.get(), 0, p->history_bytes));
+            const bool can_split = ir_len > 2 * gab::kB && (tracks % 4) == 0;
+            p->split = can_split;                  // gab_conv_set_scheme picks the classic cut
+            if (can_split) {
+                p->pmA2.alloc(a);
+                p->pmF.alloc(b);
+                p->carry.alloc((size_t)p->pairs * gab::kCarrySlots * gab::kB);
+                p->carry_bytes = sizeof(gab::fft::cf) * p->carry.size();
+                GAB_HIP_CHECK(hipMemset(p->carry.get(), 0, p->carry_bytes));
             }
-        } catch (...) {
-            gab_conv_destroy(p);
-            throw;
+        } else {
+            int blocks = (ir_len - 1 + bufsize - 1) / bufsize;
+            p->hlen = (blocks < 1 ? 1 : blocks) * bufsize;
+            p->hist.alloc((size_t)tracks * p->hlen);
+            p->hist_alt.alloc((size_t)tracks * p->hlen);
+            p->ir_copy.alloc((size_t)tracks * ir_len);
+            p->history_bytes = sizeof(float) * p->hist.size();
+            p->spectra_bytes = sizeof(float) * p->ir_copy.size();
+            GAB_HIP_CHECK(hipMemset(p->hist.get(), 0, p->history_bytes));
         }
-        gab::resident_add(p, p->device, gab::kResidentEngine,
-                          [](const void* o) { return static_cast<const gab_conv_plan*>(o)->eng_running; });
-        *out = p;
-        return GAB_OK;
+        return gab_conv_publish(std::move(p), out);
     });
 }
 
 int gab_conv_create_scheme(gab_conv_plan** out, int tracks, int bufsize, int ir_len, int scheme) {
     return gab::guarded([&]() -> int {
         if (!out) return gab::bad_arg("gab_conv_create_scheme: null plan pointer");
+        *out = nullptr;
         if (scheme == GAB_CONV_SCHEME_CLASSIC || scheme == GAB_CONV_SCHEME_SPLIT) {
             if (int rc = gab_conv_create(out, tracks, bufsize, ir_len)) return rc;
             if (int rc = gab_conv_set_scheme(*out, scheme)) {
@@ -2529,22 +2557,9 @@ int gab_conv_create_scheme(gab_conv_plan** out, int tracks, int bufsize, int ir_
         if (ir_len < 1 || ir_len > (1 << 21))
             return gab::bad_arg("gab_conv_create_scheme: the fdl scheme needs 1 <= ir_len <= 2097152");
         if (int rc = gab::refuse_unsupported_runtime_mode("gab_conv_create_scheme")) return rc;
-        auto* p = new gab_conv_plan;
-        p->tracks = tracks; p->bufsize = bufsize; p->ir_len = ir_len;
-        p->pairs = (tracks + 1) / 2;
-        try {
-            GAB_HIP_CHECK(hipGetDevice(&p->device));
-            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->reset_ev, hipEventDisableTiming));
-            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->ir_ev, hipEventDisableTiming));
-            p->fdl = gab::fdl::create(tracks, bufsize, ir_len);
-        } catch (...) {
-            gab_conv_destroy(p);
-            throw;
-        }
-        gab::resident_add(p, p->device, gab::kResidentEngine,
-                          [](const void* o) { return static_cast<const gab_conv_plan*>(o)->eng_running; });
-        *out = p;
-        return GAB_OK;
+        std::unique_ptr<gab_conv_plan> p = gab_conv_new_plan(tracks, bufsize, ir_len);
+        p->fdl.reset(gab::fdl::create(tracks, bufsize, ir_len));
+        return gab_conv_publish(std::move(p), out);
     });
 }
 
@@ -2556,45 +2571,17 @@ static int gab_conv_refuse_fdl(const gab_conv_plan* p, const char* who) {
     return GAB_ERR_INVALID_ARG;
 }
 
+// What is not ownership, in this order; every buffer, event and stream then goes with the plan, behind the device-wide wait.
 int gab_conv_destroy(gab_conv_plan* p) {
     if (!p) return GAB_OK;
     gab::resident_remove(p);
     if (p->eng_running) {                                            // never leave a resident launch behind: ring the stop rung FIRST
-        if (p->eng_words) __atomic_store_n(&p->eng_words[0], p->eng_published | 0x80000000u, __ATOMIC_RELEASE);
-        (void)hipStreamSynchronize(p->eng_stream);                   // (a null handle is the default stream)
+        __atomic_store_n(&p->eng->started->words[0], p->eng_published | 0x80000000u, __ATOMIC_RELEASE);
+        (void)hipStreamSynchronize(p->eng_stream);
         p->eng_running = false;
     }
     if (p->warm) { (void)gab_keep_warm_destroy(p->warm); p->warm = nullptr; }   // (a resident launch: before the device-wide wait)
     (void)hipDeviceSynchronize();
-    if (p->pmA) (void)hipFree(p->pmA);
-    if (p->pmB) (void)hipFree(p->pmB);
-    if (p->hist) (void)hipFree(p->hist);
-    if (p->hist_alt) (void)hipFree(p->hist_alt);
-    if (p->ir_copy) (void)hipFree(p->ir_copy);
-    if (p->pmA2) (void)hipFree(p->pmA2);
-    if (p->pmF) (void)hipFree(p->pmF);
-    if (p->carry) (void)hipFree(p->carry);
-    if (p->pmU) (void)hipFree(p->pmU);
-    if (p->ring) (void)hipFree(p->ring);
-    if (p->fdl) gab::fdl::destroy(p->fdl);
-    if (p->reset_ev) (void)hipEventDestroy(p->reset_ev);
-    if (p->ir_ev) (void)hipEventDestroy(p->ir_ev);
-    if (p->rt_stage) (void)hipFree(p->rt_stage);
-    if (p->rt_park) (void)hipFree(p->rt_park);
-    if (p->rt_counters) (void)hipFree(p->rt_counters);
-    for (hipEvent_t e : p->rt_check_ev) if (e) (void)hipEventDestroy(e);
-    if (p->rt_words) (void)hipHostFree(p->rt_words);
-    if (p->eng_in) (void)hipFree(p->eng_in);
-    if (p->eng_out) (void)hipFree(p->eng_out);
-    if (p->eng_done) (void)hipFree(p->eng_done);
-    if (p->eng_words) (void)hipHostFree(p->eng_words);
-    if (p->rt_copy_ev) (void)hipEventDestroy(p->rt_copy_ev);
-    if (p->eng_ev) (void)hipEventDestroy(p->eng_ev);
-    if (p->eng_own_stream) (void)hipStreamDestroy(p->eng_own_stream);
-    if (p->eng_copy_ev) (void)hipEventDestroy(p->eng_copy_ev);
-    if (p->eng_copy_stream) (void)hipStreamDestroy(p->eng_copy_stream);
-    if (p->rt_done_ev) (void)hipEventDestroy(p->rt_done_ev);
-    if (p->rt_copy_stream) (void)hipStreamDestroy(p->rt_copy_stream);
     delete p;
     return GAB_OK;
 }
@@ -2604,35 +2591,35 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
         if (!p || !d_ir) return gab::bad_arg("gab_conv_set_ir: null argument");
         if (p->eng_running) return gab::bad_arg("gab_conv_set_ir: the plan's engine is running (gab_conv_engine_stop first)");
         hipStream_t s = gab::as_stream(stream);
-        p->wait_for_used_streams(s, p->ir_ev, false);       // launches in flight on other streams run with the taps they were queued under
-        if (p->fdl) {
-            gab::fdl::set_ir(p->fdl, d_ir, s);                  // every partition in one launch
+        p->wait_for_used_streams(s, p->ir_ev.get(), false);       // launches in flight on other streams run with the taps they were queued under
+        if (p->fdl.get()) {
+            gab::fdl::set_ir(p->fdl.get(), d_ir, s);                  // every partition in one launch
         } else if (p->uniform) {
             for (int j = 0; j < p->uJ; ++j)
                 gab::conv_ir_spectra_uniform_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
-                    d_ir, p->pmU + (size_t)j * p->pairs * gab::kBinsB, p->tw, p->tracks, p->ir_len,
+                    d_ir, p->pmU.get() + (size_t)j * p->pairs * gab::kBinsB, p->tw, p->tracks, p->ir_len,
                     j == 0 ? 0 : p->bufsize + (j - 1) * p->uS, j == 0 ? p->bufsize : p->uS);
             int rc = gab::launch_status("conv_ir_spectra_uniform_kernel");
             if (rc) return rc;
         } else if (p->fused) {
             // pmB is null when ir_len <= 512: the kernel then skips partition B
             gab::conv_ir_spectra_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
-                d_ir, p->pmA, p->pmB, p->tw, p->tracks, p->ir_len, 0, gab::kB);
+                d_ir, p->pmA.get(), p->pmB.get(), p->tw, p->tracks, p->ir_len, 0, gab::kB);
             if (p->pmF)
                 gab::conv_ir_spectra_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
-                    d_ir, p->pmA2, p->pmF, p->tw, p->tracks, p->ir_len, gab::kB, 2 * gab::kB);
+                    d_ir, p->pmA2.get(), p->pmF.get(), p->tw, p->tracks, p->ir_len, gab::kB, 2 * gab::kB);
             int rc = gab::launch_status("conv_ir_spectra_kernel");
             if (rc) return rc;
             if (p->split && !p->fresh) {
                 // the carry ring holds the far share of the next two blocks under the old taps: recompute it from the
                 // history ring (block head - 1 is the newest) with the new ones
                 gab::conv_split_carry_refresh_kernel<<<p->pairs, gab::kThreads, 0, s>>>(
-                    p->hist, p->pmF, p->carry, p->tw, (p->head + gab::kSlots - 1) & (gab::kSlots - 1));
+                    p->hist.get(), p->pmF.get(), p->carry.get(), p->tw, (p->head + gab::kSlots - 1) & (gab::kSlots - 1));
                 rc = gab::launch_status("conv_split_carry_refresh_kernel");
                 if (rc) return rc;
             }
         } else {
-            GAB_HIP_CHECK(hipMemcpyAsync(p->ir_copy, d_ir, p->spectra_bytes,
+            GAB_HIP_CHECK(hipMemcpyAsync(p->ir_copy.get(), d_ir, p->spectra_bytes,
                                          hipMemcpyDeviceToDevice, s));
         }
         GAB_HIP_CHECK(hipStreamSynchronize(s));
@@ -2643,7 +2630,7 @@ int gab_conv_set_ir(gab_conv_plan* p, const float* d_ir, gab_stream_t stream) {
 
 int gab_conv_set_scheme(gab_conv_plan* p, int scheme) {
     if (!p) return gab::bad_arg("gab_conv_set_scheme: null plan");
-    if (p->fdl) {
+    if (p->fdl.get()) {
         if (scheme == GAB_CONV_SCHEME_FDL) return GAB_OK;
         return gab::bad_arg("gab_conv_set_scheme: a plan of the fdl scheme keeps it (create another plan for the classic or split cut)");
     }
@@ -2669,22 +2656,22 @@ int gab_conv_reset(gab_conv_plan* p, gab_stream_t stream) {
         if (!p) return gab::bad_arg("gab_conv_reset: null plan");
         if (p->eng_running) return gab::bad_arg("gab_conv_reset: the plan's engine is running (gab_conv_engine_stop first)");
         for (int b = 0; b < 2; ++b)                            // (a reset starts the stream anew: the last round trips' verdicts no longer matter)
-            if (p->rt_check_pending[b]) {
-                (void)hipEventSynchronize(p->rt_check_ev[b]);
-                p->rt_check_pending[b] = false;
-                p->rt_words[48 + 8 * b] = 0;
+            if (p->rt && p->rt->check_pending[b]) {
+                (void)hipEventSynchronize(p->rt->check_ev[b].get());
+                p->rt->check_pending[b] = false;
+                p->rt->words[48 + 8 * b] = 0;
             }
         hipStream_t s = gab::as_stream(stream);
-        p->wait_for_used_streams(s, p->reset_ev, true);      // launches still in flight on other streams read the rings: the memsets go behind them
-        if (p->fdl) gab::fdl::reset(p->fdl, s);
-        else if (p->uniform) GAB_HIP_CHECK(hipMemsetAsync(p->ring, 0, p->history_bytes, s));
-        else GAB_HIP_CHECK(hipMemsetAsync(p->hist, 0, p->history_bytes, s));
+        p->wait_for_used_streams(s, p->reset_ev.get(), true);      // launches still in flight on other streams read the rings: the memsets go behind them
+        if (p->fdl.get()) gab::fdl::reset(p->fdl.get(), s);
+        else if (p->uniform) GAB_HIP_CHECK(hipMemsetAsync(p->ring.get(), 0, p->history_bytes, s));
+        else GAB_HIP_CHECK(hipMemsetAsync(p->hist.get(), 0, p->history_bytes, s));
         p->head = 0;
         p->upos = 0;
-        if (p->carry) GAB_HIP_CHECK(hipMemsetAsync(p->carry, 0, p->carry_bytes, s));
+        if (p->carry) GAB_HIP_CHECK(hipMemsetAsync(p->carry.get(), 0, p->carry_bytes, s));
         {
             std::lock_guard<std::mutex> lock(p->order_mu);
-            GAB_HIP_CHECK(hipEventRecord(p->reset_ev, s));
+            GAB_HIP_CHECK(hipEventRecord(p->reset_ev.get(), s));
             p->reset_stream = s;
             p->reset_recorded = true;
         }
@@ -2704,14 +2691,14 @@ int gab_conv_process(gab_conv_plan* p, const float* d_in, float* d_out, int mode
         hipStream_t s = gab::as_stream(stream);
         const bool streaming = mode != GAB_CONV_STATELESS;
         if (streaming) p->order_after_reset(s);
-        if (p->fdl) {                                        // device or pinned host buffers: the same three launches
-            gab::fdl::process(p->fdl, d_in, d_out, streaming, s);
+        if (p->fdl.get()) {                                        // device or pinned host buffers: the same three launches
+            gab::fdl::process(p->fdl.get(), d_in, d_out, streaming, s);
             if (streaming) p->fresh = false;
             return GAB_OK;
         }
         if (p->uniform) {
             if (mode == GAB_CONV_STREAMING_HOST_IO) mode = GAB_CONV_STREAMING;      // same kernel, host pointers
-            gab::ConvUniform u{p->pmU, p->ring, p->uJ, p->uS, p->ring_len - 1, p->upos};
+            gab::ConvUniform u{p->pmU.get(), p->ring.get(), p->uJ, p->uS, p->ring_len - 1, p->upos};
             if (streaming) {
                 gab::conv_uniform_kernel<true><<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(
                     d_in, d_out, u, p->tw, p->tracks, p->bufsize);
@@ -2725,17 +2712,17 @@ int gab_conv_process(gab_conv_plan* p, const float* d_in, float* d_out, int mode
         }
         if (p->fused) {
             dim3 grid(p->pairs), block(gab::kThreads);
-#define GAB_CONV_ARGS d_in, d_out, p->hist, p->pmA, p->pmB, p->tw, p->tracks, p->head
+#define GAB_CONV_ARGS d_in, d_out, p->hist.get(), p->pmA.get(), p->pmB.get(), p->tw, p->tracks, p->head
             if (streaming) p->fresh = false;
             if (streaming && p->split) {
                 // pinned host buffers: the same kernel under its own name (it runs at link speed: the new
                 // block crosses the link once per role, 99 us per round trip against the classic cut's 90)
-                gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
+                gab::ConvSplit sp{p->pmA2.get(), p->pmF.get(), p->carry.get() GAB_SPLIT_DEBUG_ARG};
                 if (mode == GAB_CONV_STREAMING_HOST_IO)
-                    gab::conv_split_host_io_kernel<<<grid, block, 0, s>>>(d_in, d_out, p->hist, p->pmA, sp, p->tw,
+                    gab::conv_split_host_io_kernel<<<grid, block, 0, s>>>(d_in, d_out, p->hist.get(), p->pmA.get(), sp, p->tw,
                                                                          p->tracks, p->head);
                 else
-                    gab::conv_split_kernel<<<grid, block, 0, s>>>(d_in, d_out, p->hist, p->pmA, sp, p->tw,
+                    gab::conv_split_kernel<<<grid, block, 0, s>>>(d_in, d_out, p->hist.get(), p->pmA.get(), sp, p->tw,
                                                                  p->tracks, p->head);
                 int rc = gab::launch_status("conv_split_kernel");
                 if (rc) return rc;
@@ -2759,14 +2746,14 @@ int gab_conv_process(gab_conv_plan* p, const float* d_in, float* d_out, int mode
             dim3 block(256), grid((p->bufsize + 255) / 256, p->tracks);
             if (streaming) {
                 gab::conv_direct_kernel<true><<<grid, block, 0, s>>>(
-                    d_in, d_out, p->hist, p->ir_copy, p->tracks, p->bufsize, p->ir_len, p->hlen);
+                    d_in, d_out, p->hist.get(), p->ir_copy.get(), p->tracks, p->bufsize, p->ir_len, p->hlen);
                 dim3 g2((p->hlen + 255) / 256, p->tracks);
                 gab::conv_direct_shift_kernel<<<g2, block, 0, s>>>(
-                    d_in, p->hist, p->hist_alt, p->tracks, p->bufsize, p->hlen);
-                std::swap(p->hist, p->hist_alt);
+                    d_in, p->hist.get(), p->hist_alt.get(), p->tracks, p->bufsize, p->hlen);
+                p->hist.swap(p->hist_alt);
             } else {
                 gab::conv_direct_kernel<false><<<grid, block, 0, s>>>(
-                    d_in, d_out, p->hist, p->ir_copy, p->tracks, p->bufsize, p->ir_len, p->hlen);
+                    d_in, d_out, p->hist.get(), p->ir_copy.get(), p->tracks, p->bufsize, p->ir_len, p->hlen);
             }
             int rc = gab::launch_status("conv_direct_kernel");
             if (rc) return rc;
@@ -2775,12 +2762,14 @@ int gab_conv_process(gab_conv_plan* p, const float* d_in, float* d_out, int mode
     });
 }
 
-// The staging buffers, counters and the upload stream of gab_conv_round_trip.
-static void gab_conv_round_trip_init(gab_conv_plan* p) {
+// The staging buffers, counters and the upload stream of gab_conv_round_trip: all of them, or an exception and nothing.
+// (gab_link_plan_create, k_basic.hip, makes the same upload set-up: see there why it is written out twice.)
+static std::unique_ptr<ConvRoundTripState> gab_conv_round_trip_state(const gab_conv_plan* p) {
+    std::unique_ptr<ConvRoundTripState> rt(new ConvRoundTripState);
     const size_t n = (size_t)p->tracks * p->bufsize;
-    GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->rt_stage), 2 * n * 4, hipDeviceMallocFinegrained));
-    GAB_HIP_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->rt_stage), (int)gab::kRtSentinel, 2 * n));
-    GAB_HIP_CHECK(hipMalloc(&p->rt_park, n * 4));
+    rt->stage.alloc_with_flags(2 * n, hipDeviceMallocFinegrained);
+    GAB_HIP_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(rt->stage.get()), (int)gab::kRtSentinel, 2 * n));
+    rt->park.alloc(n);
     const int groups = 16;                            // 64 channels = 256-byte rows at 1024 channels
     int ppg = (p->pairs + groups - 1) / groups;
     ppg += ppg & 1;                                   // whole float4 columns per row
@@ -2804,37 +2793,32 @@ static void gab_conv_round_trip_init(gab_conv_plan* p) {
         fine.insert(fine.end(), v.begin(), v.end());
     }
     if ((int)fine.size() > gab::kRtMaxGroups) throw std::runtime_error("gab_conv_round_trip: too many channel groups");
-    p->rt_groups = (int)fine.size();
-    p->rt_bound[0] = 0;
-    for (int g = 0; g < p->rt_groups; ++g) p->rt_bound[g + 1] = p->rt_bound[g] + (unsigned)fine[g];
-    GAB_HIP_CHECK(hipMalloc(&p->rt_counters, sizeof(unsigned) * 32 * (p->rt_groups + 1)));      // a 128-byte line per group, one for the shares drained
-    GAB_HIP_CHECK(hipMemset(p->rt_counters, 0, sizeof(unsigned) * 32 * (p->rt_groups + 1)));
-    for (hipEvent_t& e : p->rt_check_ev) GAB_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    GAB_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p->rt_words), 64 * sizeof(unsigned), hipHostMallocDefault));
-    for (int i = 0; i < 64; ++i) p->rt_words[i] = 0;
-    {
-        // The upload's stream at the HIGHEST priority: the runtime maps streams onto a few hardware queues per priority, and where
-        // the upload's stream shares a queue with the caller's, the main launch stands behind the copy's completion packet — the
-        // call then takes upload + kernel, 123-143 us instead of 70 (measured after an engine's streams had come and gone in the
-        // process: profiles/r06_roundtrip_check.txt).  Streams of the default priority never share a queue with it.
-        int lo = 0, hi = 0;
-        GAB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        GAB_HIP_CHECK(hipStreamCreateWithPriority(&p->rt_copy_stream, hipStreamNonBlocking, hi));
-    }
-    GAB_HIP_CHECK(hipEventCreateWithFlags(&p->rt_copy_ev, hipEventDisableTiming));
-    GAB_HIP_CHECK(hipEventCreateWithFlags(&p->rt_done_ev, hipEventDisableTiming));
+    rt->groups = (int)fine.size();
+    rt->bound[0] = 0;
+    for (int g = 0; g < rt->groups; ++g) rt->bound[g + 1] = rt->bound[g] + (unsigned)fine[g];
+    rt->counters.alloc((size_t)32 * (rt->groups + 1));      // a 128-byte line per group, one for the shares drained
+    GAB_HIP_CHECK(hipMemset(rt->counters.get(), 0, sizeof(unsigned) * rt->counters.size()));
+    for (gab::Event& e : rt->check_ev) e.create();
+    rt->words.alloc(64);
+    // The upload's stream at the HIGHEST priority: the runtime maps streams onto a few hardware queues per priority, and where
+    // the upload's stream shares a queue with the caller's, the main launch stands behind the copy's completion packet — the
+    // call then takes upload + kernel, 123-143 us instead of 70 (measured after an engine's streams had come and gone in the
+    // process: profiles/r06_roundtrip_check.txt).  Streams of the default priority never share a queue with it.
+    rt->copy_stream = gab::Stream::highest_priority();
+    rt->copy_ev.create();
+    rt->done_ev.create();
     GAB_HIP_CHECK(hipDeviceSynchronize());
-    p->rt_epoch = 0;
+    return rt;
 }
 
 // The verdict of the last check launch (conv_round_trip_check_kernel): waits for it (it runs a few microseconds behind the call
 // that queued it), GAB_OK or GAB_ERR_RUNTIME with the message.  The plan's next upload must come behind it either way: the
 // check launch is what puts the sentinel back.
 static int gab_conv_round_trip_finish_check(gab_conv_plan* p, int b, bool wait, const char* who) {
-    if (!p->rt_check_pending[b]) return GAB_OK;
+    if (!p->rt || !p->rt->check_pending[b]) return GAB_OK;      // (no round trip yet: nothing is pending)
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 0;;) {
-        const hipError_t q = hipEventQuery(p->rt_check_ev[b]);
+        const hipError_t q = hipEventQuery(p->rt->check_ev[b].get());
         if (q == hipSuccess) break;
         (void)hipGetLastError();
         if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -2844,9 +2828,9 @@ static int gab_conv_round_trip_finish_check(gab_conv_plan* p, int b, bool wait, 
             return GAB_ERR_RUNTIME;
         }
     }
-    p->rt_check_pending[b] = false;
-    const unsigned verdict = __atomic_load_n(&p->rt_words[48 + 8 * b], __ATOMIC_ACQUIRE);
-    p->rt_words[48 + 8 * b] = 0;
+    p->rt->check_pending[b] = false;
+    const unsigned verdict = __atomic_load_n(&p->rt->words[48 + 8 * b], __ATOMIC_ACQUIRE);
+    p->rt->words[48 + 8 * b] = 0;
     if (p->rt_check_mode != 0 && (verdict & gab::kRtErrTorn)) {
         gab::set_last_error(std::string(who) + ": a word the round trip's kernel consumed while the upload was still running is not the word the "
                             "completed upload left in the staging buffer (an engine write that landed in pieces or out of order): the output of THAT "
@@ -2900,31 +2884,32 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
             GAB_HIP_CHECK(hipStreamSynchronize(s));
             return GAB_OK;
         }
-        if (!p->rt_stage) gab_conv_round_trip_init(p);
+        if (!p->rt) p->rt = gab_conv_round_trip_state(p);
         // The staging buffers take turns: this call fills buffer (epoch + 1) & 1, whose check launch (queued two calls ago: it
         // puts the sentinel back) must be through — waited for; the OTHER buffer's check (the previous call's) is looked at
         // without waiting: a paced caller finds its verdict here, a back-to-back caller one call later.
         {
-            const int mine = (int)((p->rt_epoch + 1) & 1u);
+            const int mine = (int)((p->rt->epoch + 1) & 1u);
             const int ra = gab_conv_round_trip_finish_check(p, mine, true, "gab_conv_round_trip (an earlier call)");
             const int rb = gab_conv_round_trip_finish_check(p, mine ^ 1, false, "gab_conv_round_trip (the previous call)");
             if (ra || rb) return ra ? ra : rb;
         }
-        if (p->rt_checked_out != h_out) {              // the kernel writes h_out itself: it must be mapped into the device
+        if (p->rt->checked_out != h_out) {              // the kernel writes h_out itself: it must be mapped into the device
             if (!mapped(h_out))
                 return gab::bad_arg("gab_conv_round_trip: h_out must be pinned host memory (hipHostMalloc) or device memory");
-            p->rt_checked_out = h_out;
+            p->rt->checked_out = h_out;
         }
         p->order_after_reset(s);
         const size_t bytes = sizeof(float) * (size_t)p->tracks * p->bufsize;
         // the device counters run on from launch to launch and are compared with epoch x members: the plan's epoch moves
         // only when a launch has really been made
-        const unsigned epoch = p->rt_epoch + 1;
+        const unsigned epoch = p->rt->epoch + 1;
         const int buf = (int)(epoch & 1u);                                           // this call's staging buffer
-        unsigned* const stage = p->rt_stage + (size_t)buf * p->tracks * p->bufsize;
-        volatile unsigned* const done = p->rt_words;
-        unsigned* const landed = p->rt_words + 16;
-        volatile unsigned* const error = p->rt_words + 32;
+        unsigned* const stage = p->rt->stage.get() + (size_t)buf * p->tracks * p->bufsize;
+        unsigned* const words = p->rt->words.get();
+        volatile unsigned* const done = words;
+        unsigned* const landed = words + 16;
+        volatile unsigned* const error = words + 32;
         bool upload = true;
 #ifdef GAB_ABLATE
         if (getenv("GAB_RT_SKIP_UPLOAD")) upload = false;   // diagnostic builds: the input never lands — every wait must run out
@@ -2939,10 +2924,10 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         // put the stage back to all-sentinel and the upload stream to rest (after anything that may have left words behind)
         auto rearm_stage = [&]() {
             (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(p->rt_copy_stream);
-            (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->rt_stage), (int)gab::kRtSentinel, 2 * (size_t)p->tracks * p->bufsize);
-            p->rt_words[48] = p->rt_words[56] = 0;      // (check launches over words that never landed say nothing)
-            p->rt_check_pending[0] = p->rt_check_pending[1] = false;
+            (void)hipStreamSynchronize(p->rt->copy_stream.get());
+            (void)hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(p->rt->stage.get()), (int)gab::kRtSentinel, 2 * (size_t)p->tracks * p->bufsize);
+            p->rt->words[48] = p->rt->words[56] = 0;      // (check launches over words that never landed say nothing)
+            p->rt->check_pending[0] = p->rt->check_pending[1] = false;
             (void)hipDeviceSynchronize();
         };
         // The engine copy goes out in pieces of kRtUploadPiece bytes, a multiple of four: the runtime cuts a copy into engine
@@ -2959,7 +2944,7 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         auto upload_range = [&](size_t lo, size_t hi) {
             for (size_t off = lo; off < hi; off += gab::kRtUploadPiece)
                 GAB_HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char*>(stage) + off, reinterpret_cast<const char*>(h_in) + off,
-                                             std::min(gab::kRtUploadPiece, hi - off), hipMemcpyHostToDevice, p->rt_copy_stream));
+                                             std::min(gab::kRtUploadPiece, hi - off), hipMemcpyHostToDevice, p->rt->copy_stream.get()));
         };
         auto upload_pieces = [&]() {
             if (tear < 0) { upload_range(0, bytes); return; }
@@ -2974,26 +2959,26 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         };
         if (upload && !mapped(h_in)) {
             upload_pieces();
-            GAB_HIP_CHECK(hipStreamSynchronize(p->rt_copy_stream));
+            GAB_HIP_CHECK(hipStreamSynchronize(p->rt->copy_stream.get()));
             __atomic_store_n(landed, epoch, __ATOMIC_RELEASE);
             streamed = false;
         } else if (upload) {
             upload_pieces();
         }
-        gab::ConvRoundTrip rt{stage, p->rt_park, h_out, p->rt_counters, p->rt_words, p->rt_words + 16, p->rt_words + 32,
-                              epoch, p->rt_groups, {}};
-        for (int g = 0; g <= p->rt_groups; ++g) rt.bound[g] = p->rt_bound[g];
+        gab::ConvRoundTrip rt{stage, p->rt->park.get(), h_out, p->rt->counters.get(), words, words + 16, words + 32,
+                              epoch, p->rt->groups, {}};
+        for (int g = 0; g <= p->rt->groups; ++g) rt.bound[g] = p->rt->bound[g];
         // The launch's own stop event (hipExtLaunchKernelGGL) is how its end is observed: queried below (measured against
         // hipStreamSynchronize, an event recorded behind the launch and hipStreamQuery: profiles/r05_roundtrip_completion.txt).
-        hipExtLaunchKernelGGL(gab::conv_round_trip_kernel, dim3(p->pairs), dim3(gab::kThreads), 0, s, nullptr, p->rt_done_ev, 0,
-                              rt, p->hist, (const float4*)p->pmA, (const float4*)p->pmB, (const gab::fft::cf*)p->tw, p->tracks, p->head);
+        hipExtLaunchKernelGGL(gab::conv_round_trip_kernel, dim3(p->pairs), dim3(gab::kThreads), 0, s, nullptr, p->rt->done_ev.get(), 0,
+                              rt, p->hist.get(), (const float4*)p->pmA.get(), (const float4*)p->pmB.get(), (const gab::fft::cf*)p->tw, p->tracks, p->head);
         int rc = gab::launch_status("conv_round_trip_kernel");
         if (rc) {                                       // nothing ran: the epoch, the history and the counters stay as they were
             if (upload) rearm_stage();                  // (the upload did: its words must not pass for the next call's)
             return rc;
         }
-        p->rt_epoch = epoch;
-        if (upload && streamed) GAB_HIP_CHECK(hipEventRecord(p->rt_copy_ev, p->rt_copy_stream));
+        p->rt->epoch = epoch;
+        if (upload && streamed) GAB_HIP_CHECK(hipEventRecord(p->rt->copy_ev.get(), p->rt->copy_stream.get()));
         // The check launch: queued on the caller's stream (behind the main launch) by the HOST, once the host has seen the upload's
         // completion event — no wait for that event is ever put into a stream: the runtime maps streams onto a few hardware
         // queues, and a barrier that waits 15-20 us for the event holds up whatever shares its queue (measured: the next call's
@@ -3002,10 +2987,10 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         // the sentinel back.
         const int consumed_slot = p->head;
         auto queue_check = [&]() {
-            gab::conv_round_trip_check_kernel<<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(stage, p->hist, p->rt_words + 48 + 8 * buf, consumed_slot);
+            gab::conv_round_trip_check_kernel<<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(stage, p->hist.get(), words + 48 + 8 * buf, consumed_slot);
             if (gab::launch_status("conv_round_trip_check_kernel")) throw std::runtime_error(gab::last_error());
-            GAB_HIP_CHECK(hipEventRecord(p->rt_check_ev[buf], s));
-            p->rt_check_pending[buf] = true;
+            GAB_HIP_CHECK(hipEventRecord(p->rt->check_ev[buf].get(), s));
+            p->rt->check_pending[buf] = true;
         };
         if (upload && !streamed) queue_check();         // (an upload that was complete before the launch)
         p->head = (p->head + 1) & (gab::kSlots - 1);
@@ -3031,10 +3016,10 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
         unsigned spins = 0;
         bool ended = false;
         while (!told || *done != epoch) {
-            if (!told && hipEventQuery(p->rt_copy_ev) == hipSuccess) {
+            if (!told && hipEventQuery(p->rt->copy_ev.get()) == hipSuccess) {
                 if (tear >= 0) {                            // (diagnostic builds) the word's right value, late
-                    GAB_HIP_CHECK(hipMemcpyAsync(stage + tear, reinterpret_cast<const unsigned*>(h_in) + tear, 4, hipMemcpyHostToDevice, p->rt_copy_stream));
-                    GAB_HIP_CHECK(hipStreamSynchronize(p->rt_copy_stream));
+                    GAB_HIP_CHECK(hipMemcpyAsync(stage + tear, reinterpret_cast<const unsigned*>(h_in) + tear, 4, hipMemcpyHostToDevice, p->rt->copy_stream.get()));
+                    GAB_HIP_CHECK(hipStreamSynchronize(p->rt->copy_stream.get()));
                 }
                 __atomic_store_n(landed, epoch, __ATOMIC_RELEASE);
                 told = true;
@@ -3051,7 +3036,7 @@ int gab_conv_round_trip(gab_conv_plan* p, const float* h_in, float* h_out, gab_s
             GAB_HIP_CHECK(hipStreamSynchronize(s));
         } else {
             for (spins = 0;;) {
-                const hipError_t q = hipEventQuery(p->rt_done_ev);
+                const hipError_t q = hipEventQuery(p->rt->done_ev.get());
                 if (q == hipSuccess) break;
                 (void)hipGetLastError();
                 if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -3095,7 +3080,7 @@ int gab_conv_newest_block(gab_conv_plan* p, float* d_out, gab_stream_t stream) {
         if (!p->fused || p->fresh) return gab::bad_arg("gab_conv_newest_block: a 512-sample plan that has taken at least one buffer");
         if (p->eng_running) return gab::bad_arg("gab_conv_newest_block: the plan's engine is running");
         conv_newest_block_kernel<<<dim3(p->pairs), dim3(256), 0, gab::as_stream(stream)>>>(
-            p->hist, d_out, p->tracks, (p->head + gab::kSlots - 1) & (gab::kSlots - 1));
+            p->hist.get(), d_out, p->tracks, (p->head + gab::kSlots - 1) & (gab::kSlots - 1));
         return gab::launch_status("conv_newest_block_kernel");
     });
 }
@@ -3109,24 +3094,24 @@ int gab_conv_engine_rings(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
         if (p->eng_running) return gab::bad_arg("gab_conv_engine_rings: the plan's engine is running");
         if (ring_buffers < 3 || ring_buffers > 4096) return gab::bad_arg("gab_conv_engine_rings: ring_buffers must be 3..4096");
         const size_t n = (size_t)p->tracks * p->bufsize;
-        if (!p->eng_own_stream) {                     // the launch's own stream (see gab_conv_plan): made here, ahead of any timed start
-            int lo = 0, hi = 0;                       // (numerically lower = higher priority)
-            GAB_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            GAB_HIP_CHECK(hipStreamCreateWithPriority(&p->eng_own_stream, hipStreamNonBlocking, hi));
-            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->eng_ev, hipEventDisableTiming));
-        }
-        if (p->eng_ring != ring_buffers) {
-            if (p->eng_in) { (void)hipFree(p->eng_in); p->eng_in = nullptr; }
-            if (p->eng_out) { (void)hipFree(p->eng_out); p->eng_out = nullptr; }
-            p->eng_ring = 0;
+        if (!p->eng) p->eng.reset(new ConvEngineState);     // with the launch's own stream: made here, ahead of any timed start
+        ConvEngineState& e = *p->eng;
+        if (e.ring != ring_buffers) {
+            // the old rings go first; an allocation that fails takes the other one of the new pair with it: no rings, ring 0
+            e.in.release();
+            e.out.release();
+            e.ring = 0;
             // ordinary device memory: the launch reads the input ring with system-scope loads and writes the output
             // ring with write-through stores, so what a copy engine writes is seen and what it reads is there
-            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_in), n * 4 * ring_buffers, hipDeviceMallocDefault));
-            GAB_HIP_CHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&p->eng_out), n * 4 * ring_buffers, hipDeviceMallocDefault));
-            p->eng_ring = ring_buffers;
+            gab::DeviceBuf<float> in, out;
+            in.alloc_with_flags(n * ring_buffers, hipDeviceMallocDefault);
+            out.alloc_with_flags(n * ring_buffers, hipDeviceMallocDefault);
+            e.in = std::move(in);
+            e.out = std::move(out);
+            e.ring = ring_buffers;
         }
-        *d_in_ring = p->eng_in;
-        *d_out_ring = p->eng_out;
+        *d_in_ring = e.in.get();
+        *d_out_ring = e.out.get();
         return GAB_OK;
     });
 }
@@ -3164,22 +3149,22 @@ int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
                                  "idle_seconds) before the engine is started").c_str());
         hipStream_t caller = gab::as_stream(stream);
         // the launch goes on the plan's own stream, behind whatever the caller's stream holds now
-        GAB_HIP_CHECK(hipEventRecord(p->eng_ev, caller));
-        GAB_HIP_CHECK(hipStreamWaitEvent(p->eng_own_stream, p->eng_ev, 0));
-        hipStream_t s = p->eng_own_stream;
+        ConvEngineState& e = *p->eng;                   // (gab_conv_engine_rings made it)
+        GAB_HIP_CHECK(hipEventRecord(e.ev.get(), caller));
+        GAB_HIP_CHECK(hipStreamWaitEvent(e.own_stream.get(), e.ev.get(), 0));
+        hipStream_t s = e.own_stream.get();
         const size_t prog_words = 2 * (size_t)(p->tracks / 4) + 64;        // + the started count and the relay word, a line of their own each
-        if (!p->eng_done) GAB_HIP_CHECK(hipMalloc(&p->eng_done, prog_words * sizeof(unsigned)));
-        if (!p->eng_words) {
-            GAB_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p->eng_words), 64 * sizeof(unsigned), hipHostMallocDefault));
-        }
-        for (int i = 0; i < 64; ++i) p->eng_words[i] = 0;
+        if (!e.started) e.started.reset(new ConvEngineState::Started(prog_words));
+        unsigned* const done = e.started->done.get();
+        unsigned* const words = e.started->words.get();
+        for (int i = 0; i < 64; ++i) words[i] = 0;
         p->order_after_reset(s);
-        GAB_HIP_CHECK(hipMemsetAsync(p->eng_done, 0, prog_words * sizeof(unsigned), s));
-        gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
-        gab::ConvEngine eng{p->eng_words, p->eng_done + prog_words - 1, p->eng_done, p->eng_words + 16, p->eng_words + 32, ring_buffers, 1,
-                            p->eng_done + prog_words - 33, p->eng_words + 48, (unsigned long long)(p->eng_idle_seconds * 1e8)};
+        GAB_HIP_CHECK(hipMemsetAsync(done, 0, prog_words * sizeof(unsigned), s));
+        gab::ConvSplit sp{p->pmA2.get(), p->pmF.get(), p->carry.get() GAB_SPLIT_DEBUG_ARG};
+        gab::ConvEngine eng{words, done + prog_words - 1, done, words + 16, words + 32, ring_buffers, 1,
+                            done + prog_words - 33, words + 48, (unsigned long long)(p->eng_idle_seconds * 1e8)};
         gab::conv_split_engine12_kernel<<<dim3(p->tracks / 4), dim3(gab::kB12Threads), 0, s>>>(
-            p->eng_in, p->eng_out, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, eng);
+            e.in.get(), e.out.get(), p->hist.get(), p->pmA.get(), sp, p->tw, p->tracks, p->head, eng);
         int rc = gab::launch_status("conv_split_engine12_kernel");
         if (rc) return rc;
         p->eng_running = true;
@@ -3187,8 +3172,8 @@ int gab_conv_engine_start(gab_conv_plan* p, int ring_buffers, float** d_in_ring,
         p->eng_seen_completed = 0;
         p->eng_stream = s;
         p->fresh = false;
-        *d_in_ring = p->eng_in;
-        *d_out_ring = p->eng_out;
+        *d_in_ring = e.in.get();
+        *d_out_ring = e.out.get();
         return GAB_OK;
     });
 }
@@ -3200,7 +3185,7 @@ int gab_conv_engine_submit(gab_conv_plan* p, int n_more, int flush) {
     if (p->eng_published + (unsigned)n_more >= 0x40000000u) return gab::bad_arg("gab_conv_engine_submit: more than 2^30 buffers in one launch (stop and start again)");
     p->eng_published += (unsigned)n_more;
     // the doorbell: buffers published so far; bit 30 = finish them without waiting for more (one store: count and rung together)
-    __atomic_store_n(&p->eng_words[0], p->eng_published | (flush ? 0x40000000u : 0u), __ATOMIC_RELEASE);
+    __atomic_store_n(&p->eng->started->words[0], p->eng_published | (flush ? 0x40000000u : 0u), __ATOMIC_RELEASE);
     return GAB_OK;
 }
 
@@ -3220,7 +3205,7 @@ int gab_conv_engine_running(gab_conv_plan* p, int* running) {
 int gab_conv_engine_wait(gab_conv_plan* p, int count, double timeout_seconds) {
     if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_wait")) return rc;
     return gab::guarded([&]() -> int {
-        if (!p || !p->eng_words) return gab::bad_arg("gab_conv_engine_wait: no engine");
+        if (!p || !p->eng || !p->eng->started) return gab::bad_arg("gab_conv_engine_wait: no engine");
         if (count < 0 || (unsigned)count > p->eng_published) return gab::bad_arg("gab_conv_engine_wait: count exceeds what has been published");
         const auto t0 = std::chrono::steady_clock::now();
         unsigned spins = 0;
@@ -3228,13 +3213,13 @@ int gab_conv_engine_wait(gab_conv_plan* p, int count, double timeout_seconds) {
         for (;;) {
             gab_conv_engine_completed(p, &done);
             if (done >= count) return GAB_OK;
-            if (p->eng_words[32]) {
+            if (p->eng->started->words[32]) {
                 gab::set_last_error("gab_conv_engine_wait: the engine gave up waiting for the doorbell");
                 return GAB_ERR_RUNTIME;
             }
             if ((++spins & 0xfffu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_seconds) {
                 // was the launch ever there?  (the first / the last workgroup to begin say so: [48], [49])
-                const unsigned first = __atomic_load_n(&p->eng_words[48], __ATOMIC_ACQUIRE), all = __atomic_load_n(&p->eng_words[49], __ATOMIC_ACQUIRE);
+                const unsigned first = __atomic_load_n(&p->eng->started->words[48], __ATOMIC_ACQUIRE), all = __atomic_load_n(&p->eng->started->words[49], __ATOMIC_ACQUIRE);
                 int on_device = 0;
                 (void)gab_conv_engine_running(p, &on_device);
                 std::string where;
@@ -3258,8 +3243,8 @@ int gab_conv_engine_wait(gab_conv_plan* p, int count, double timeout_seconds) {
 
 int gab_conv_engine_completed(gab_conv_plan* p, int* completed) {
     if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_completed")) return rc;
-    if (!p || !completed || !p->eng_words) return gab::bad_arg("gab_conv_engine_completed: no engine");
-    const unsigned c = __atomic_load_n(&p->eng_words[16], __ATOMIC_ACQUIRE);      // two writers may cross: keep the maximum seen
+    if (!p || !completed || !p->eng || !p->eng->started) return gab::bad_arg("gab_conv_engine_completed: no engine");
+    const unsigned c = __atomic_load_n(&p->eng->started->words[16], __ATOMIC_ACQUIRE);      // two writers may cross: keep the maximum seen
     if ((int)(c - p->eng_seen_completed) > 0) p->eng_seen_completed = c;
     *completed = (int)p->eng_seen_completed;
     return GAB_OK;
@@ -3271,7 +3256,7 @@ int gab_conv_engine_feed(gab_conv_plan* p, int n_buffers, int ahead) {
         if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_feed: no running engine");
         // a buffer is reported back once FIVE later ones are published (asked for a period early, delivered a period late,
         // its count taken a period after that and passed on by workgroup 0): fewer than six in flight and nothing moves
-        if (n_buffers < 0 || ahead < 6 || ahead >= p->eng_ring)
+        if (n_buffers < 0 || ahead < 6 || ahead >= p->eng->ring)
             return gab::bad_arg("gab_conv_engine_feed: n_buffers >= 0 and 6 <= ahead < ring_buffers (a buffer is reported back once five later ones are published)");
         const unsigned first = p->eng_published, last = first + (unsigned)n_buffers;
         const auto t0 = std::chrono::steady_clock::now();
@@ -3285,9 +3270,9 @@ int gab_conv_engine_feed(gab_conv_plan* p, int n_buffers, int ahead) {
                 gab::set_last_error("gab_conv_engine_feed: the engine stopped consuming");
                 return GAB_ERR_RUNTIME;
             }
-            if (p->eng_words[32]) break;
+            if (p->eng->started->words[32]) break;
         }
-        if (p->eng_words[32]) {
+        if (p->eng->started->words[32]) {
             gab::set_last_error("gab_conv_engine_feed: the engine gave up waiting for the doorbell");
             return GAB_ERR_RUNTIME;
         }
@@ -3315,17 +3300,17 @@ int gab_conv_engine_stop(gab_conv_plan* p) {
     if (int rc = gab_conv_refuse_fdl(p, "gab_conv_engine_stop")) return rc;
     return gab::guarded([&]() -> int {
         if (!p || !p->eng_running) return gab::bad_arg("gab_conv_engine_stop: no running engine");
-        __atomic_store_n(&p->eng_words[0], p->eng_published | 0x80000000u, __ATOMIC_RELEASE);
+        __atomic_store_n(&p->eng->started->words[0], p->eng_published | 0x80000000u, __ATOMIC_RELEASE);
         GAB_HIP_CHECK(hipStreamSynchronize(p->eng_stream));
         p->eng_running = false;
-        if (p->eng_words[32]) {
+        if (p->eng->started->words[32]) {
             // The engine had given up (the doorbell silent for the idle limit): it ended its burst with what it had taken, and
             // buffers published behind that (a pipelined burst without the flush rung leaves the last one waiting for its
             // successor) were never consumed.  History ring, carry ring and head go on from what WAS consumed: every inverse
             // wave's own count, read now that the launch is over — not from what was published.
             const size_t waves = 2 * (size_t)(p->tracks / 4);
             std::vector<unsigned> prog(waves);
-            GAB_HIP_CHECK(hipMemcpy(prog.data(), p->eng_done, waves * sizeof(unsigned), hipMemcpyDeviceToHost));
+            GAB_HIP_CHECK(hipMemcpy(prog.data(), p->eng->started->done.get(), waves * sizeof(unsigned), hipMemcpyDeviceToHost));
             unsigned consumed = p->eng_published;
             for (unsigned v : prog) consumed = std::min(consumed, v);
             p->eng_seen_completed = consumed;
@@ -3364,17 +3349,16 @@ int gab_conv_engine_round_trip(gab_conv_plan* p, const float* h_in, float* h_out
         gab_conv_engine_completed(p, &done);
         if ((unsigned)done != p->eng_published)
             return gab::bad_arg("gab_conv_engine_round_trip: buffers are still in flight (ONE buffer at a time: wait for what has been published)");
-        if (!p->eng_copy_stream) {
-            GAB_HIP_CHECK(hipStreamCreateWithFlags(&p->eng_copy_stream, hipStreamNonBlocking));
-            GAB_HIP_CHECK(hipEventCreateWithFlags(&p->eng_copy_ev, hipEventDisableTiming));
-        }
+        if (!p->eng->link) p->eng->link.reset(new ConvEngineState::Link);
+        const hipStream_t copy_stream = p->eng->link->copy_stream.get();
+        const hipEvent_t copy_ev = p->eng->link->copy_ev.get();
         const size_t n = (size_t)p->tracks * p->bufsize;
-        const size_t slot = p->eng_published % (unsigned)p->eng_ring;
+        const size_t slot = p->eng_published % (unsigned)p->eng->ring;
         auto spin = [&](const char* what) -> int {          // (an event query: hipStreamSynchronize would yield the thread)
-            GAB_HIP_CHECK(hipEventRecord(p->eng_copy_ev, p->eng_copy_stream));
+            GAB_HIP_CHECK(hipEventRecord(copy_ev, copy_stream));
             const auto t0 = std::chrono::steady_clock::now();
             for (unsigned spins = 0;;) {
-                const hipError_t q = hipEventQuery(p->eng_copy_ev);
+                const hipError_t q = hipEventQuery(copy_ev);
                 if (q == hipSuccess) return GAB_OK;
                 (void)hipGetLastError();
                 if (q != hipErrorNotReady) GAB_HIP_CHECK(q);
@@ -3385,11 +3369,11 @@ int gab_conv_engine_round_trip(gab_conv_plan* p, const float* h_in, float* h_out
                 }
             }
         };
-        GAB_HIP_CHECK(hipMemcpyAsync(p->eng_in + slot * n, h_in, n * sizeof(float), hipMemcpyHostToDevice, p->eng_copy_stream));
+        GAB_HIP_CHECK(hipMemcpyAsync(p->eng->in.get() + slot * n, h_in, n * sizeof(float), hipMemcpyHostToDevice, copy_stream));
         if (int rc = spin("the upload")) return rc;
         if (int rc = gab_conv_engine_submit(p, 1, 1)) return rc;
         if (int rc = gab_conv_engine_wait(p, (int)p->eng_published, 5.0)) return rc;
-        GAB_HIP_CHECK(hipMemcpyAsync(h_out, p->eng_out + slot * n, n * sizeof(float), hipMemcpyDeviceToHost, p->eng_copy_stream));
+        GAB_HIP_CHECK(hipMemcpyAsync(h_out, p->eng->out.get() + slot * n, n * sizeof(float), hipMemcpyDeviceToHost, copy_stream));
         return spin("the download");
     });
 }
@@ -3402,9 +3386,9 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
         if (p->eng_running) return gab::bad_arg("gab_conv_process_batch: the plan's engine is running and owns its history (gab_conv_engine_stop first)");
         if (n_buffers <= 0) return gab::bad_arg("gab_conv_process_batch: n_buffers must be > 0");
         hipStream_t s = gab::as_stream(stream);
-        if (p->fdl) {
+        if (p->fdl.get()) {
             p->order_after_reset(s);
-            gab::fdl::process_batch(p->fdl, d_in, d_out, n_buffers, s);
+            gab::fdl::process_batch(p->fdl.get(), d_in, d_out, n_buffers, s);
             p->fresh = false;
             return GAB_OK;
         }
@@ -3417,7 +3401,7 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
             // the classic cut's launch: 10.5 instead of 9.3).  A launch boundary puts them back in step for the price of one
             // cold start per chunk (0.03 us per buffer).
             p->order_after_reset(s);                          // both cuts: a batch on another stream than the reset's waits for it
-            gab::ConvSplit sp{p->pmA2, p->pmF, p->carry GAB_SPLIT_DEBUG_ARG};
+            gab::ConvSplit sp{p->pmA2.get(), p->pmF.get(), p->carry.get() GAB_SPLIT_DEBUG_ARG};
             const size_t step = (size_t)p->tracks * p->bufsize;
             for (int done = 0; done < n_buffers;) {
                 const int n = (int)std::min<size_t>(gab::kBatchChunk, (size_t)(n_buffers - done));
@@ -3426,11 +3410,11 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
                     // the split cut, both roles of a duo in one resident workgroup: same bits as n split launches.
                     // Twelve waves, three per SIMD (round 6)
                     gab::conv_split_batch12_kernel<<<dim3(p->tracks / 4), dim3(gab::kB12Threads), 0, s>>>(
-                        d_in + done * step, d_out + done * step, p->hist, p->pmA, sp, p->tw, p->tracks, p->head, n);
+                        d_in + done * step, d_out + done * step, p->hist.get(), p->pmA.get(), sp, p->tw, p->tracks, p->head, n);
                     rc = gab::launch_status("conv_split_batch12_kernel");
                 } else {
                     gab::conv_batch_kernel<<<dim3(p->pairs), dim3(gab::kThreads), 0, s>>>(
-                        d_in + done * step, d_out + done * step, p->hist, p->pmA, p->pmB, p->tw, p->tracks, p->head, n);
+                        d_in + done * step, d_out + done * step, p->hist.get(), p->pmA.get(), p->pmB.get(), p->tw, p->tracks, p->head, n);
                     rc = gab::launch_status("conv_batch_kernel");
                 }
                 if (rc) return rc;
@@ -3452,8 +3436,8 @@ int gab_conv_process_batch(gab_conv_plan* p, const float* d_in, float* d_out, in
 
 int gab_conv_state_bytes(const gab_conv_plan* p, size_t* spectra, size_t* history) {
     if (!p) return gab::bad_arg("gab_conv_state_bytes: null plan");
-    if (p->fdl) {                           // spectra: the taps' spectra; history: the delay line and the previous block
-        gab::fdl::state_bytes(p->fdl, spectra, history);
+    if (p->fdl.get()) {                           // spectra: the taps' spectra; history: the delay line and the previous block
+        gab::fdl::state_bytes(p->fdl.get(), spectra, history);
         return GAB_OK;
     }
     // everything resident for the plan: a plan that can use the split cut holds both sets of spectra
@@ -3467,11 +3451,11 @@ int gab_conv_state_bytes(const gab_conv_plan* p, size_t* spectra, size_t* histor
 #ifdef GAB_ABLATE
 // diagnostic builds only: how many words of the round trip's staging buffer are NOT the sentinel (between calls: none)
 int gab_debug_rt_stage_dirty(gab_conv_plan* p, long long* first_index) {
-    if (!p || !p->rt_stage) return -1;
+    if (!p || !p->rt) return -1;
     (void)hipDeviceSynchronize();
     const size_t n = 2 * (size_t)p->tracks * p->bufsize;          // both staging buffers
     std::vector<unsigned> h(n);
-    if (hipMemcpy(h.data(), p->rt_stage, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(h.data(), p->rt->stage.get(), n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     int dirty = 0;
     if (first_index) *first_index = -1;
     for (size_t i = 0; i < n; ++i)

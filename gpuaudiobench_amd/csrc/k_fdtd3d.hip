@@ -29,6 +29,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <mutex>
 #include <utility>
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "gab_common.hpp"
+#include "gab_plan.hpp"
 
 namespace gab {
 namespace {
@@ -915,11 +917,31 @@ struct FdtdGraphKey {
     }
 };
 
+// The four arrays of one ping-pong side; view() is the plain struct the kernels take by value.
+struct FdtdFieldBufs {
+    gab::DeviceBuf<float> p, vx, vy, vz;
+    void alloc(size_t np, size_t nvx, size_t nvy, size_t nvz) {
+        p.alloc(np);
+        vx.alloc(nvx);
+        vy.alloc(nvy);
+        vz.alloc(nvz);
+    }
+    gab::Fields view() const { return gab::Fields{p.get(), vx.get(), vy.get(), vz.get()}; }
+};
+
+// What the LDS-resident form keeps: made whole at its first launch (prepare_resident), or not at all.
+struct FdtdResidentBufs {
+    gab::DeviceBuf<unsigned> xbuf;          // [2 parities][workgroups][4 faces][fr rows][128 granules {pressure, tag}] + the timeout word
+    size_t xbuf_dwords = 0;
+    gab::PinnedBuf<unsigned> timeout_host;  // pinned copy of the timeout word (copied behind every resident launch)
+};
+
 struct gab_fdtd_plan {
     gab_fdtd_params P;
+    FdtdFieldBufs side[2];             // the memory behind cur_real / nxt_real, whichever way round they are
     gab::Fields cur{}, nxt{};          // ping-pong
-    float* inj = nullptr;              // per-sample source sums of the current buffer
-    float* strip = nullptr;            // per-sample receiver values
+    gab::DeviceBuf<float> inj;         // per-sample source sums of the current buffer
+    gab::DeviceBuf<float> strip;       // per-sample receiver values
     int strip_cap = 0;
     size_t np = 0, nvx = 0, nvy = 0, nvz = 0;   // floats ALLOCATED per field (slab + ghosts)
     // z-slab of a decomposed grid: planes [z_begin, z_end) are owned; the pressure array carries one
@@ -929,8 +951,8 @@ struct gab_fdtd_plan {
     gab::Fields cur_real{}, nxt_real{};
     // track-dependent source / receiver cells (0 tracks: the shared cells of P)
     int pos_tracks = 0, pos_groups = 0;
-    long long *d_pos_rcv = nullptr, *d_pos_group_cell = nullptr;
-    int *d_pos_group_start = nullptr, *d_pos_group_tracks = nullptr;
+    gab::DeviceBuf<long long> d_pos_rcv, d_pos_group_cell;
+    gab::DeviceBuf<int> d_pos_group_start, d_pos_group_tracks;
     bool use_graphs = true;
     bool lds_tiles = true;    // rows wide enough to fill a 32-lane row of the LDS-halo kernel (GAB_FDTD_LDS=0: off)
     bool sample_tiles = true; // small rooms: one launch per sample, S steps in a tile (GAB_FDTD_TILE=0: off)
@@ -939,41 +961,20 @@ struct gab_fdtd_plan {
     gab::ResidentGeom rgeom{};
     int res_rpt = 0;                    // rows per thread slot (0: the grid does not take the resident kernel)
     size_t res_lds_bytes = 0;
-    unsigned* res_xbuf = nullptr;       // [2 parities][workgroups][4 faces][fr rows][128 granules {pressure, tag}] + the timeout word
-    size_t res_xbuf_dwords = 0;
+    std::unique_ptr<FdtdResidentBufs> res;
     unsigned res_tag = 0;               // steps the resident kernel has run on this plan: the exchange tags go on from here
-    unsigned* res_timeout_host = nullptr;   // pinned copy of the timeout word (copied behind every resident launch)
     bool form_step = false;             // gab_fdtd_set_form(GAB_FDTD_FORM_STEP): never the resident kernel
-    hipStream_t capture_stream = nullptr;   // capture target (the caller's stream may be the null stream)
+    gab::Stream capture_stream;         // capture target (the caller's stream may be the null stream)
     std::vector<std::pair<FdtdGraphKey, hipGraphExec_t>> graphs;   // small LRU, newest last
+
+    void drop_graphs() {                // (the one resource here without an owner type: it is used nowhere else)
+        for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+        graphs.clear();
+    }
+    ~gab_fdtd_plan() { drop_graphs(); }
 };
 
 namespace {
-
-void free_fields(gab::Fields& f) {
-    if (f.p) (void)hipFree(f.p);
-    if (f.vx) (void)hipFree(f.vx);
-    if (f.vy) (void)hipFree(f.vy);
-    if (f.vz) (void)hipFree(f.vz);
-    f = gab::Fields{};
-}
-
-void free_track_positions(gab_fdtd_plan* f) {
-    if (f->d_pos_rcv) (void)hipFree(f->d_pos_rcv);
-    if (f->d_pos_group_cell) (void)hipFree(f->d_pos_group_cell);
-    if (f->d_pos_group_start) (void)hipFree(f->d_pos_group_start);
-    if (f->d_pos_group_tracks) (void)hipFree(f->d_pos_group_tracks);
-    f->d_pos_rcv = f->d_pos_group_cell = nullptr;
-    f->d_pos_group_start = f->d_pos_group_tracks = nullptr;
-    f->pos_tracks = f->pos_groups = 0;
-}
-
-void alloc_fields(gab::Fields& f, const gab_fdtd_plan& pl) {
-    GAB_HIP_CHECK(hipMalloc(&f.p, pl.np * sizeof(float)));
-    GAB_HIP_CHECK(hipMalloc(&f.vx, pl.nvx * sizeof(float)));
-    GAB_HIP_CHECK(hipMalloc(&f.vy, pl.nvy * sizeof(float)));
-    GAB_HIP_CHECK(hipMalloc(&f.vz, pl.nvz * sizeof(float)));
-}
 
 void zero_fields(gab::Fields& f, const gab_fdtd_plan& pl, hipStream_t s) {
     GAB_HIP_CHECK(hipMemsetAsync(f.p, 0, pl.np * sizeof(float), s));
@@ -1063,7 +1064,6 @@ void choose_resident_geometry(gab_fdtd_plan* f) {
 bool prepare_resident(gab_fdtd_plan* f, hipStream_t s) {
     auto give_up = [&]() {
         (void)hipGetLastError();
-        if (f->res_xbuf) { (void)hipFree(f->res_xbuf); f->res_xbuf = nullptr; }
         f->res_rpt = 0;
         return false;
     };
@@ -1077,12 +1077,15 @@ bool prepare_resident(gab_fdtd_plan* f, hipStream_t s) {
         return give_up();
     const size_t wgs = (size_t)f->rgeom.gy * f->rgeom.gz;
     if (per_cu < 1 || wgs > (size_t)per_cu * (size_t)cus) return give_up();
-    f->res_xbuf_dwords = (size_t)2 * wgs * 4 * f->rgeom.fr * gab::kResRowDwords;
-    if (hipMalloc(&f->res_xbuf, sizeof(unsigned) * (f->res_xbuf_dwords + 4)) != hipSuccess) return give_up();
-    if (hipMemsetAsync(f->res_xbuf, 0, sizeof(unsigned) * (f->res_xbuf_dwords + 4), s) != hipSuccess) return give_up();   // tag 0 = never written
-    if (!f->res_timeout_host) {
-        if (hipHostMalloc(&f->res_timeout_host, sizeof(unsigned), hipHostMallocDefault) != hipSuccess) return give_up();
-        *f->res_timeout_host = 0;
+    try {
+        std::unique_ptr<FdtdResidentBufs> r(new FdtdResidentBufs);
+        r->xbuf_dwords = (size_t)2 * wgs * 4 * f->rgeom.fr * gab::kResRowDwords;
+        r->xbuf.alloc(r->xbuf_dwords + 4);
+        GAB_HIP_CHECK(hipMemsetAsync(r->xbuf.get(), 0, sizeof(unsigned) * r->xbuf.size(), s));   // tag 0 = never written
+        r->timeout_host.alloc(1);
+        f->res = std::move(r);
+    } catch (const std::exception&) {
+        return give_up();
     }
     return true;
 }
@@ -1090,15 +1093,16 @@ bool prepare_resident(gab_fdtd_plan* f, hipStream_t s) {
 // A resident launch that gave up waiting left its word in the pinned copy (it travels behind every resident launch on
 // the launch's stream).  Consumes it: the plan takes the step kernels from now on.  0, or 1 + the step it stopped at.
 unsigned take_resident_timeout(gab_fdtd_plan* f) {
-    if (!f->res_timeout_host || *f->res_timeout_host == 0) return 0;
-    const unsigned at = *f->res_timeout_host;
-    *f->res_timeout_host = 0;
+    if (!f->res || f->res->timeout_host[0] == 0) return 0;
+    const unsigned at = f->res->timeout_host[0];
+    f->res->timeout_host[0] = 0;
     f->resident = false;
     return at;
 }
 
 int create_slab(gab_fdtd_plan** out, const gab_fdtd_params* params, int z_begin, int z_end, const char* who) {
     if (!out || !params) return gab::bad_arg((std::string(who) + ": null pointer").c_str());
+    *out = nullptr;
     if (int rc = gab::refuse_unsupported_runtime_mode(who)) return rc;
     const gab_fdtd_params& P = *params;
     if (P.nx < 3 || P.ny < 3 || P.nz < 3) return gab::bad_arg((std::string(who) + ": grid too small").c_str());
@@ -1110,7 +1114,7 @@ int create_slab(gab_fdtd_plan** out, const gab_fdtd_params* params, int z_begin,
     if (P.steps_per_sample < 1) return gab::bad_arg((std::string(who) + ": steps_per_sample must be >= 1").c_str());
     if (z_begin < 0 || z_end > P.nz || z_end - z_begin < 1)
         return gab::bad_arg((std::string(who) + ": slab must be a non-empty range inside [0, nz)").c_str());
-    auto* f = new gab_fdtd_plan;
+    std::unique_ptr<gab_fdtd_plan> f(new gab_fdtd_plan);
     f->P = P;
     f->z_begin = z_begin;
     f->z_end = z_end;
@@ -1129,20 +1133,16 @@ int create_slab(gab_fdtd_plan** out, const gab_fdtd_params* params, int z_begin,
     f->nvx = (size_t)(P.nx + 4) * P.ny * nzl + 4;    // padded pitch, see file header
     f->nvy = (size_t)P.nx * (P.ny + 1) * nzl;
     f->nvz = (size_t)P.nx * P.ny * (nzl + 1);
-    try {
-        alloc_fields(f->cur_real, *f);
-        alloc_fields(f->nxt_real, *f);
-    } catch (...) {
-        gab_fdtd_destroy(f);
-        throw;
-    }
+    for (FdtdFieldBufs& b : f->side) b.alloc(f->np, f->nvx, f->nvy, f->nvz);
+    f->cur_real = f->side[0].view();
+    f->nxt_real = f->side[1].view();
     f->cur = virtual_base(f->cur_real, *f);
     f->nxt = virtual_base(f->nxt_real, *f);
-    choose_resident_geometry(f);
-    *out = f;
-    int rc = gab_fdtd_reset(f, nullptr);
+    choose_resident_geometry(f.get());
+    int rc = gab_fdtd_reset(f.get(), nullptr);
     if (rc) return rc;
     GAB_HIP_CHECK(hipStreamSynchronize(nullptr));
+    *out = f.release();                 // whole, zeroed and at rest: only now the caller's
     return GAB_OK;
 }
 
@@ -1208,14 +1208,13 @@ void launch_step(const gab_fdtd_plan* f, hipStream_t q, const gab::Fields& cur, 
 void ensure_strips(gab_fdtd_plan* f, int bufsize, hipStream_t s) {
     if (f->strip_cap >= bufsize) return;
     GAB_HIP_CHECK(hipStreamSynchronize(s));
-    for (auto& c : f->graphs) (void)hipGraphExecDestroy(c.second);   // they point at the old strips
-    f->graphs.clear();
-    if (f->inj) (void)hipFree(f->inj);
-    if (f->strip) (void)hipFree(f->strip);
-    f->inj = f->strip = nullptr;
-    GAB_HIP_CHECK(hipMalloc(&f->inj, sizeof(float) * bufsize));
-    GAB_HIP_CHECK(hipMalloc(&f->strip, sizeof(float) * bufsize));
-    GAB_HIP_CHECK(hipMemsetAsync(f->strip, 0, sizeof(float) * bufsize, s));
+    f->drop_graphs();                   // they point at the old strips
+    f->strip_cap = 0;
+    f->inj.release();
+    f->strip.release();
+    f->inj.alloc((size_t)bufsize);
+    f->strip.alloc((size_t)bufsize);
+    GAB_HIP_CHECK(hipMemsetAsync(f->strip.get(), 0, sizeof(float) * bufsize, s));
     f->strip_cap = bufsize;
 }
 
@@ -1254,16 +1253,7 @@ int gab_fdtd_destroy(gab_fdtd_plan* f) {
     if (!f) return GAB_OK;
     (void)hipDeviceSynchronize();
     const unsigned gave_up_at = take_resident_timeout(f);     // a last call nobody asked about
-    for (auto& g : f->graphs) (void)hipGraphExecDestroy(g.second);
-    if (f->capture_stream) (void)hipStreamDestroy(f->capture_stream);
-    free_fields(f->cur_real);
-    free_fields(f->nxt_real);
-    if (f->inj) (void)hipFree(f->inj);
-    if (f->strip) (void)hipFree(f->strip);
-    if (f->res_xbuf) (void)hipFree(f->res_xbuf);
-    if (f->res_timeout_host) (void)hipHostFree(f->res_timeout_host);
-    free_track_positions(f);
-    delete f;
+    delete f;                                                 // (the graph executables first, then every member's own)
     if (gave_up_at) {
         gab::set_last_error("gab_fdtd_destroy: the plan's last LDS-resident launch had timed out at step " + std::to_string(gave_up_at - 1) +
                             " waiting for a neighbour workgroup; that call's output was NaN");
@@ -1356,7 +1346,7 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &cap);
         bool resident = f->resident && !f->form_step && f->res_rpt > 0 && !f->pos_tracks && cap == hipStreamCaptureStatusNone;
-        if (resident && !f->res_xbuf) resident = prepare_resident(f, s);     // false: this device cannot hold the grid at once
+        if (resident && !f->res) resident = prepare_resident(f, s);     // false: this device cannot hold the grid at once
         const bool by_sample = f->sample_tiles && !f->pos_tracks && P.steps_per_sample == 3 && f->z_begin == 0 &&
                                f->z_end == P.nz && P.nx <= 56 && P.ny <= 56 && P.nz <= 56;
         // enqueue the whole chain on `q`, walking local copies of the ping-pong pair
@@ -1366,8 +1356,8 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
             if (f->pos_tracks) {
                 auto io = [&](float* p, int extract, int inject) {
                     gab::fdtd_track_io_kernel<<<1, 256, 0, q>>>(p, d_in, d_out, tracks, bufsize, extract, inject,
-                                                               f->d_pos_rcv, f->pos_groups, f->d_pos_group_cell,
-                                                               f->d_pos_group_start, f->d_pos_group_tracks);
+                                                               f->d_pos_rcv.get(), f->pos_groups, f->d_pos_group_cell.get(),
+                                                               f->d_pos_group_start.get(), f->d_pos_group_tracks.get());
                 };
                 io(cur.p, -1, first_sample);
                 for (int smp = first_sample; smp < last; ++smp) {
@@ -1379,27 +1369,27 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
                 }
                 return;
             }
-            gab::fdtd_source_sums_kernel<<<(n_samples + 127) / 128, 128, 0, q>>>(d_in, f->inj, tracks, bufsize,
+            gab::fdtd_source_sums_kernel<<<(n_samples + 127) / 128, 128, 0, q>>>(d_in, f->inj.get(), tracks, bufsize,
                                                                                first_sample, n_samples);
             // the first sample's source goes straight into the current pressure grid; later
             // ones are folded into the step that precedes them
-            gab::fdtd_add_source_kernel<<<1, 64, 0, q>>>(cur.p, src, f->inj, first_sample);
+            gab::fdtd_add_source_kernel<<<1, 64, 0, q>>>(cur.p, src, f->inj.get(), first_sample);
             if (resident) {
                 // the whole buffer in ONE launch, the room resident in LDS (fields updated in place in `cur`)
                 const gab::Grid g{P.nx, P.ny, P.nz, P.nx + 4, 0};
                 const size_t rcv = P.receiver_z * sxy + (size_t)P.receiver_y * P.nx + P.receiver_x;
                 const unsigned wgs = (unsigned)(f->rgeom.gy * f->rgeom.gz);
-                unsigned* const tmo = f->res_xbuf + f->res_xbuf_dwords;
+                unsigned* const tmo = f->res->xbuf.get() + f->res->xbuf_dwords;
 #define GAB_RESIDENT_LAUNCH(RPT)                                                                                   \
     gab::fdtd_resident_kernel<RPT><<<dim3(wgs), dim3(gab::kResThreads), f->res_lds_bytes, q>>>(                    \
-        cur, g, f->rgeom, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, 1.0f - P.absorption_coeff, src, rcv, f->inj, f->strip, \
-        first_sample, n_samples, P.steps_per_sample, f->res_xbuf, f->res_tag, tmo)
+        cur, g, f->rgeom, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, 1.0f - P.absorption_coeff, src, rcv, f->inj.get(), f->strip.get(), \
+        first_sample, n_samples, P.steps_per_sample, f->res->xbuf.get(), f->res_tag, tmo)
                 g_resident_chain.run(q, [&]() { if (f->res_rpt == 1) GAB_RESIDENT_LAUNCH(1); else GAB_RESIDENT_LAUNCH(2); });
 #undef GAB_RESIDENT_LAUNCH
                 f->res_tag += (unsigned)n_samples * (unsigned)P.steps_per_sample;
                 dim3 bgrid((n_samples + 127) / 128, tracks);
-                gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip, d_out, tracks, bufsize, first_sample,
-                                                                n_samples, tmo, f->res_timeout_host);
+                gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip.get(), d_out, tracks, bufsize, first_sample,
+                                                                n_samples, tmo, f->res->timeout_host.get());
                 return;
             }
             if (by_sample) {
@@ -1412,25 +1402,25 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
                 for (int smp = first_sample; smp < last; ++smp) {
                     gab::fdtd_sample_tile_kernel<TY, TZ, 3, NT><<<grid, block, 0, q>>>(
                         cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, 1.0f - P.absorption_coeff, src, rcv,
-                        smp + 1 < last ? f->inj + smp + 1 : nullptr, f->strip + smp);
+                        smp + 1 < last ? f->inj.get() + smp + 1 : nullptr, f->strip.get() + smp);
                     std::swap(cur, nxt);
                 }
                 dim3 bgrid((n_samples + 127) / 128, tracks);
-                gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip, d_out, tracks, bufsize, first_sample,
+                gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip.get(), d_out, tracks, bufsize, first_sample,
                                                                 n_samples);
                 return;
             }
             for (int smp = first_sample; smp < last; ++smp) {
                 for (int step = 0; step < P.steps_per_sample; ++step) {
                     const bool closes = step == P.steps_per_sample - 1;
-                    const float* add_next = (closes && smp + 1 < last) ? f->inj + smp + 1 : nullptr;
-                    float* strip_out = closes ? f->strip + smp : nullptr;
+                    const float* add_next = (closes && smp + 1 < last) ? f->inj.get() + smp + 1 : nullptr;
+                    float* strip_out = closes ? f->strip.get() + smp : nullptr;
                     launch_step(f, q, cur, nxt, add_next, strip_out);
                     std::swap(cur, nxt);
                 }
             }
             dim3 bgrid((n_samples + 127) / 128, tracks);
-            gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip, d_out, tracks, bufsize, first_sample,
+            gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip.get(), d_out, tracks, bufsize, first_sample,
                                                             n_samples);
         };
         const long swaps = resident ? 0 : (long)n_samples * (by_sample ? 1 : P.steps_per_sample);
@@ -1449,11 +1439,10 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
                 }
             if (!exec) {
                 hipGraph_t graph = nullptr;
-                if (!f->capture_stream)
-                    GAB_HIP_CHECK(hipStreamCreateWithFlags(&f->capture_stream, hipStreamNonBlocking));
-                GAB_HIP_CHECK(hipStreamBeginCapture(f->capture_stream, hipStreamCaptureModeThreadLocal));
-                enqueue(f->capture_stream, f->cur, f->nxt);
-                GAB_HIP_CHECK(hipStreamEndCapture(f->capture_stream, &graph));
+                if (!f->capture_stream) f->capture_stream.create(hipStreamNonBlocking);
+                GAB_HIP_CHECK(hipStreamBeginCapture(f->capture_stream.get(), hipStreamCaptureModeThreadLocal));
+                enqueue(f->capture_stream.get(), f->cur, f->nxt);
+                GAB_HIP_CHECK(hipStreamEndCapture(f->capture_stream.get(), &graph));
                 GAB_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                 (void)hipGraphDestroy(graph);
                 if (f->graphs.size() >= 4) {
@@ -1493,9 +1482,12 @@ int gab_fdtd_set_track_positions(gab_fdtd_plan* f, const int* src_xyz, const int
             if (!cell(src_xyz + 3 * t, &src[t]) || !cell(rcv_xyz + 3 * t, &rcv[t]))
                 return gab::bad_arg("gab_fdtd_set_track_positions: a position lies outside the grid");
         GAB_HIP_CHECK(hipDeviceSynchronize());
-        for (auto& c : f->graphs) (void)hipGraphExecDestroy(c.second);     // captured for the old cells
-        f->graphs.clear();
-        free_track_positions(f);
+        f->drop_graphs();               // captured for the old cells
+        f->pos_tracks = f->pos_groups = 0;
+        f->d_pos_rcv.release();
+        f->d_pos_group_cell.release();
+        f->d_pos_group_start.release();
+        f->d_pos_group_tracks.release();
         if (tracks == 0) return GAB_OK;
         // tracks that share a source cell, in track order (stable sort by cell)
         std::vector<int> order(tracks);
@@ -1509,14 +1501,14 @@ int gab_fdtd_set_track_positions(gab_fdtd_plan* f, const int* src_xyz, const int
                 gstart.push_back(k);
             }
         gstart.push_back(tracks);
-        auto upload = [](auto** d, const auto& h) {
-            GAB_HIP_CHECK(hipMalloc(d, h.size() * sizeof(h[0])));
-            GAB_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
+        auto upload = [](auto& d, const auto& h) {
+            d.alloc(h.size());
+            GAB_HIP_CHECK(hipMemcpy(d.get(), h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
         };
-        upload(&f->d_pos_rcv, rcv);
-        upload(&f->d_pos_group_cell, gcell);
-        upload(&f->d_pos_group_start, gstart);
-        upload(&f->d_pos_group_tracks, order);
+        upload(f->d_pos_rcv, rcv);
+        upload(f->d_pos_group_cell, gcell);
+        upload(f->d_pos_group_start, gstart);
+        upload(f->d_pos_group_tracks, order);
         f->pos_tracks = tracks;
         f->pos_groups = (int)gcell.size();
         return GAB_OK;
@@ -1537,7 +1529,7 @@ int gab_fdtd_source_sums(gab_fdtd_plan* f, const float* d_in, int tracks, int bu
         if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_fdtd_source_sums: sizes must be > 0");
         hipStream_t s = gab::as_stream(stream);
         ensure_strips(f, bufsize, s);
-        gab::fdtd_source_sums_kernel<<<(bufsize + 127) / 128, 128, 0, s>>>(d_in, f->inj, tracks, bufsize, 0, bufsize);
+        gab::fdtd_source_sums_kernel<<<(bufsize + 127) / 128, 128, 0, s>>>(d_in, f->inj.get(), tracks, bufsize, 0, bufsize);
         return gab::launch_status("fdtd_source_sums_kernel");
     });
 }
@@ -1550,7 +1542,7 @@ int gab_fdtd_inject(gab_fdtd_plan* f, int sample, gab_stream_t stream) {
         if (P.source_z < f->z_begin || P.source_z >= f->z_end) return GAB_OK;       // another slab's cell
         const size_t sxy = (size_t)P.nx * P.ny;
         const size_t src = P.source_z * sxy + (size_t)P.source_y * P.nx + P.source_x;
-        gab::fdtd_add_source_kernel<<<1, 64, 0, gab::as_stream(stream)>>>(f->cur.p, src, f->inj, sample);
+        gab::fdtd_add_source_kernel<<<1, 64, 0, gab::as_stream(stream)>>>(f->cur.p, src, f->inj.get(), sample);
         return gab::launch_status("fdtd_add_source_kernel");
     });
 }
@@ -1559,7 +1551,7 @@ int gab_fdtd_step(gab_fdtd_plan* f, int strip_sample, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!f) return gab::bad_arg("gab_fdtd_step: null plan");
         if (strip_sample >= f->strip_cap) return gab::bad_arg("gab_fdtd_step: strip_sample outside the buffer");
-        float* strip_out = strip_sample >= 0 ? f->strip + strip_sample : nullptr;
+        float* strip_out = strip_sample >= 0 ? f->strip.get() + strip_sample : nullptr;
         launch_step(f, gab::as_stream(stream), f->cur, f->nxt, nullptr, strip_out);
         std::swap(f->cur, f->nxt);
         std::swap(f->cur_real, f->nxt_real);
@@ -1590,14 +1582,14 @@ int gab_fdtd_emit(gab_fdtd_plan* f, float* d_out, int tracks, int bufsize, gab_s
         if (tracks <= 0 || bufsize <= 0 || bufsize > f->strip_cap)
             return gab::bad_arg("gab_fdtd_emit: sizes must be > 0 and within the recorded strip");
         gab::fdtd_broadcast_kernel<<<dim3((bufsize + 127) / 128, tracks), 128, 0, gab::as_stream(stream)>>>(
-            f->strip, d_out, tracks, bufsize, 0, bufsize);
+            f->strip.get(), d_out, tracks, bufsize, 0, bufsize);
         return gab::launch_status("fdtd_broadcast_kernel");
     });
 }
 
 int gab_fdtd_strip(gab_fdtd_plan* f, float** d_strip, int* capacity) {
     if (!f || !d_strip) return gab::bad_arg("gab_fdtd_strip: null pointer");
-    *d_strip = f->strip;
+    *d_strip = f->strip.get();
     if (capacity) *capacity = f->strip_cap;
     return GAB_OK;
 }
@@ -1605,7 +1597,7 @@ int gab_fdtd_strip(gab_fdtd_plan* f, float** d_strip, int* capacity) {
 int gab_fdtd_copy_pressure(gab_fdtd_plan* f, float* d_dst, gab_stream_t stream) {
     return gab::guarded([&]() -> int {
         if (!f || !d_dst) return gab::bad_arg("gab_fdtd_copy_pressure: null pointer");
-        if (f->res_timeout_host && *f->res_timeout_host) {           // left in place: the next process / status / reset consumes it
+        if (f->res && f->res->timeout_host[0]) {           // left in place: the next process / status / reset consumes it
             gab::set_last_error("gab_fdtd_copy_pressure: an LDS-resident launch timed out waiting for a neighbour workgroup; "
                                 "the plan's fields are undefined, reset it");
             return GAB_ERR_RUNTIME;
