@@ -217,6 +217,15 @@ PROTOTYPES = {
     "gab_reverb_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "gab_reverb_row_floats": (_I, [_I, _I]),
     "gab_reverb_gmax": (_F, [_I]),
+    "gab_gate_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_gate_destroy": (_I, [_P]),
+    "gab_gate_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_gate_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_gate_reset": (_I, [_P, _P]),
+    "gab_gate_process": (_I, [_P, _P, _P, _P, _P, _P]),
+    "gab_gate_process_batch": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "gab_gate_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_gate_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

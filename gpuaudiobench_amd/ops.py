@@ -769,7 +769,118 @@ class DynamicsPlan(_Handle):
     launch = _launcher("gab_dyn_process")
 
 
-_REVERB_SPREAD = 4.65      # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)
+def gate_params(open_db, close_db=None, attack_ms=1.0, release_ms=100.0, hold_ms=10.0, range_db=None, duck_db=None,
+                fs=48000.0):
+    """A row (all arguments scalars) or a table [n][7] float32 of GatePlan parameters {open, close, att, rel, g_open,
+    g_closed, hold} from the knobs of a gate; float64, rounded once.  Thresholds go from dB to linear levels; close_db
+    defaults to 3 dB under open_db; a time of 0 ms is a coefficient of 0, else exp(-1 / (ms fs / 1000)), held to the
+    plan's 1 - 2^-20; hold_ms becomes a whole number of samples.  A noise gate: g_open = 1 and g_closed from range_db
+    (<= 0; None: 0, the gate shuts).  duck_db (<= 0) given makes the ducker's row instead: g_open = that depth,
+    g_closed = 1, to be run with the voice as the key."""
+    import numpy as np
+    if duck_db is not None and range_db is not None:
+        raise ValueError("range_db belongs to a gate, duck_db to a ducker: give one")
+    args = [np.asarray(a, np.float64) for a in (open_db, open_db if close_db is None else close_db, attack_ms, release_ms,
+                                                hold_ms, 0.0 if range_db is None else range_db,
+                                                0.0 if duck_db is None else duck_db)]
+    scalar = all(a.ndim == 0 for a in args)
+    open_db, close_db_, att_ms, rel_ms, hold_ms, range_db_, duck_db_ = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    if close_db is None:
+        close_db_ = open_db - 3.0
+    if ((close_db_ > open_db).any() or (att_ms < 0.0).any() or (rel_ms < 0.0).any() or (hold_ms < 0.0).any()
+            or (range_db_ > 0.0).any() or (duck_db_ > 0.0).any() or fs <= 0.0):
+        raise ValueError("needs close_db <= open_db, attack_ms, release_ms, hold_ms >= 0, range_db <= 0, duck_db <= 0, fs > 0")
+    att = np.where(att_ms > 0.0, np.exp(-1.0 / np.where(att_ms > 0.0, att_ms * fs / 1000.0, 1.0)), 0.0)
+    rel = np.where(rel_ms > 0.0, np.exp(-1.0 / np.where(rel_ms > 0.0, rel_ms * fs / 1000.0, 1.0)), 0.0)
+    cap = 1.0 - 2.0 ** -20                                           # the plan's cap on a coefficient: 22 s at 48 kHz
+    one = np.ones_like(open_db)
+    if duck_db is None:
+        g_open, g_closed = one, (0.0 * one if range_db is None else 10.0 ** (range_db_ / 20.0))
+    else:
+        g_open, g_closed = 10.0 ** (duck_db_ / 20.0), one
+    table = np.stack([np.minimum(10.0 ** (open_db / 20.0), 2.0 ** 64), np.minimum(10.0 ** (close_db_ / 20.0), 2.0 ** 64),
+                      np.minimum(att, cap), np.minimum(rel, cap), g_open, g_closed,
+                      np.minimum(np.rint(hold_ms * fs / 1000.0), 2.0 ** 24)], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class GatePlan(_Handle):
+    """gab_gate_plan: a noise gate or ducker per track: a two-state machine with hysteresis (open above `open`, the hold
+    runs down below `close`) and a hold counter, and a linear gain that glides to g_open or g_closed.  Parameters per
+    track {open, close, att, rel, g_open, g_closed, hold} (gate_params makes them from dB and ms); tracks [g link,
+    (g + 1) link) share one detector.  A new plan is pass-through; new parameters are ramped in over the next buffer
+    unless ramp=False (the hold is never ramped)."""
+
+    _destroy = "gab_gate_destroy"
+    FIELDS = ("open", "close", "att", "rel", "g_open", "g_closed", "hold")
+
+    def __init__(self, tracks, bufsize, link=1):
+        self.tracks, self.bufsize, self.link = tracks, bufsize, link
+        self._h = C.c_void_p()
+        check(lib.gab_gate_create(C.byref(self._h), tracks, bufsize, link))
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][7], or [n][7] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n, rest = divmod(table.numel(), len(self.FIELDS))
+        if rest or n == 0:
+            raise ValueError("table must hold whole rows of 7 values")
+        if first_track is None:
+            if n != self.tracks:
+                raise ValueError("table must hold a row per track (or give first_track)")
+            check(lib.gab_gate_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
+        else:
+            check(lib.gab_gate_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
+
+    def reset(self):
+        """Every gate shut at target's g_closed, current := target, a pending ramp dropped."""
+        check(lib.gab_gate_reset(self._h, _stream()))
+
+    def process(self, x, key=None, out=None, act=None):
+        """One buffer, track-major [tracks*bufsize]; out may be x itself.  key: the side chain the detector reads instead
+        of x (may not overlap out).  act: an int32 tensor [tracks] that receives the buffer's count of open samples."""
+        assert x.numel() == self.tracks * self.bufsize
+        out = torch.empty_like(x) if out is None else out
+        return self._run(lib.gab_gate_process, x, key, out, act, 1, ())
+
+    def process_batch(self, xs, key=None, out=None, act=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch; key the same shape, act [n][tracks] int32."""
+        n = _n_buffers(self, xs)
+        out = torch.empty_like(xs) if out is None else out
+        return self._run(lib.gab_gate_process_batch, xs, key, out, act, n, (n,))
+
+    def _run(self, fn, x, key, out, act, n, extra):
+        assert out.numel() == x.numel() and (key is None or key.numel() == x.numel())
+        assert act is None or act.numel() == n * self.tracks
+        check(fn(self._h, _dev(x), None if key is None else _dev(key), _dev(out),
+                 None if act is None else _dev(act, torch.int32), *extra, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][7]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_gate_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return _view(a.value, self.tracks, 7).clone(), _view(b.value, self.tracks, 7).clone()
+
+    def state(self):
+        """Copies of (the gain [tracks] float32, the count [tracks] int32: -1 while closed)."""
+        g, c, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_gate_state(self._h, C.byref(g), C.byref(c), C.byref(n)))
+        return (_view(g.value, self.tracks, 1).clone().view(self.tracks),
+                _view(c.value, self.tracks, 1).clone().view(torch.int32).view(self.tracks))
+
+    def prepare(self, x, out, key=None, act=None, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  All state that changes is on the device; which kernel form runs (steady, or the ramp form when
+        a ramp is pending) is the host's choice at the call and what a capture replays, so capture only with no ramp
+        pending: gab_c_api.h, "Captured calls"."""
+        return (self._h, _dev(x), None if key is None else _dev(key), _dev(out),
+                None if act is None else _dev(act, torch.int32), _stream(stream))
+
+    launch = _launcher("gab_gate_process")
+
+
+_REVERB_SPREAD = 4.65     # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)
 
 
 def _primes_from(lengths):

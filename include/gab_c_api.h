@@ -1012,6 +1012,95 @@ int gab_reverb_state(gab_reverb_plan* plan, float** d_lines, size_t* capacity, u
 int gab_reverb_row_floats(int lines, int outs);
 float gab_reverb_gmax(int lines);
 
+/* ---- gate: a noise gate / ducker per track, a two-state machine with hysteresis and a hold counter, a linear gain
+ * that glides between two levels, ramped parameters, linked detectors and a side chain (additive; the reference has no
+ * gate) ------------------------------------------------------------------------------------------------------------
+ * The block of a channel strip in front of the compressor.  Everything is linear: levels are compared as they are, the
+ * gain is a one-pole glide, and no transcendental of any kind enters, so the device can be restated bit for bit.
+ *   parameters     device, [tracks][7] float32 (GAB_GATE_FIELDS):
+ *                    0 open      linear level above which the gate opens         finite, 0 <= open <= 2^64
+ *                    1 close     linear level below which the hold runs down     0 <= close <= open of the same row
+ *                    2 att       one-pole coefficient while open                 0 <= att <= 1 - 2^-20
+ *                    3 rel       one-pole coefficient while closed               0 <= rel <= 1 - 2^-20
+ *                    4 g_open    linear gain the track glides to while open      0 <= g_open <= 256
+ *                    5 g_closed  linear gain while closed                        0 <= g_closed <= 256
+ *                    6 hold      samples the gate stays open below close         an integer value, 0 <= hold <= 2^24
+ *                  A noise gate is g_open = 1, g_closed = the range (0: shut); a ducker is g_open = the depth,
+ *                  g_closed = 1, with the voice as the key: there is no mode switch.  The plan carries two tables,
+ *                  `current` and `target`; a new plan has {0, 0, 0, 0, 1, 1, 0} in both on every track, a gain of 1
+ *                  and a count of -1: pass-through bit for bit, for every sample, finite or not.
+ *     set_params(ramp = 1)  target := the new table, current stays.  On the next processed buffer fields 0 to 5 of every
+ *                  track are p[s] = fmaf(target - current, r[s], current), r[s] = (s + 1) / bufsize (the delay plan's
+ *                  table: float64 on the host, rounded once; target - current rounded once); after that buffer
+ *                  current := target by a copy.  Field 6 is not ramped: that buffer takes target's hold from its first
+ *                  sample, as every buffer does.  Two sets before a buffer: the ramp still starts from current.
+ *     set_params(ramp = 0)  current := target := the new table, at once.
+ *     set_params_tracks     the same for rows [first_track, first_track + n_tracks), d_params [n_tracks][7]; the other
+ *                  rows keep their current and target.
+ *                  The values are checked on the device first, against the column `admitted` above (close against
+ *                  the open of its own row in d_params).  A violation: GAB_ERR_INVALID_ARG naming the first (track,
+ *                  field) in index order; the plan keeps what it had, a pending ramp included.  Both calls are
+ *                  synchronous with respect to `stream` and take effect with the next buffer.
+ *                  Why att and rel stop at 1 - 2^-20 (the dynamics plan's argument): a ramped value is the rounding of
+ *                  current + fl(target - current) r with 0 < r <= 1.  fl(target - current) is off by at most 2^-25,
+ *                  the fmaf's rounding of a value below 1 by at most 2^-25 more, so a ramped coefficient can land
+ *                  above the larger of its two ends, but by no more than 2^-24: it stays below 1 - 2^-20 + 2^-24 < 1,
+ *                  and the glide below stays a convex combination of the gain and its goal.  (open, close, g_open and
+ *                  g_closed cannot become negative: for ends that are both >= 0, fl(target - current) lies between
+ *                  -current and target by the monotonicity of rounding.)  In the same way a ramped close may land a
+ *                  rounding above the ramped open of its sample.  That is harmless: the order of the two tests below
+ *                  decides, a > open first.
+ *     reset        the count -1 (closed) and the gain target's g_closed on every track, so that a gate starts shut
+ *                  and does not leak one release tail; current := target, a pending ramp dropped.
+ *     params       the plan's own two tables, for inspection.
+ *     state        the gain ([tracks] float32) and the count ([tracks] int32), for inspection.
+ *   create         tracks >= 1, bufsize >= 1, link a power of two in 1..64 with tracks % link == 0: tracks [g link,
+ *                  (g + 1) link) share one detector and nothing else; every track keeps its own row, its own gain and
+ *                  its own count.  Arguments are checked before any device call.
+ *   process        one buffer.  d_in and d_out track-major [t*B + s]; d_out == d_in is allowed (no other overlap).
+ *                  d_key is null or a block of the same shape that does not overlap d_out (refused): the side chain,
+ *                  which the detector reads instead of d_in.  d_act is null or [tracks] int32: per track the number of
+ *                  samples of the buffer on which the gate was open (the gate's LED).  Any bufsize, any alignment, any
+ *                  track count: the same bits.
+ *   process_batch  n_buffers buffers back to back in one launch: d_in, d_key, d_out [n][T*B], d_act [n][T]; a pending
+ *                  ramp runs through the first of them; same bits as n calls of process.  process and process_batch
+ *                  allocate nothing and wait for nothing; the gain and the count are device state.
+ * The bits of one sample.  On a buffer without a pending ramp p = target, on one with a ramp the formula above for
+ * fields 0 to 5; H = (int)hold of target on either.  Every - and * below is rounded once, fmaf only where written;
+ * fmaxf ignores a NaN operand.  For sample n of track j in link group G, x the input, k the key block if one is given,
+ * else x, and the track's carried g (float32) and c (int32):
+ *     detector   a  = fmaxf over j' in G of |k[j'][n]|, from 0         (a NaN is ignored, as by the meter's peak)
+ *     state      c  = a > open ? H : a >= close ? (c >= 0 ? H : -1) : max(c - 1, -1)
+ *                o  = c >= 0
+ *     glide      tg = o ? g_open : g_closed;   al = o ? att : rel;   g = fmaf(al, g - tg, tg)
+ *     output     y  = x * g
+ *     act        the number of samples of the buffer with o
+ * So the gate opens on the first sample above open, stays open for exactly `hold` samples below close (the count runs
+ * H - 1, ..., 0, -1), and a level between close and open keeps whatever state there is and re-arms the hold of an open
+ * gate.  g is a convex combination of its old value and g_open or g_closed: it stays within [0, 256] once it is there
+ * and decays through the subnormals to 0 under g_closed = 0 (the device keeps subnormals).  g and c are finite whatever
+ * the samples are: a NaN or an infinity in x reaches y (x times a finite gain) and nothing else; a NaN in the key is
+ * ignored and an infinity in the key opens the gate.  Nothing has rounding freedom: every launch form gives the same
+ * bits, and a shard of tracks that is a multiple of link, run as its own plan, gives those tracks' bits.
+ * Out of scope: downward expansion with a ratio (the dynamics plan's log2 domain), look-ahead (a gab_delay plan in
+ * front of d_in, with the undelayed signal as d_key, gives it), a filtered key (a gab_eq plan on the key gives it).
+ * The launch works on 16 tracks x 64 samples per wave, four waves to a workgroup: fewer than 16 x 1024 tracks use a
+ * part of the device.  One thread at a time per plan.                                                               */
+typedef struct gab_gate_plan gab_gate_plan;
+#define GAB_GATE_FIELDS 7
+int gab_gate_create(gab_gate_plan** plan, int tracks, int bufsize, int link);
+int gab_gate_destroy(gab_gate_plan* plan);
+int gab_gate_set_params(gab_gate_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_gate_set_params_tracks(gab_gate_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                               gab_stream_t stream);
+int gab_gate_reset(gab_gate_plan* plan, gab_stream_t stream);
+int gab_gate_process(gab_gate_plan* plan, const float* d_in, const float* d_key, float* d_out, int* d_act,
+                     gab_stream_t stream);
+int gab_gate_process_batch(gab_gate_plan* plan, const float* d_in, const float* d_key, float* d_out, int* d_act,
+                           int n_buffers, gab_stream_t stream);
+int gab_gate_params(gab_gate_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_gate_state(gab_gate_plan* plan, float** d_gain, int** d_count, size_t* n_tracks);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
