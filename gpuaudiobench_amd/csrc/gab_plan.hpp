@@ -1,9 +1,13 @@
 // gab_plan.hpp — what the host halves of the plans share.  Who owns device memory, pinned memory,
-// events and streams: every plan.  For eq, mix, delay, meter, resample, dynamics and reverb also "check, then commit"
-// for a set of parameters (one check kernel, a rule per plan); the entries of a ranged set; the table that is ramped
-// from current to target over one buffer.
+// events and streams: every plan.  For the eight track plans (eq, mix, delay, meter, resample, dynamics, reverb and
+// gate) also "check, then commit" for a set of parameters (one check kernel, a rule per plan); the bodies of their
+// extern "C" entries (create, process_batch, a ranged set, the exposed table, destroy, and every call that starts with
+// a null check); the table that is ramped from current to target over one buffer.
 #pragma once
 
+#include <cstdint>
+#include <initializer_list>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -37,6 +41,10 @@ public:
         n_ = n;
     }
     void release() { if (p_) (void)hipFree(p_); p_ = nullptr; n_ = 0; }         // (for another size: release, then alloc)
+    void fill(const T& v) {                                                     // v in every element, from the host
+        const std::vector<T> h(n_, v);
+        GAB_HIP_CHECK(hipMemcpy(p_, h.data(), n_ * sizeof(T), hipMemcpyHostToDevice));
+    }
     void swap(DeviceBuf& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); }
     T* get() const { return p_; }
     size_t size() const { return n_; }  // elements
@@ -167,7 +175,79 @@ int check_then(const DeviceBuf<unsigned>& flag, hipStream_t s, const char* who, 
     return GAB_OK;
 }
 
+// The text of a row rule: value i of rows `row` wide, the first of them track first_track's.
+inline std::string row_refusal(unsigned i, unsigned row, int first_track, const char* name, const char* rule) {
+    return "track " + std::to_string(first_track + (int)(i / row)) + " field " + std::to_string((int)(i % row)) + " (" +
+           name + ") " + rule + "; the plan keeps its parameters";
+}
+
+// ---- what a launch function asks of its pointers ----
+// Do a[0, n_floats) and b[0, n_floats) share a byte?
+inline bool overlaps(const float* a, const float* b, size_t n_floats) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t bytes = (uintptr_t)n_floats * sizeof(float);
+    return pa < pb + bytes && pb < pa + bytes;
+}
+
+// Is every one of them on a 16-byte boundary (a null pointer is)?
+inline bool all_aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t bits = 0;
+    for (const void* p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15u) == 0;
+}
+
+// The floats of a ring: the smallest power of two that is at least `need`.
+inline size_t ring_capacity(size_t need) {
+    size_t cap = 1;
+    while (cap < need) cap *= 2;
+    return cap;
+}
+
 // ---- the entries ----
+// Every refusal of an argument: "<who>: <what>" and GAB_ERR_INVALID_ARG.
+inline int refuse(const char* who, const char* what) { return bad_arg((std::string(who) + ": " + what).c_str()); }
+
+// The body of an extern "C" function that starts with a null check: `needed` (the plan first), then body().
+template <class Body>
+int entry(const char* who, std::initializer_list<const void*> needed, Body&& body, const char* what = "null pointer") {
+    return guarded([&]() -> int {
+        for (const void* p : needed)
+            if (!p) return refuse(who, what);
+        return body();
+    });
+}
+
+// The body of gab_X_process_batch: null pointers, then n_buffers, then body() (the plan's own checks and its launch).
+// gab_X_process is entry() with a body that launches one buffer.
+template <class Body>
+int batch_entry(const char* who, std::initializer_list<const void*> needed, int n_buffers, Body&& body) {
+    return entry(who, needed, [&]() -> int {
+        if (n_buffers <= 0) return refuse(who, "n_buffers must be > 0");
+        return body();
+    });
+}
+
+// The body of gab_X_create.  check() is the plan's own verdict on its arguments (GAB_OK, or a refusal with its text
+// set) and works out what build needs of them; build(P&) allocates and fills the plan, whose tracks and bufsize are
+// set, and returns GAB_OK or a launch's status.  The plan sits in a unique_ptr until it is published, last: *out is null
+// after every refusal and after a build that throws, and nothing of a half-built plan stays behind.
+template <class P, class Check, class Build>
+int create_entry(const char* who, P** out, int tracks, int bufsize, Check&& check, Build&& build) {
+    return guarded([&]() -> int {
+        if (!out) return refuse(who, "null plan pointer");
+        *out = nullptr;
+        if (tracks <= 0 || bufsize <= 0) return refuse(who, "tracks and bufsize must be > 0");
+        if (int rc = check()) return rc;
+        if (int rc = refuse_unsupported_runtime_mode(who)) return rc;
+        auto p = std::make_unique<P>();
+        p->tracks = tracks;
+        p->bufsize = bufsize;
+        if (int rc = build(*p)) return rc;
+        *out = p.release();
+        return GAB_OK;
+    });
+}
+
 inline bool track_range_ok(int plan_tracks, int first_track, int n_tracks) {
     return !(first_track < 0 || n_tracks <= 0 || first_track > plan_tracks - n_tracks);
 }
@@ -176,11 +256,10 @@ inline bool track_range_ok(int plan_tracks, int first_track, int n_tracks) {
 // n_tracks)): null pointers, then the range, then the plan's set(plan, d_src, first_track, n_tracks, who, rest...).
 template <class F, class P, class S, class... A>
 int set_entry(const char* who, F set, P* plan, const S* d_src, bool whole, int first_track, int n_tracks, A... rest) {
-    return guarded([&]() -> int {
-        if (!plan || !d_src) return bad_arg((std::string(who) + ": null pointer").c_str());
+    return entry(who, {plan, d_src}, [&]() -> int {
         if (whole) return set(plan, d_src, 0, plan->tracks, who, rest...);
         if (!track_range_ok(plan->tracks, first_track, n_tracks))
-            return bad_arg((std::string(who) + ": the track range is outside the plan").c_str());
+            return refuse(who, "the track range is outside the plan");
         return set(plan, d_src, first_track, n_tracks, who, rest...);
     });
 }
@@ -222,13 +301,6 @@ struct RampedTable {
         GAB_HIP_CHECK(hipMemcpy(target.get(), init.data(), init.size() * sizeof(float), hipMemcpyHostToDevice));
     }
 
-    // for gab_X_params / gab_mix_gains: the tables themselves, not copies
-    void expose(float** d_current, float** d_target, size_t* n_floats) const {
-        *d_current = current.get();
-        *d_target = target.get();
-        *n_floats = current.size();
-    }
-
     // The commit, for values that passed the check: n floats at `offset` of target; of current too unless they are
     // ramped in.  Synchronises: d_src is the caller's again when this returns.
     void commit(const float* d_src, size_t offset, size_t n, bool ramped, hipStream_t s) {
@@ -248,5 +320,17 @@ struct RampedTable {
         pending = false;
     }
 };
+
+// The body of gab_X_params / gab_mix_gains: the plan's tables themselves, not copies.
+template <class P>
+int expose_entry(const char* who, P* plan, RampedTable P::*table, float** d_current, float** d_target,
+                 size_t* n_floats) {
+    return entry(who, {plan, d_current, d_target, n_floats}, [&] {
+        *d_current = (plan->*table).current.get();
+        *d_target = (plan->*table).target.get();
+        *n_floats = (plan->*table).current.size();
+        return GAB_OK;
+    });
+}
 
 }  // namespace gab

@@ -259,8 +259,7 @@ struct DelayRule {
         const int field = (int)(i & 3u);
         const char* rule = field == 0 ? "must be finite and within [min_delay, max_delay]"
                                       : (field == 1 ? "must be finite and below 1 in magnitude" : "must be finite");
-        return "track " + std::to_string(first_track + (int)(i / 4u)) + " field " + std::to_string(field) + " (" +
-               kDelayFields[field] + ") " + rule + "; the plan keeps its parameters";
+        return row_refusal(i, 4, first_track, kDelayFields[field], rule);
     }
 };
 
@@ -315,31 +314,26 @@ int delay_set_range(gab_delay_plan* p, const float* d_params, int first_track, i
 extern "C" {
 
 int gab_delay_create(gab_delay_plan** out, int tracks, int bufsize, int max_delay, int interp) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_delay_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_delay_create: tracks and bufsize must be > 0");
+    const int min_delay = interp == GAB_DELAY_LAGRANGE3 ? 2 : 1;
+    size_t cap = 0;
+    return gab::create_entry("gab_delay_create", out, tracks, bufsize, [&] {
         if (interp != GAB_DELAY_LINEAR && interp != GAB_DELAY_LAGRANGE3)
             return gab::bad_arg("gab_delay_create: interp must be GAB_DELAY_LINEAR or GAB_DELAY_LAGRANGE3");
-        const int min_delay = interp == GAB_DELAY_LAGRANGE3 ? 2 : 1;
         if (max_delay < min_delay || max_delay > (1 << gab::kDelayMaxLog2))
             return gab::bad_arg("gab_delay_create: max_delay must be min_delay..2^20 (min_delay: 1 linear, 2 Lagrange)");
-        size_t cap = 1;
-        while (cap < (size_t)max_delay + 3 + (size_t)bufsize) cap *= 2;
+        cap = gab::ring_capacity((size_t)max_delay + 3 + (size_t)bufsize);
         if (cap > ((size_t)1 << 31)) return gab::bad_arg("gab_delay_create: bufsize is too large for a track's ring");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_delay_create")) return rc;
-        auto p = std::make_unique<gab_delay_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->max_delay = max_delay; p->interp = interp;
-        p->min_delay = min_delay; p->capacity = cap;
-        p->params.create((size_t)tracks * 4, bufsize);
-        p->ring.alloc((size_t)tracks * cap);
-        p->pos.alloc((size_t)tracks);
-        p->flag.alloc(1);
+        return GAB_OK;
+    }, [&](gab_delay_plan& p) {
+        p.max_delay = max_delay; p.interp = interp; p.min_delay = min_delay; p.capacity = cap;
+        p.params.create((size_t)tracks * 4, bufsize);
+        p.ring.alloc((size_t)tracks * cap);
+        p.pos.alloc((size_t)tracks);
+        p.flag.alloc(1);
         // pass-through: {min_delay, 0, 0, 1} on every track, an empty line
-        p->params.fill({(float)min_delay, 0.0f, 0.0f, 1.0f}, tracks);
-        GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, (size_t)tracks * cap * sizeof(float)));
-        GAB_HIP_CHECK(hipMemset(p->pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
-        *out = p.release();
+        p.params.fill({(float)min_delay, 0.0f, 0.0f, 1.0f}, tracks);
+        GAB_HIP_CHECK(hipMemset(p.ring.get(), 0, (size_t)tracks * cap * sizeof(float)));
+        GAB_HIP_CHECK(hipMemset(p.pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
         return GAB_OK;
     });
 }
@@ -358,8 +352,7 @@ int gab_delay_set_params_tracks(gab_delay_plan* plan, const float* d_params, int
 }
 
 int gab_delay_reset(gab_delay_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_delay_reset: null pointer");
+    return gab::entry("gab_delay_reset", {plan}, [&] {
         hipStream_t s = gab::as_stream(stream);
         GAB_HIP_CHECK(hipMemsetAsync(plan->ring.get(), 0, plan->ring.size() * sizeof(float), s));
         GAB_HIP_CHECK(hipMemsetAsync(plan->pos.get(), 0, plan->pos.size() * sizeof(unsigned), s));
@@ -369,31 +362,21 @@ int gab_delay_reset(gab_delay_plan* plan, gab_stream_t stream) {
 }
 
 int gab_delay_process(gab_delay_plan* plan, const float* d_in, float* d_out, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_delay_process: null pointer");
-        return gab::delay_process(plan, d_in, d_out, 1, gab::as_stream(stream));
-    });
+    return gab::entry("gab_delay_process", {plan, d_in, d_out},
+                      [&] { return gab::delay_process(plan, d_in, d_out, 1, gab::as_stream(stream)); });
 }
 
 int gab_delay_process_batch(gab_delay_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_delay_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_delay_process_batch: n_buffers must be > 0");
-        return gab::delay_process(plan, d_in, d_out, n_buffers, gab::as_stream(stream));
-    });
+    return gab::batch_entry("gab_delay_process_batch", {plan, d_in, d_out}, n_buffers,
+                            [&] { return gab::delay_process(plan, d_in, d_out, n_buffers, gab::as_stream(stream)); });
 }
 
 int gab_delay_params(gab_delay_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_delay_params: null pointer");
-        plan->params.expose(d_current, d_target, n_floats);
-        return GAB_OK;
-    });
+    return gab::expose_entry("gab_delay_params", plan, &gab_delay_plan::params, d_current, d_target, n_floats);
 }
 
 int gab_delay_line(gab_delay_plan* plan, float** d_ring, size_t* capacity, unsigned** d_pos) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_ring || !capacity || !d_pos) return gab::bad_arg("gab_delay_line: null pointer");
+    return gab::entry("gab_delay_line", {plan, d_ring, capacity, d_pos}, [&] {
         *d_ring = plan->ring.get();
         *capacity = plan->capacity;
         *d_pos = plan->pos.get();

@@ -357,8 +357,7 @@ struct DynRule {
     }
     std::string refusal(unsigned i, int first_track) const {
         const int field = (int)(i % GAB_DYN_FIELDS);
-        return "track " + std::to_string(first_track + (int)(i / GAB_DYN_FIELDS)) + " field " + std::to_string(field) +
-               " (" + kDynFields[field] + ") " + kDynRules[field] + "; the plan keeps its parameters";
+        return row_refusal(i, GAB_DYN_FIELDS, first_track, kDynFields[field], kDynRules[field]);
     }
 };
 
@@ -375,22 +374,14 @@ struct gab_dyn_plan {
 namespace gab {
 namespace {
 
-bool dyn_overlap(const float* a, const float* b, size_t n) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
 // n buffers in one launch; then, if a ramp ran through the first of them, current := target.  Nothing is allocated and
 // nothing waits here.
 int dyn_process(gab_dyn_plan* p, const float* d_in, const float* d_key, float* d_out, float* d_gr, int n_buffers,
                 hipStream_t s, const char* who) {
-    if (d_key && dyn_overlap(d_key, d_out, (size_t)n_buffers * p->tracks * p->bufsize))
-        return bad_arg((std::string(who) + ": d_key may not overlap d_out").c_str());
+    if (d_key && overlaps(d_key, d_out, (size_t)n_buffers * p->tracks * p->bufsize))
+        return refuse(who, "d_key may not overlap d_out");
     const dim3 grid((unsigned)((p->tracks + kDynTracks - 1) / kDynTracks));
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) |
-                           reinterpret_cast<uintptr_t>(d_key);
-    const bool vec = (bits & 15u) == 0 && p->bufsize % 4 == 0;
+    const bool vec = all_aligned16({d_in, d_out, d_key}) && p->bufsize % 4 == 0;
     const bool ramp = p->params.pending;
 #define GAB_DYN(VV, KK, RR)                                                                                        \
     dyn_kernel<VV, KK, RR><<<grid, kDynTracks, 0, s>>>(d_in, d_key, d_out, d_gr, p->smooth.get(),                  \
@@ -424,23 +415,19 @@ int dyn_set_range(gab_dyn_plan* p, const float* d_params, int first_track, int n
 extern "C" {
 
 int gab_dyn_create(gab_dyn_plan** out, int tracks, int bufsize, int link) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_dyn_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_dyn_create: tracks and bufsize must be > 0");
+    return gab::create_entry("gab_dyn_create", out, tracks, bufsize, [&] {
         if (link < 1 || link > gab::kDynMaxLink || (link & (link - 1)) != 0)
             return gab::bad_arg("gab_dyn_create: link must be a power of two in 1..64");
         if (tracks % link != 0) return gab::bad_arg("gab_dyn_create: tracks must be a multiple of link");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_dyn_create")) return rc;
-        auto p = std::make_unique<gab_dyn_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->link = link;
-        p->params.create((size_t)tracks * GAB_DYN_FIELDS, bufsize);
-        p->smooth.alloc((size_t)tracks);
-        p->flag.alloc(1);
+        return GAB_OK;
+    }, [&](gab_dyn_plan& p) {
+        p.link = link;
+        p.params.create((size_t)tracks * GAB_DYN_FIELDS, bufsize);
+        p.smooth.alloc((size_t)tracks);
+        p.flag.alloc(1);
         // pass-through: {0, 0, 0, 0, 0, 0, 1, -256} on every track, a smoothed gain of 0
-        p->params.fill({0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, -256.0f}, tracks);
-        GAB_HIP_CHECK(hipMemset(p->smooth.get(), 0, (size_t)tracks * sizeof(float)));
-        *out = p.release();
+        p.params.fill({0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, -256.0f}, tracks);
+        GAB_HIP_CHECK(hipMemset(p.smooth.get(), 0, (size_t)tracks * sizeof(float)));
         return GAB_OK;
     });
 }
@@ -458,8 +445,7 @@ int gab_dyn_set_params_tracks(gab_dyn_plan* plan, const float* d_params, int fir
 }
 
 int gab_dyn_reset(gab_dyn_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_dyn_reset: null pointer");
+    return gab::entry("gab_dyn_reset", {plan}, [&] {
         hipStream_t s = gab::as_stream(stream);
         GAB_HIP_CHECK(hipMemsetAsync(plan->smooth.get(), 0, plan->smooth.size() * sizeof(float), s));
         plan->params.snap(s);
@@ -469,33 +455,25 @@ int gab_dyn_reset(gab_dyn_plan* plan, gab_stream_t stream) {
 
 int gab_dyn_process(gab_dyn_plan* plan, const float* d_in, const float* d_key, float* d_out, float* d_gr,
                     gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_dyn_process: null pointer");
+    return gab::entry("gab_dyn_process", {plan, d_in, d_out}, [&] {
         return gab::dyn_process(plan, d_in, d_key, d_out, d_gr, 1, gab::as_stream(stream), "gab_dyn_process");
     });
 }
 
 int gab_dyn_process_batch(gab_dyn_plan* plan, const float* d_in, const float* d_key, float* d_out, float* d_gr,
                           int n_buffers, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_dyn_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_dyn_process_batch: n_buffers must be > 0");
+    return gab::batch_entry("gab_dyn_process_batch", {plan, d_in, d_out}, n_buffers, [&] {
         return gab::dyn_process(plan, d_in, d_key, d_out, d_gr, n_buffers, gab::as_stream(stream),
                                 "gab_dyn_process_batch");
     });
 }
 
 int gab_dyn_params(gab_dyn_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_dyn_params: null pointer");
-        plan->params.expose(d_current, d_target, n_floats);
-        return GAB_OK;
-    });
+    return gab::expose_entry("gab_dyn_params", plan, &gab_dyn_plan::params, d_current, d_target, n_floats);
 }
 
 int gab_dyn_state(gab_dyn_plan* plan, float** d_smooth, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_smooth || !n_floats) return gab::bad_arg("gab_dyn_state: null pointer");
+    return gab::entry("gab_dyn_state", {plan, d_smooth, n_floats}, [&] {
         *d_smooth = plan->smooth.get();
         *n_floats = plan->smooth.size();
         return GAB_OK;
@@ -503,8 +481,7 @@ int gab_dyn_state(gab_dyn_plan* plan, float** d_smooth, size_t* n_floats) {
 }
 
 int gab_dyn_poly(const float** log2_coeffs, int* n_log2, const float** exp2_coeffs, int* n_exp2) {
-    return gab::guarded([&]() -> int {
-        if (!log2_coeffs || !n_log2 || !exp2_coeffs || !n_exp2) return gab::bad_arg("gab_dyn_poly: null pointer");
+    return gab::entry("gab_dyn_poly", {log2_coeffs, n_log2, exp2_coeffs, n_exp2}, [&] {
         *log2_coeffs = gab::kDynLog2;
         *n_log2 = 7;
         *exp2_coeffs = gab::kDynExp2;

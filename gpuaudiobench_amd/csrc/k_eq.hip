@@ -358,10 +358,6 @@ int eq_launch_sequential(const gab_eq_plan* p, const float* d_in, float* d_out, 
     return launch_status("eq_sequential_kernel");
 }
 
-bool eq_aligned(const void* a, const void* b) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0;
-}
-
 // check, then commit (gab_plan.hpp): a refused set leaves the table as it was.  src null: the identity filter.
 int eq_set_range(gab_eq_plan* p, const float* d_coeffs, int first_track, int n_tracks, const char* who, hipStream_t s) {
     const int S = p->sections;
@@ -392,24 +388,19 @@ int eq_set_range(gab_eq_plan* p, const float* d_coeffs, int first_track, int n_t
 extern "C" {
 
 int gab_eq_create(gab_eq_plan** out, int tracks, int bufsize, int sections) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_eq_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_eq_create: tracks and bufsize must be > 0");
+    return gab::create_entry("gab_eq_create", out, tracks, bufsize, [&] {
         if (sections < 1 || sections > gab::kEqMaxSections) return gab::bad_arg("gab_eq_create: sections must be 1..16");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_eq_create")) return rc;
-        auto p = std::make_unique<gab_eq_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->sections = sections;
-        gab::eq_pick_form(bufsize, sections, &p->M, &p->H);
-        p->row_words = gab::eq_row_words(p->M ? p->M : 1);
-        const size_t n = (size_t)tracks * sections;
-        p->table.alloc(n * p->row_words);
-        p->state.alloc(n * 2);
-        p->flag.alloc(1);
-        GAB_HIP_CHECK(hipMemset(p->state.get(), 0, n * 2 * sizeof(float)));
-        if (int rc = gab::eq_set_range(p.get(), nullptr, 0, tracks, "gab_eq_create", nullptr)) return rc;   // identity
-        *out = p.release();
         return GAB_OK;
+    }, [&](gab_eq_plan& p) {
+        p.sections = sections;
+        gab::eq_pick_form(bufsize, sections, &p.M, &p.H);
+        p.row_words = gab::eq_row_words(p.M ? p.M : 1);
+        const size_t n = (size_t)tracks * sections;
+        p.table.alloc(n * p.row_words);
+        p.state.alloc(n * 2);
+        p.flag.alloc(1);
+        GAB_HIP_CHECK(hipMemset(p.state.get(), 0, n * 2 * sizeof(float)));
+        return gab::eq_set_range(&p, nullptr, 0, tracks, "gab_eq_create", nullptr);      // identity
     });
 }
 
@@ -425,34 +416,28 @@ int gab_eq_set_coeffs(gab_eq_plan* plan, const float* d_coeffs, gab_stream_t str
 }
 
 int gab_eq_reset(gab_eq_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_eq_reset: null plan");
+    return gab::entry("gab_eq_reset", {plan}, [&] {
         GAB_HIP_CHECK(hipMemsetAsync(plan->state.get(), 0, plan->state.size() * sizeof(float), gab::as_stream(stream)));
         return GAB_OK;
-    });
+    }, "null plan");
 }
 
 int gab_eq_process_sequential(gab_eq_plan* plan, const float* d_in, float* d_out, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_eq_process_sequential: null pointer");
-        return gab::eq_launch_sequential(plan, d_in, d_out, gab::as_stream(stream));
-    });
+    return gab::entry("gab_eq_process_sequential", {plan, d_in, d_out},
+                      [&] { return gab::eq_launch_sequential(plan, d_in, d_out, gab::as_stream(stream)); });
 }
 
 int gab_eq_process(gab_eq_plan* plan, const float* d_in, float* d_out, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_eq_process: null pointer");
-        if (plan->M == 0 || !gab::eq_aligned(d_in, d_out))
+    return gab::entry("gab_eq_process", {plan, d_in, d_out}, [&] {
+        if (plan->M == 0 || !gab::all_aligned16({d_in, d_out}))
             return gab::eq_launch_sequential(plan, d_in, d_out, gab::as_stream(stream));
         return gab::eq_launch_scan(plan, d_in, d_out, 1, gab::as_stream(stream));
     });
 }
 
 int gab_eq_process_batch(gab_eq_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_eq_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_eq_process_batch: n_buffers must be > 0");
-        if (plan->M != 0 && gab::eq_aligned(d_in, d_out))
+    return gab::batch_entry("gab_eq_process_batch", {plan, d_in, d_out}, n_buffers, [&]() -> int {
+        if (plan->M != 0 && gab::all_aligned16({d_in, d_out}))
             return gab::eq_launch_scan(plan, d_in, d_out, n_buffers, gab::as_stream(stream));
         // no scan for this shape: the ordered kernel, one launch per buffer
         const size_t stride = (size_t)plan->tracks * plan->bufsize;
@@ -464,8 +449,7 @@ int gab_eq_process_batch(gab_eq_plan* plan, const float* d_in, float* d_out, int
 }
 
 int gab_eq_state(gab_eq_plan* plan, float** d_state, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_state || !n_floats) return gab::bad_arg("gab_eq_state: null pointer");
+    return gab::entry("gab_eq_state", {plan, d_state, n_floats}, [&] {
         *d_state = plan->state.get();
         *n_floats = plan->state.size();
         return GAB_OK;
@@ -473,8 +457,7 @@ int gab_eq_state(gab_eq_plan* plan, float** d_state, size_t* n_floats) {
 }
 
 int gab_eq_form(const gab_eq_plan* plan, int* samples_per_lane, int* segments) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !samples_per_lane || !segments) return gab::bad_arg("gab_eq_form: null pointer");
+    return gab::entry("gab_eq_form", {plan, samples_per_lane, segments}, [&] {
         *samples_per_lane = plan->M;
         *segments = plan->H;
         return GAB_OK;

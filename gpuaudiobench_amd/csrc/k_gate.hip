@@ -470,8 +470,7 @@ struct GateRule {
     }
     std::string refusal(unsigned i, int first_track) const {
         const int field = (int)(i % GAB_GATE_FIELDS);
-        return "track " + std::to_string(first_track + (int)(i / GAB_GATE_FIELDS)) + " field " + std::to_string(field) +
-               " (" + kGateFields[field] + ") " + kGateRules[field] + "; the plan keeps its parameters";
+        return row_refusal(i, GAB_GATE_FIELDS, first_track, kGateFields[field], kGateRules[field]);
     }
 };
 
@@ -489,22 +488,14 @@ struct gab_gate_plan {
 namespace gab {
 namespace {
 
-bool gate_overlap(const float* a, const float* b, size_t n) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
 // n buffers in one launch; then, if a ramp ran through the first of them, current := target.  Nothing is allocated and
 // nothing waits here.
 int gate_process(gab_gate_plan* p, const float* d_in, const float* d_key, float* d_out, int* d_act, int n_buffers,
                  hipStream_t s, const char* who) {
-    if (d_key && gate_overlap(d_key, d_out, (size_t)n_buffers * p->tracks * p->bufsize))
-        return bad_arg((std::string(who) + ": d_key may not overlap d_out").c_str());
+    if (d_key && overlaps(d_key, d_out, (size_t)n_buffers * p->tracks * p->bufsize))
+        return refuse(who, "d_key may not overlap d_out");
     const dim3 grid((unsigned)((p->tracks + kGateTracks - 1) / kGateTracks));
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) |
-                           reinterpret_cast<uintptr_t>(d_key);
-    const bool vec = (bits & 15u) == 0 && p->bufsize % 4 == 0;
+    const bool vec = all_aligned16({d_in, d_out, d_key}) && p->bufsize % 4 == 0;
     const bool ramp = p->params.pending;
 #define GAB_GATE(VV, KK, RR)                                                                                       \
     gate_kernel<VV, KK, RR><<<grid, kGateWaves * 64, 0, s>>>(d_in, d_key, d_out, d_act, p->gain.get(),             \
@@ -538,27 +529,21 @@ int gate_set_range(gab_gate_plan* p, const float* d_params, int first_track, int
 extern "C" {
 
 int gab_gate_create(gab_gate_plan** out, int tracks, int bufsize, int link) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_gate_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_gate_create: tracks and bufsize must be > 0");
+    return gab::create_entry("gab_gate_create", out, tracks, bufsize, [&] {
         if (link < 1 || link > gab::kGateMaxLink || (link & (link - 1)) != 0)
             return gab::bad_arg("gab_gate_create: link must be a power of two in 1..64");
         if (tracks % link != 0) return gab::bad_arg("gab_gate_create: tracks must be a multiple of link");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_gate_create")) return rc;
-        auto p = std::make_unique<gab_gate_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->link = link;
-        p->params.create((size_t)tracks * GAB_GATE_FIELDS, bufsize);
-        p->gain.alloc((size_t)tracks);
-        p->count.alloc((size_t)tracks);
-        p->flag.alloc(1);
+        return GAB_OK;
+    }, [&](gab_gate_plan& p) {
+        p.link = link;
+        p.params.create((size_t)tracks * GAB_GATE_FIELDS, bufsize);
+        p.gain.alloc((size_t)tracks);
+        p.count.alloc((size_t)tracks);
+        p.flag.alloc(1);
         // pass-through: {0, 0, 0, 0, 1, 1, 0} on every track, a gain of 1, a count of -1
-        p->params.fill({0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 0.0f}, tracks);
-        const std::vector<float> ones((size_t)tracks, 1.0f);
-        const std::vector<int> closed((size_t)tracks, -1);
-        GAB_HIP_CHECK(hipMemcpy(p->gain.get(), ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemcpy(p->count.get(), closed.data(), closed.size() * sizeof(int), hipMemcpyHostToDevice));
-        *out = p.release();
+        p.params.fill({0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 0.0f}, tracks);
+        p.gain.fill(1.0f);
+        p.count.fill(-1);
         return GAB_OK;
     });
 }
@@ -576,8 +561,7 @@ int gab_gate_set_params_tracks(gab_gate_plan* plan, const float* d_params, int f
 }
 
 int gab_gate_reset(gab_gate_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_gate_reset: null pointer");
+    return gab::entry("gab_gate_reset", {plan}, [&]() -> int {
         hipStream_t s = gab::as_stream(stream);
         gab::gate_reset_kernel<<<dim3((unsigned)((plan->tracks + 255) / 256)), 256, 0, s>>>(
             plan->gain.get(), plan->count.get(), plan->params.target.get(), plan->tracks);
@@ -589,33 +573,25 @@ int gab_gate_reset(gab_gate_plan* plan, gab_stream_t stream) {
 
 int gab_gate_process(gab_gate_plan* plan, const float* d_in, const float* d_key, float* d_out, int* d_act,
                      gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_gate_process: null pointer");
+    return gab::entry("gab_gate_process", {plan, d_in, d_out}, [&] {
         return gab::gate_process(plan, d_in, d_key, d_out, d_act, 1, gab::as_stream(stream), "gab_gate_process");
     });
 }
 
 int gab_gate_process_batch(gab_gate_plan* plan, const float* d_in, const float* d_key, float* d_out, int* d_act,
                            int n_buffers, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_gate_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_gate_process_batch: n_buffers must be > 0");
+    return gab::batch_entry("gab_gate_process_batch", {plan, d_in, d_out}, n_buffers, [&] {
         return gab::gate_process(plan, d_in, d_key, d_out, d_act, n_buffers, gab::as_stream(stream),
                                  "gab_gate_process_batch");
     });
 }
 
 int gab_gate_params(gab_gate_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_gate_params: null pointer");
-        plan->params.expose(d_current, d_target, n_floats);
-        return GAB_OK;
-    });
+    return gab::expose_entry("gab_gate_params", plan, &gab_gate_plan::params, d_current, d_target, n_floats);
 }
 
 int gab_gate_state(gab_gate_plan* plan, float** d_gain, int** d_count, size_t* n_tracks) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_gain || !d_count || !n_tracks) return gab::bad_arg("gab_gate_state: null pointer");
+    return gab::entry("gab_gate_state", {plan, d_gain, d_count, n_tracks}, [&] {
         *d_gain = plan->gain.get();
         *d_count = plan->count.get();
         *n_tracks = plan->gain.size();

@@ -263,7 +263,7 @@ namespace {
 // n buffers in one launch; nothing is allocated, nothing waits
 int meter_launch(gab_meter_plan* p, const float* d_in, float* d_rows, int n_buffers, hipStream_t s) {
     const dim3 grid((unsigned)((p->tracks + kMeterTracks - 1) / kMeterTracks));
-    const bool vec = (reinterpret_cast<uintptr_t>(d_in) & 15u) == 0 && p->bufsize % 4 == 0;
+    const bool vec = all_aligned16({d_in}) && p->bufsize % 4 == 0;
 #define GAB_METER(VV)                                                                                              \
     meter_kernel<VV><<<grid, 256, 0, s>>>(d_in, d_rows, p->hist.get(), p->filter.get(), p->ring.get(),             \
                                           p->pos.get(), p->consts.get(), p->tracks, p->bufsize, p->window,        \
@@ -286,22 +286,19 @@ void meter_clear(gab_meter_plan* p, hipStream_t s) {
 extern "C" {
 
 int gab_meter_create(gab_meter_plan** out, int tracks, int bufsize, int window) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_meter_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_meter_create: tracks and bufsize must be > 0");
+    return gab::create_entry("gab_meter_create", out, tracks, bufsize, [&] {
         if (window < 1 || window > gab::kMeterMaxWindow) return gab::bad_arg("gab_meter_create: window must be 1..64");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_meter_create")) return rc;
-        auto p = std::make_unique<gab_meter_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->window = window;
-        p->inv_B = (float)(1.0 / (double)bufsize);
-        p->inv_W = (float)(1.0 / (double)window);
-        p->consts.alloc((size_t)gab::kMeterTapWords + gab::kMeterCoeffWords);
-        p->hist.alloc((size_t)tracks * gab::kMeterHistWords);
-        p->filter.alloc((size_t)tracks * 4);
-        p->ring.alloc((size_t)tracks * window);
-        p->pos.alloc((size_t)tracks);
-        p->flag.alloc(1);
+        return GAB_OK;
+    }, [&](gab_meter_plan& p) {
+        p.window = window;
+        p.inv_B = (float)(1.0 / (double)bufsize);
+        p.inv_W = (float)(1.0 / (double)window);
+        p.consts.alloc((size_t)gab::kMeterTapWords + gab::kMeterCoeffWords);
+        p.hist.alloc((size_t)tracks * gab::kMeterHistWords);
+        p.filter.alloc((size_t)tracks * 4);
+        p.ring.alloc((size_t)tracks * window);
+        p.pos.alloc((size_t)tracks);
+        p.flag.alloc(1);
         // the true-peak taps: phase k = 1, 2, 3 of a 4x interpolator, 12 taps each, a Hann-like window of half-width
         // 6.5; float64, each phase divided by its sum (added in ascending j), rounded once
         float taps[gab::kMeterTapWords];
@@ -315,13 +312,12 @@ int gab_meter_create(gab_meter_plan** out, int tracks, int bufsize, int window) 
             }
             for (int j = 0; j < gab::kMeterTaps; ++j) taps[(k - 1) * gab::kMeterTaps + j] = (float)(h[j] / sum);
         }
-        GAB_HIP_CHECK(hipMemcpy(p->consts.get(), taps, sizeof(taps), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemset(p->consts.get() + gab::kMeterTapWords, 0, gab::kMeterCoeffWords * sizeof(float)));
-        GAB_HIP_CHECK(hipMemcpy(p->consts.get() + gab::kMeterTapWords, gab::kMeterDefault, sizeof(gab::kMeterDefault),
+        GAB_HIP_CHECK(hipMemcpy(p.consts.get(), taps, sizeof(taps), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemset(p.consts.get() + gab::kMeterTapWords, 0, gab::kMeterCoeffWords * sizeof(float)));
+        GAB_HIP_CHECK(hipMemcpy(p.consts.get() + gab::kMeterTapWords, gab::kMeterDefault, sizeof(gab::kMeterDefault),
                                 hipMemcpyHostToDevice));
-        gab::meter_clear(p.get(), nullptr);
+        gab::meter_clear(&p, nullptr);
         GAB_HIP_CHECK(hipStreamSynchronize(nullptr));
-        *out = p.release();
         return GAB_OK;
     });
 }
@@ -330,8 +326,7 @@ int gab_meter_destroy(gab_meter_plan* plan) { return gab::destroy_plan(plan, "ga
 
 // check, then commit (gab_plan.hpp): a refused set leaves the rows as they were
 int gab_meter_set_weighting(gab_meter_plan* plan, const float* d_sections, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_sections) return gab::bad_arg("gab_meter_set_weighting: null pointer");
+    return gab::entry("gab_meter_set_weighting", {plan, d_sections}, [&] {
         hipStream_t s = gab::as_stream(stream);
         return gab::check_then(plan->flag, s, "gab_meter_set_weighting", d_sections, 10, gab::MeterRule{}, 0, [&] {
             GAB_HIP_CHECK(hipMemcpyAsync(plan->consts.get() + gab::kMeterTapWords, d_sections, 10 * sizeof(float),
@@ -351,31 +346,24 @@ int gab_meter_set_decay(gab_meter_plan* plan, float decay, gab_stream_t) {
 }
 
 int gab_meter_reset(gab_meter_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_meter_reset: null pointer");
+    return gab::entry("gab_meter_reset", {plan}, [&] {
         gab::meter_clear(plan, gab::as_stream(stream));
         return GAB_OK;
     });
 }
 
 int gab_meter_process(gab_meter_plan* plan, const float* d_in, float* d_rows, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_rows) return gab::bad_arg("gab_meter_process: null pointer");
-        return gab::meter_launch(plan, d_in, d_rows, 1, gab::as_stream(stream));
-    });
+    return gab::entry("gab_meter_process", {plan, d_in, d_rows},
+                      [&] { return gab::meter_launch(plan, d_in, d_rows, 1, gab::as_stream(stream)); });
 }
 
 int gab_meter_process_batch(gab_meter_plan* plan, const float* d_in, float* d_rows, int n_buffers, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_rows) return gab::bad_arg("gab_meter_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_meter_process_batch: n_buffers must be > 0");
-        return gab::meter_launch(plan, d_in, d_rows, n_buffers, gab::as_stream(stream));
-    });
+    return gab::batch_entry("gab_meter_process_batch", {plan, d_in, d_rows}, n_buffers,
+                            [&] { return gab::meter_launch(plan, d_in, d_rows, n_buffers, gab::as_stream(stream)); });
 }
 
 int gab_meter_state(gab_meter_plan* plan, float** d_hist, float** d_filter, float** d_ring, unsigned** d_pos) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_hist || !d_filter || !d_ring || !d_pos) return gab::bad_arg("gab_meter_state: null pointer");
+    return gab::entry("gab_meter_state", {plan, d_hist, d_filter, d_ring, d_pos}, [&] {
         *d_hist = plan->hist.get();
         *d_filter = plan->filter.get();
         *d_ring = plan->ring.get();

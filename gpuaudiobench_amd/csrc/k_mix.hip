@@ -336,7 +336,10 @@ int mix_launch(gab_mix_plan* p, const float* d_in, float* d_out, int n, int layo
     return GAB_OK;
 }
 
-int mix_process(gab_mix_plan* p, const float* d_in, float* d_out, int n_buffers, int layout, hipStream_t s) {
+int mix_process(gab_mix_plan* p, const float* d_in, float* d_out, int n_buffers, int layout, hipStream_t s,
+                const char* who) {
+    if (layout != GAB_MIX_TRACK_MAJOR && layout != GAB_MIX_SAMPLE_MAJOR)
+        return refuse(who, "layout must be GAB_MIX_TRACK_MAJOR or GAB_MIX_SAMPLE_MAJOR");
     const size_t in_stride = (size_t)p->tracks * p->bufsize, out_stride = (size_t)p->buses * p->bufsize;
     const bool ramp = p->gains.pending;
     for (int done = 0; done < n_buffers;) {
@@ -363,30 +366,26 @@ int mix_set_range(gab_mix_plan* p, const float* d_gains, int first_track, int n_
 extern "C" {
 
 int gab_mix_create(gab_mix_plan** out, int tracks, int bufsize, int buses) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_mix_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_mix_create: tracks and bufsize must be > 0");
+    const long long n_groups = ((long long)tracks + gab::kMixGroupTracks - 1) / gab::kMixGroupTracks;
+    return gab::create_entry("gab_mix_create", out, tracks, bufsize, [&] {
         if (buses < 1 || buses > gab::kMixMaxBuses) return gab::bad_arg("gab_mix_create: buses must be 1..64");
-        const long long n_groups = ((long long)tracks + gab::kMixGroupTracks - 1) / gab::kMixGroupTracks;
         if (n_groups * (((long long)bufsize + 63) / 64) > INT_MAX)
             return gab::bad_arg("gab_mix_create: tracks x bufsize is too large for one launch");
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_mix_create")) return rc;
-        auto p = std::make_unique<gab_mix_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->buses = buses;
-        gab::mix_pick_form(bufsize, buses, &p->leaf_tracks, &p->group_leaves);
-        p->n_groups = (int)n_groups;
-        p->gains.create((size_t)tracks * buses, bufsize);
-        p->flag.alloc(1);
+        return GAB_OK;
+    }, [&](gab_mix_plan& p) {
+        p.buses = buses;
+        gab::mix_pick_form(bufsize, buses, &p.leaf_tracks, &p.group_leaves);
+        p.n_groups = (int)n_groups;
+        p.gains.create((size_t)tracks * buses, bufsize);
+        p.flag.alloc(1);
         // The workspace of the final pass: as many buffers' partial sums as fit 32 MiB, at least one and at most
         // kMixBatchChunk.  A longer batch is that many buffers per launch, one launch after the other.
-        const size_t per_buffer = (size_t)p->n_groups * buses * bufsize * sizeof(float);
+        const size_t per_buffer = (size_t)p.n_groups * buses * bufsize * sizeof(float);
         size_t chunk = ((size_t)32 << 20) / per_buffer;
         chunk = chunk < 1 ? 1 : (chunk > (size_t)gab::kMixBatchChunk ? (size_t)gab::kMixBatchChunk : chunk);
-        p->part_buffers = p->n_groups > 1 ? (int)chunk : gab::kMixBatchChunk;
-        if (p->n_groups > 1) p->part.alloc(chunk * per_buffer / sizeof(float));
-        p->gains.fill(std::vector<float>((size_t)buses, 0.0f), tracks);      // silence
-        *out = p.release();
+        p.part_buffers = p.n_groups > 1 ? (int)chunk : gab::kMixBatchChunk;
+        if (p.n_groups > 1) p.part.alloc(chunk * per_buffer / sizeof(float));
+        p.gains.fill(std::vector<float>((size_t)buses, 0.0f), tracks);      // silence
         return GAB_OK;
     });
 }
@@ -404,44 +403,31 @@ int gab_mix_set_gains_tracks(gab_mix_plan* plan, const float* d_gains, int first
 }
 
 int gab_mix_reset(gab_mix_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_mix_reset: null pointer");
+    return gab::entry("gab_mix_reset", {plan}, [&] {
         plan->gains.snap(gab::as_stream(stream));
         return GAB_OK;
     });
 }
 
 int gab_mix_process(gab_mix_plan* plan, const float* d_in, float* d_out, int layout, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_mix_process: null pointer");
-        if (layout != GAB_MIX_TRACK_MAJOR && layout != GAB_MIX_SAMPLE_MAJOR)
-            return gab::bad_arg("gab_mix_process: layout must be GAB_MIX_TRACK_MAJOR or GAB_MIX_SAMPLE_MAJOR");
-        return gab::mix_process(plan, d_in, d_out, 1, layout, gab::as_stream(stream));
+    return gab::entry("gab_mix_process", {plan, d_in, d_out}, [&] {
+        return gab::mix_process(plan, d_in, d_out, 1, layout, gab::as_stream(stream), "gab_mix_process");
     });
 }
 
 int gab_mix_process_batch(gab_mix_plan* plan, const float* d_in, float* d_out, int n_buffers, int layout,
                           gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_mix_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_mix_process_batch: n_buffers must be > 0");
-        if (layout != GAB_MIX_TRACK_MAJOR && layout != GAB_MIX_SAMPLE_MAJOR)
-            return gab::bad_arg("gab_mix_process_batch: layout must be GAB_MIX_TRACK_MAJOR or GAB_MIX_SAMPLE_MAJOR");
-        return gab::mix_process(plan, d_in, d_out, n_buffers, layout, gab::as_stream(stream));
+    return gab::batch_entry("gab_mix_process_batch", {plan, d_in, d_out}, n_buffers, [&] {
+        return gab::mix_process(plan, d_in, d_out, n_buffers, layout, gab::as_stream(stream), "gab_mix_process_batch");
     });
 }
 
 int gab_mix_gains(gab_mix_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_mix_gains: null pointer");
-        plan->gains.expose(d_current, d_target, n_floats);
-        return GAB_OK;
-    });
+    return gab::expose_entry("gab_mix_gains", plan, &gab_mix_plan::gains, d_current, d_target, n_floats);
 }
 
 int gab_mix_form(const gab_mix_plan* plan, int* leaf_tracks, int* group_leaves) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !leaf_tracks || !group_leaves) return gab::bad_arg("gab_mix_form: null pointer");
+    return gab::entry("gab_mix_form", {plan, leaf_tracks, group_leaves}, [&] {
         *leaf_tracks = plan->leaf_tracks;
         *group_leaves = plan->group_leaves;
         return GAB_OK;

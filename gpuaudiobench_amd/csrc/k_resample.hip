@@ -237,40 +237,37 @@ int resample_launch(gab_resample_plan* p, const float* d_in, float* d_out, int n
 extern "C" {
 
 int gab_resample_create(gab_resample_plan** out, int tracks, int bufsize, int up, int down, int taps) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_resample_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_resample_create: tracks and bufsize must be > 0");
+    int L = 0, M = 0;               // up and down, reduced
+    return gab::create_entry("gab_resample_create", out, tracks, bufsize, [&] {
         if (bufsize > gab::kRsMaxBufsize) return gab::bad_arg("gab_resample_create: bufsize must be <= 2^20");
         if (up < 1 || up > gab::kRsMaxRatio || down < 1 || down > gab::kRsMaxRatio)
             return gab::bad_arg("gab_resample_create: up and down must be 1..1024");
         if (taps < 4 || taps > gab::kRsMaxTaps || taps % 2 != 0)
             return gab::bad_arg("gab_resample_create: taps must be even and 4..256");
         const int g = gab::gcd_int(up, down);
-        const int L = up / g, M = down / g;
+        L = up / g; M = down / g;
         if (L * taps > gab::kRsMaxTable) {
             gab::set_last_error("gab_resample_create: a table of up * taps = " + std::to_string(L * taps) +
                                 " floats (up reduced) is more than 16384");
             return GAB_ERR_UNSUPPORTED;
         }
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_resample_create")) return rc;
-        auto p = std::make_unique<gab_resample_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->L = L; p->M = M; p->K = taps;
+        return GAB_OK;
+    }, [&](gab_resample_plan& p) {
+        p.L = L; p.M = M; p.K = taps;
         const long long BL = (long long)bufsize * L;
-        p->out_capacity = (int)gab::ceil_div(BL, M);
-        p->period = M / gab::gcd_int((int)(BL % M), M);
+        p.out_capacity = (int)gab::ceil_div(BL, M);
+        p.period = M / gab::gcd_int((int)(BL % M), M);
         const size_t lds = gab::resample_lds_bytes(taps);
         if (lds > 64 * 1024)
             GAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gab::resample_kernel),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        p->taps.alloc((size_t)L * taps);
-        p->hist.alloc((size_t)tracks * (taps - 1));
-        p->flag.alloc(1);
+        p.taps.alloc((size_t)L * taps);
+        p.hist.alloc((size_t)tracks * (taps - 1));
+        p.flag.alloc(1);
         const std::vector<float> h = gab::resample_design(L, M, taps);
-        GAB_HIP_CHECK(hipMemcpy(p->taps.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemset(p->hist.get(), 0, p->hist.size() * sizeof(float)));
+        GAB_HIP_CHECK(hipMemcpy(p.taps.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemset(p.hist.get(), 0, p.hist.size() * sizeof(float)));
         GAB_HIP_CHECK(hipStreamSynchronize(nullptr));
-        *out = p.release();
         return GAB_OK;
     });
 }
@@ -280,9 +277,7 @@ int gab_resample_destroy(gab_resample_plan* plan) {
 }
 
 int gab_resample_shape(gab_resample_plan* plan, int* up, int* down, int* taps, int* out_capacity, int* period) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !up || !down || !taps || !out_capacity || !period)
-            return gab::bad_arg("gab_resample_shape: null pointer");
+    return gab::entry("gab_resample_shape", {plan, up, down, taps, out_capacity, period}, [&] {
         *up = plan->L; *down = plan->M; *taps = plan->K; *out_capacity = plan->out_capacity; *period = plan->period;
         return GAB_OK;
     });
@@ -290,8 +285,7 @@ int gab_resample_shape(gab_resample_plan* plan, int* up, int* down, int* taps, i
 
 // check, then commit (gab_plan.hpp): a refused table leaves the plan's as it was
 int gab_resample_set_taps(gab_resample_plan* plan, const float* d_taps, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_taps) return gab::bad_arg("gab_resample_set_taps: null pointer");
+    return gab::entry("gab_resample_set_taps", {plan, d_taps}, [&] {
         hipStream_t s = gab::as_stream(stream);
         const size_t n = (size_t)plan->L * plan->K;
         const gab::ResampleRule rule{(unsigned)plan->K};
@@ -303,8 +297,7 @@ int gab_resample_set_taps(gab_resample_plan* plan, const float* d_taps, gab_stre
 }
 
 int gab_resample_reset(gab_resample_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_resample_reset: null pointer");
+    return gab::entry("gab_resample_reset", {plan}, [&] {
         GAB_HIP_CHECK(hipMemsetAsync(plan->hist.get(), 0, plan->hist.size() * sizeof(float), gab::as_stream(stream)));
         plan->k = 0;
         return GAB_OK;
@@ -312,25 +305,19 @@ int gab_resample_reset(gab_resample_plan* plan, gab_stream_t stream) {
 }
 
 int gab_resample_process(gab_resample_plan* plan, const float* d_in, float* d_out, int* n_out, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out || !n_out) return gab::bad_arg("gab_resample_process: null pointer");
-        return gab::resample_launch(plan, d_in, d_out, 1, n_out, gab::as_stream(stream));
-    });
+    return gab::entry("gab_resample_process", {plan, d_in, d_out, n_out},
+                      [&] { return gab::resample_launch(plan, d_in, d_out, 1, n_out, gab::as_stream(stream)); });
 }
 
 int gab_resample_process_batch(gab_resample_plan* plan, const float* d_in, float* d_out, int n_buffers, int* counts,
                                gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out || !counts) return gab::bad_arg("gab_resample_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_resample_process_batch: n_buffers must be > 0");
+    return gab::batch_entry("gab_resample_process_batch", {plan, d_in, d_out, counts}, n_buffers, [&] {
         return gab::resample_launch(plan, d_in, d_out, n_buffers, counts, gab::as_stream(stream));
     });
 }
 
 int gab_resample_state(gab_resample_plan* plan, float** d_hist, float** d_taps, long long* buffers_since_reset_mod_period) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_hist || !d_taps || !buffers_since_reset_mod_period)
-            return gab::bad_arg("gab_resample_state: null pointer");
+    return gab::entry("gab_resample_state", {plan, d_hist, d_taps, buffers_since_reset_mod_period}, [&] {
         *d_hist = plan->hist.get();
         *d_taps = plan->taps.get();
         *buffers_since_reset_mod_period = plan->k;

@@ -273,8 +273,7 @@ struct ReverbRule {
         const char* name = field < N ? "g" : (field < 2 * N ? "damp" : (field < 3 * N ? "b" : (field < row - 1 ? "c" : "dry")));
         const char* rule = field < N ? "must be finite and at most gab_reverb_gmax(lines) in magnitude"
                                      : (field < 2 * N ? "must be within [0, 1 - 2^-20]" : "must be finite");
-        return "track " + std::to_string(first_track + (int)(i / (unsigned)row)) + " field " + std::to_string(field) +
-               " (" + name + ") " + rule + "; the plan keeps its parameters";
+        return row_refusal(i, (unsigned)row, first_track, name, rule);
     }
 };
 
@@ -318,8 +317,7 @@ float reverb_gmax(int lines) {
 // n buffers in one launch; then, if a ramp ran through the first of them, current := target.  Nothing is allocated and
 // nothing waits here.
 int reverb_process(gab_reverb_plan* p, const float* d_in, float* d_out, int n_buffers, hipStream_t s, const char* who) {
-    if (p->outs != 1 && (const float*)d_out == d_in)
-        return bad_arg((std::string(who) + ": d_out == d_in needs outs == 1").c_str());
+    if (p->outs != 1 && (const float*)d_out == d_in) return refuse(who, "d_out == d_in needs outs == 1");
     const int per_wave = kRevChains / p->lines;
     const dim3 grid((unsigned)((p->tracks + per_wave - 1) / per_wave));
     const unsigned mask = (unsigned)(p->capacity - 1);
@@ -375,37 +373,31 @@ int gab_reverb_row_floats(int lines, int outs) {
 float gab_reverb_gmax(int lines) { return gab::reverb_gmax(lines); }
 
 int gab_reverb_create(gab_reverb_plan** out, int tracks, int bufsize, int lines, int outs, int max_delay) {
-    return gab::guarded([&]() -> int {
-        if (!out) return gab::bad_arg("gab_reverb_create: null plan pointer");
-        *out = nullptr;
-        if (tracks <= 0 || bufsize <= 0) return gab::bad_arg("gab_reverb_create: tracks and bufsize must be > 0");
+    return gab::create_entry("gab_reverb_create", out, tracks, bufsize, [&] {
         if (!gab::reverb_lines_ok(lines)) return gab::bad_arg("gab_reverb_create: lines must be 4, 8 or 16");
         if (outs != 1 && outs != 2) return gab::bad_arg("gab_reverb_create: outs must be 1 or 2");
         if (max_delay < GAB_REVERB_MIN_DELAY || max_delay > (1 << gab::kRevMaxLog2))
             return gab::bad_arg("gab_reverb_create: max_delay must be GAB_REVERB_MIN_DELAY..2^20");
-        size_t cap = 1;
-        while (cap < (size_t)max_delay + gab::kRevChunk) cap *= 2;
-        if (int rc = gab::refuse_unsupported_runtime_mode("gab_reverb_create")) return rc;
-        auto p = std::make_unique<gab_reverb_plan>();
-        p->tracks = tracks; p->bufsize = bufsize; p->lines = lines; p->outs = outs; p->max_delay = max_delay;
-        p->row = lines * (3 + outs) + 1; p->capacity = cap;
+        return GAB_OK;
+    }, [&](gab_reverb_plan& p) {
+        p.lines = lines; p.outs = outs; p.max_delay = max_delay;
+        p.row = lines * (3 + outs) + 1;
+        p.capacity = gab::ring_capacity((size_t)max_delay + gab::kRevChunk);
         const size_t chains = (size_t)tracks * (size_t)lines;
-        p->params.create((size_t)tracks * (size_t)p->row, bufsize);
-        p->ring.alloc(chains * cap);
-        p->pos.alloc((size_t)tracks);
-        p->q.alloc(chains);
-        p->delays.alloc(chains);
-        p->flag.alloc(1);
+        p.params.create((size_t)tracks * (size_t)p.row, bufsize);
+        p.ring.alloc(chains * p.capacity);
+        p.pos.alloc((size_t)tracks);
+        p.q.alloc(chains);
+        p.delays.alloc(chains);
+        p.flag.alloc(1);
         // pass-through: dry = 1, everything else 0, every delay max_delay, empty lines
-        std::vector<float> init((size_t)p->row, 0.0f);
+        std::vector<float> init((size_t)p.row, 0.0f);
         init.back() = 1.0f;
-        p->params.fill(init, tracks);
-        const std::vector<int> m(chains, max_delay);
-        GAB_HIP_CHECK(hipMemcpy(p->delays.get(), m.data(), chains * sizeof(int), hipMemcpyHostToDevice));
-        GAB_HIP_CHECK(hipMemset(p->ring.get(), 0, chains * cap * sizeof(float)));
-        GAB_HIP_CHECK(hipMemset(p->pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
-        GAB_HIP_CHECK(hipMemset(p->q.get(), 0, chains * sizeof(float)));
-        *out = p.release();
+        p.params.fill(init, tracks);
+        p.delays.fill(max_delay);
+        GAB_HIP_CHECK(hipMemset(p.ring.get(), 0, chains * p.capacity * sizeof(float)));
+        GAB_HIP_CHECK(hipMemset(p.pos.get(), 0, (size_t)tracks * sizeof(unsigned)));
+        GAB_HIP_CHECK(hipMemset(p.q.get(), 0, chains * sizeof(float)));
         return GAB_OK;
     });
 }
@@ -435,8 +427,7 @@ int gab_reverb_set_delays_tracks(gab_reverb_plan* plan, const int* d_delays, int
 }
 
 int gab_reverb_reset(gab_reverb_plan* plan, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan) return gab::bad_arg("gab_reverb_reset: null pointer");
+    return gab::entry("gab_reverb_reset", {plan}, [&] {
         hipStream_t s = gab::as_stream(stream);
         GAB_HIP_CHECK(hipMemsetAsync(plan->ring.get(), 0, plan->ring.size() * sizeof(float), s));
         GAB_HIP_CHECK(hipMemsetAsync(plan->pos.get(), 0, plan->pos.size() * sizeof(unsigned), s));
@@ -447,34 +438,25 @@ int gab_reverb_reset(gab_reverb_plan* plan, gab_stream_t stream) {
 }
 
 int gab_reverb_process(gab_reverb_plan* plan, const float* d_in, float* d_out, gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_reverb_process: null pointer");
+    return gab::entry("gab_reverb_process", {plan, d_in, d_out}, [&] {
         return gab::reverb_process(plan, d_in, d_out, 1, gab::as_stream(stream), "gab_reverb_process");
     });
 }
 
 int gab_reverb_process_batch(gab_reverb_plan* plan, const float* d_in, float* d_out, int n_buffers,
                              gab_stream_t stream) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_in || !d_out) return gab::bad_arg("gab_reverb_process_batch: null pointer");
-        if (n_buffers <= 0) return gab::bad_arg("gab_reverb_process_batch: n_buffers must be > 0");
+    return gab::batch_entry("gab_reverb_process_batch", {plan, d_in, d_out}, n_buffers, [&] {
         return gab::reverb_process(plan, d_in, d_out, n_buffers, gab::as_stream(stream), "gab_reverb_process_batch");
     });
 }
 
 int gab_reverb_params(gab_reverb_plan* plan, float** d_current, float** d_target, size_t* n_floats) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_current || !d_target || !n_floats) return gab::bad_arg("gab_reverb_params: null pointer");
-        plan->params.expose(d_current, d_target, n_floats);
-        return GAB_OK;
-    });
+    return gab::expose_entry("gab_reverb_params", plan, &gab_reverb_plan::params, d_current, d_target, n_floats);
 }
 
 int gab_reverb_state(gab_reverb_plan* plan, float** d_lines, size_t* capacity, unsigned** d_pos, float** d_q,
                      int** d_delays) {
-    return gab::guarded([&]() -> int {
-        if (!plan || !d_lines || !capacity || !d_pos || !d_q || !d_delays)
-            return gab::bad_arg("gab_reverb_state: null pointer");
+    return gab::entry("gab_reverb_state", {plan, d_lines, capacity, d_pos, d_q, d_delays}, [&] {
         *d_lines = plan->ring.get();
         *capacity = plan->capacity;
         *d_pos = plan->pos.get();

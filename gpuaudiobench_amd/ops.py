@@ -90,6 +90,92 @@ def _n_buffers(plan, xs):
     return n
 
 
+def _positions(ptr, n):
+    """A copy of a library-owned vector [n] of uint32 positions, as int64."""
+    return _view(ptr, n, 1).clone().view(torch.int32).to(torch.int64).view(n)
+
+
+class _TrackPlan(_Handle):
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate) share: `tracks` channels of
+    `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
+
+    def _fn(self, what):
+        return getattr(lib, self._destroy[:-len("destroy")] + what)
+
+    def _create(self, tracks, bufsize, *rest):
+        self.tracks, self.bufsize = tracks, bufsize
+        self._h = C.c_void_p()
+        check(self._fn("create")(C.byref(self._h), tracks, bufsize, *rest))
+
+    def reset(self):
+        check(self._fn("reset")(self._h, _stream()))
+
+    def _rows(self, t, width, first_track, what="table"):
+        """How many rows of `width` values t holds: whole rows, and without a first_track one per track."""
+        n, rest = divmod(t.numel(), width)
+        if rest or n == 0:
+            raise ValueError("%s must hold whole rows of %d values" % (what, width))
+        if first_track is None and n != self.tracks:
+            raise ValueError("%s must hold a row per track (or give first_track)" % what)
+        return n
+
+    def _set(self, what, ptr, first_track, n_tracks, *rest):
+        """gab_<plan>_set_<what> (first_track None: every track of the plan), else gab_<plan>_set_<what>_tracks."""
+        if first_track is None:
+            check(self._fn("set_" + what)(self._h, ptr, *rest, _stream()))
+        else:
+            check(self._fn("set_" + what + "_tracks")(self._h, ptr, first_track, n_tracks, *rest, _stream()))
+
+    def _tables(self, what, width):
+        """Copies of (current, target) of the ramped table behind gab_<plan>_<what>, each [tracks][width]."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(self._fn(what)(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        return _view(a.value, self.tracks, width).clone(), _view(b.value, self.tracks, width).clone()
+
+    def _process(self, what, xs, out, n, shape, *rest, sized=True):
+        """gab_<plan>_<what>(plan, xs, out, *rest, stream) on the n buffers of xs; returns out.  out=None: a new tensor
+        of `shape` (None: like xs); a given out holds as many elements (sized=False: not looked at)."""
+        assert xs.numel() == n * self.tracks * self.bufsize
+        if out is None:
+            out = torch.empty_like(xs) if shape is None else torch.empty(shape, dtype=torch.float32, device=xs.device)
+        assert not sized or out.numel() == (xs.numel() if shape is None else torch.Size(shape).numel())
+        check(self._fn(what)(self._h, _dev(xs), _dev(out), *rest, _stream()))
+        return out
+
+
+class _KeyedPlan(_TrackPlan):
+    """The plans with a side chain, dynamics and gate: rows of len(FIELDS) parameters per track, tracks [g link,
+    (g + 1) link) on one detector, and a process call of the form (x, key, out, extra): key is what the detector reads
+    instead of x, extra an optional block of dtype `_extra` with a word per track and buffer."""
+
+    _extra = torch.float32
+
+    def __init__(self, tracks, bufsize, link=1):
+        self.link = link
+        self._create(tracks, bufsize, link)
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][len(FIELDS)], or [n][len(FIELDS)] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n = self._rows(table, len(self.FIELDS), first_track)
+        self._set("params", _dev(table), first_track, n, 1 if ramp else 0)
+
+    def _run(self, what, x, key, out, extra, n):
+        """n None: process, one buffer; else process_batch on n buffers."""
+        assert n is not None or x.numel() == self.tracks * self.bufsize
+        out = torch.empty_like(x) if out is None else out
+        assert out.numel() == x.numel() and (key is None or key.numel() == x.numel())
+        assert extra is None or extra.numel() == (n or 1) * self.tracks
+        rest = () if n is None else (n,)
+        check(self._fn(what)(self._h, _dev(x), None if key is None else _dev(key), _dev(out),
+                             None if extra is None else _dev(extra, self._extra), *rest, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][len(FIELDS)]."""
+        return self._tables("params", len(self.FIELDS))
+
+
 def device_count():
     n = C.c_int(0)
     check(lib.gab_device_count(C.byref(n)))
@@ -440,26 +526,21 @@ class ConvPlan(_Handle):
         return a.value, b.value
 
 
-class EqPlan(_Handle, _Prepared):
+class EqPlan(_TrackPlan, _Prepared):
     """gab_eq_plan: `sections` biquads in series on each of `tracks` channels, every (track, section) with its own
     coefficients, state carried from buffer to buffer.  A new plan is the identity filter."""
 
     _destroy = "gab_eq_destroy"
 
     def __init__(self, tracks, bufsize, sections):
-        self.tracks, self.bufsize, self.sections = tracks, bufsize, sections
-        self._h = C.c_void_p()
-        check(lib.gab_eq_create(C.byref(self._h), tracks, bufsize, sections))
+        self.sections = sections
+        self._create(tracks, bufsize, sections)
 
     def set_coeffs(self, coeffs, first_track=None, n_tracks=None):
         """coeffs: device tensor [tracks][sections][5] = {b0,b1,b2,a1,a2} (a0 = 1), or [n_tracks][sections][5]
         for tracks [first_track, first_track + n_tracks)."""
-        if first_track is None:
-            assert coeffs.numel() == self.tracks * self.sections * 5
-            check(lib.gab_eq_set_coeffs(self._h, _dev(coeffs), _stream()))
-        else:
-            assert coeffs.numel() == n_tracks * self.sections * 5
-            check(lib.gab_eq_set_coeffs_tracks(self._h, _dev(coeffs), first_track, n_tracks, _stream()))
+        assert coeffs.numel() == (self.tracks if first_track is None else n_tracks) * self.sections * 5
+        self._set("coeffs", _dev(coeffs), first_track, n_tracks)
 
     def set_sos(self, sos, tracks=None):
         """sos: scipy's second-order sections, [sections][6] = {b0,b1,b2,a0,a1,a2} for every track or
@@ -479,23 +560,14 @@ class EqPlan(_Handle, _Prepared):
         else:
             self.set_coeffs(d, first, n)
 
-    def reset(self):
-        check(lib.gab_eq_reset(self._h, _stream()))
-
     def process(self, x, out=None, sequential=False):
         """One buffer, track-major [tracks*bufsize]; out may be x (in place).  sequential=True: the ordered form."""
-        assert x.numel() == self.tracks * self.bufsize
-        out = torch.empty_like(x) if out is None else out
-        fn = lib.gab_eq_process_sequential if sequential else lib.gab_eq_process
-        check(fn(self._h, _dev(x), _dev(out), _stream()))
-        return out
+        return self._process("process_sequential" if sequential else "process", x, out, 1, None, sized=False)
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch."""
         n = _n_buffers(self, xs)
-        out = torch.empty_like(xs) if out is None else out
-        check(lib.gab_eq_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
-        return out
+        return self._process("process_batch", xs, out, n, None, n, sized=False)
 
     def state(self):
         """A copy of the carried state, [tracks][sections][2] = (z1, z2)."""
@@ -513,7 +585,7 @@ class EqPlan(_Handle, _Prepared):
     launch = _launcher("gab_eq_process")
 
 
-class MixPlan(_Handle):
+class MixPlan(_TrackPlan):
     """gab_mix_plan: `tracks` channels summed into `buses` buses with a linear gain per (track, bus), in a fixed
     summation order (`form`).  A new plan is silence; new gains are ramped in over the next buffer unless ramp=False."""
 
@@ -521,9 +593,8 @@ class MixPlan(_Handle):
     _LAYOUTS = {"track": 0, "sample": 1}
 
     def __init__(self, tracks, bufsize, buses):
-        self.tracks, self.bufsize, self.buses = tracks, bufsize, buses
-        self._h = C.c_void_p()
-        check(lib.gab_mix_create(C.byref(self._h), tracks, bufsize, buses))
+        self.buses = buses
+        self._create(tracks, bufsize, buses)
 
     def set_gains(self, g, ramp=True, first_track=None, n_tracks=None):
         """g: device tensor [tracks][buses], or [n_tracks][buses] for tracks [first_track, first_track + n_tracks)
@@ -532,15 +603,13 @@ class MixPlan(_Handle):
         if first_track is None:
             if n_tracks is not None:
                 raise ValueError("n_tracks needs first_track")
-            assert g.numel() == self.tracks * self.buses
-            check(lib.gab_mix_set_gains(self._h, _dev(g), 1 if ramp else 0, _stream()))
-        else:
-            if n_tracks is None:                    # the rows g holds
-                n_tracks, rest = divmod(g.numel(), self.buses)
-                if rest or n_tracks == 0:
-                    raise ValueError("g must hold whole rows of %d buses" % self.buses)
-            assert g.numel() == n_tracks * self.buses
-            check(lib.gab_mix_set_gains_tracks(self._h, _dev(g), first_track, n_tracks, 1 if ramp else 0, _stream()))
+            n_tracks = self.tracks
+        elif n_tracks is None:                      # the rows g holds
+            n_tracks, rest = divmod(g.numel(), self.buses)
+            if rest or n_tracks == 0:
+                raise ValueError("g must hold whole rows of %d buses" % self.buses)
+        assert g.numel() == n_tracks * self.buses
+        self._set("gains", _dev(g), first_track, n_tracks, 1 if ramp else 0)
 
     @staticmethod
     def stereo_gains(gain_db, pan):
@@ -565,32 +634,21 @@ class MixPlan(_Handle):
 
     def reset(self):
         """current := target: a pending ramp is dropped."""
-        check(lib.gab_mix_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, out=None, layout="track"):
         """One buffer: x [tracks*bufsize] track-major ("track") or sample-major ("sample", ConvPlan's output);
         returns [buses*bufsize], bus-major.  out must not overlap x."""
-        assert x.numel() == self.tracks * self.bufsize
-        if out is None:
-            out = torch.empty(self.buses * self.bufsize, dtype=torch.float32, device=x.device)
-        assert out.numel() == self.buses * self.bufsize
-        check(lib.gab_mix_process(self._h, _dev(x), _dev(out), self._LAYOUTS[layout], _stream()))
-        return out
+        return self._process("process", x, out, 1, (self.buses * self.bufsize,), self._LAYOUTS[layout])
 
     def process_batch(self, xs, out=None, layout="track"):
         """Consecutive buffers [n][tracks*bufsize] -> [n][buses*bufsize] in one launch."""
         n = _n_buffers(self, xs)
-        if out is None:
-            out = torch.empty(n * self.buses * self.bufsize, dtype=torch.float32, device=xs.device)
-        assert out.numel() == n * self.buses * self.bufsize
-        check(lib.gab_mix_process_batch(self._h, _dev(xs), _dev(out), n, self._LAYOUTS[layout], _stream()))
-        return out
+        return self._process("process_batch", xs, out, n, (n * self.buses * self.bufsize,), n, self._LAYOUTS[layout])
 
     def gains(self):
         """Copies of (current, target), each [tracks][buses]."""
-        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        check(lib.gab_mix_gains(self._h, C.byref(a), C.byref(b), C.byref(n)))
-        return (_view(a.value, self.tracks, self.buses).clone(), _view(b.value, self.tracks, self.buses).clone())
+        return self._tables("gains", self.buses)
 
     @property
     def form(self):
@@ -607,7 +665,7 @@ class MixPlan(_Handle):
     launch = _launcher("gab_mix_process")
 
 
-class DelayPlan(_Handle, _Prepared):
+class DelayPlan(_TrackPlan, _Prepared):
     """gab_delay_plan: a delay line per track, read at a fractional position (interp "linear" or "lagrange3"), with a
     feedback path.  Parameters per track {delay (samples), feedback, wet, dry}; a new plan is pass-through; new
     parameters are ramped in over the next buffer unless ramp=False."""
@@ -618,55 +676,39 @@ class DelayPlan(_Handle, _Prepared):
     def __init__(self, tracks, bufsize, max_delay, interp="linear"):
         if interp not in self._INTERP:
             raise ValueError("interp must be 'linear' or 'lagrange3'")
-        self.tracks, self.bufsize, self.max_delay, self.interp = tracks, bufsize, max_delay, interp
+        self.max_delay, self.interp = max_delay, interp
         self.min_delay = 2 if interp == "lagrange3" else 1
-        self._h = C.c_void_p()
-        check(lib.gab_delay_create(C.byref(self._h), tracks, bufsize, max_delay, self._INTERP[interp]))
+        self._create(tracks, bufsize, max_delay, self._INTERP[interp])
 
     def set_params(self, params, ramp=True, first_track=0):
         """params: device tensor [n][4] = {delay, feedback, wet, dry} for tracks [first_track, first_track + n).
         ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
-        n, rest = divmod(params.numel(), 4)
-        if rest or n == 0:
-            raise ValueError("params must hold whole rows of 4 values")
-        if first_track == 0 and n == self.tracks:
-            check(lib.gab_delay_set_params(self._h, _dev(params), 1 if ramp else 0, _stream()))
-        else:
-            check(lib.gab_delay_set_params_tracks(self._h, _dev(params), first_track, n, 1 if ramp else 0, _stream()))
+        n = self._rows(params, 4, first_track, "params")
+        whole = first_track == 0 and n == self.tracks           # (first_track has a number by default: any n goes)
+        self._set("params", _dev(params), None if whole else first_track, n, 1 if ramp else 0)
 
     def reset(self):
         """Zero lines, current := target, a pending ramp dropped."""
-        check(lib.gab_delay_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, out=None):
         """One buffer, track-major [tracks*bufsize]; out may be x itself."""
-        assert x.numel() == self.tracks * self.bufsize
-        out = torch.empty_like(x) if out is None else out
-        assert out.numel() == x.numel()
-        check(lib.gab_delay_process(self._h, _dev(x), _dev(out), _stream()))
-        return out
+        return self._process("process", x, out, 1, None)
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch."""
         n = _n_buffers(self, xs)
-        out = torch.empty_like(xs) if out is None else out
-        assert out.numel() == xs.numel()
-        check(lib.gab_delay_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
-        return out
+        return self._process("process_batch", xs, out, n, None, n)
 
     def params(self):
         """Copies of (current, target), each [tracks][4]."""
-        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        check(lib.gab_delay_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
-        return _view(a.value, self.tracks, 4).clone(), _view(b.value, self.tracks, 4).clone()
+        return self._tables("params", 4)
 
     def line(self):
         """Copies of (ring [tracks][capacity] float32, write positions [tracks] int64)."""
         r, p, cap = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
         check(lib.gab_delay_line(self._h, C.byref(r), C.byref(cap), C.byref(p)))
-        ring = _view(r.value, self.tracks, cap.value).clone()
-        pos = _view(p.value, self.tracks, 1).clone().view(torch.int32).to(torch.int64).view(self.tracks)
-        return ring, pos
+        return _view(r.value, self.tracks, cap.value).clone(), _positions(p.value, self.tracks)
 
     launch = _launcher("gab_delay_process")
 
@@ -696,7 +738,7 @@ def dynamics_params(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_
     return table[0] if scalar else table
 
 
-class DynamicsPlan(_Handle):
+class DynamicsPlan(_KeyedPlan):
     """gab_dyn_plan: a compressor / limiter per track with a carried smoothed gain.  Parameters per track {thr, slope,
     knee, kq, att, rel, makeup, range} (dynamics_params makes them from dB, ratio and ms); tracks [g link, (g + 1) link)
     share one detector.  A new plan is pass-through; new parameters are ramped in over the next buffer unless
@@ -705,53 +747,18 @@ class DynamicsPlan(_Handle):
     _destroy = "gab_dyn_destroy"
     FIELDS = ("thr", "slope", "knee", "kq", "att", "rel", "makeup", "range")
 
-    def __init__(self, tracks, bufsize, link=1):
-        self.tracks, self.bufsize, self.link = tracks, bufsize, link
-        self._h = C.c_void_p()
-        check(lib.gab_dyn_create(C.byref(self._h), tracks, bufsize, link))
-
-    def set_params(self, table, ramp=True, first_track=None):
-        """table: device tensor [tracks][8], or [n][8] for tracks [first_track, first_track + n).
-        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
-        n, rest = divmod(table.numel(), len(self.FIELDS))
-        if rest or n == 0:
-            raise ValueError("table must hold whole rows of 8 values")
-        if first_track is None:
-            if n != self.tracks:
-                raise ValueError("table must hold a row per track (or give first_track)")
-            check(lib.gab_dyn_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
-        else:
-            check(lib.gab_dyn_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
-
     def reset(self):
         """The smoothed gain zero, current := target, a pending ramp dropped."""
-        check(lib.gab_dyn_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, key=None, out=None, gr=None):
         """One buffer, track-major [tracks*bufsize]; out may be x itself.  key: the side chain the detector reads instead
         of x (may not overlap out).  gr: a tensor [tracks] that receives the buffer's smallest smoothed gain."""
-        assert x.numel() == self.tracks * self.bufsize
-        out = torch.empty_like(x) if out is None else out
-        return self._run(lib.gab_dyn_process, x, key, out, gr, 1, ())
+        return self._run("process", x, key, out, gr, None)
 
     def process_batch(self, xs, key=None, out=None, gr=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch; key the same shape, gr [n][tracks]."""
-        n = _n_buffers(self, xs)
-        out = torch.empty_like(xs) if out is None else out
-        return self._run(lib.gab_dyn_process_batch, xs, key, out, gr, n, (n,))
-
-    def _run(self, fn, x, key, out, gr, n, extra):
-        assert out.numel() == x.numel() and (key is None or key.numel() == x.numel())
-        assert gr is None or gr.numel() == n * self.tracks
-        check(fn(self._h, _dev(x), None if key is None else _dev(key), _dev(out), None if gr is None else _dev(gr),
-                 *extra, _stream()))
-        return out
-
-    def params(self):
-        """Copies of (current, target), each [tracks][8]."""
-        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        check(lib.gab_dyn_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
-        return _view(a.value, self.tracks, 8).clone(), _view(b.value, self.tracks, 8).clone()
+        return self._run("process_batch", xs, key, out, gr, _n_buffers(self, xs))
 
     def state(self):
         """A copy of the smoothed gain, [tracks], log2 units."""
@@ -804,7 +811,7 @@ def gate_params(open_db, close_db=None, attack_ms=1.0, release_ms=100.0, hold_ms
     return table[0] if scalar else table
 
 
-class GatePlan(_Handle):
+class GatePlan(_KeyedPlan):
     """gab_gate_plan: a noise gate or ducker per track: a two-state machine with hysteresis (open above `open`, the hold
     runs down below `close`) and a hold counter, and a linear gain that glides to g_open or g_closed.  Parameters per
     track {open, close, att, rel, g_open, g_closed, hold} (gate_params makes them from dB and ms); tracks [g link,
@@ -813,54 +820,20 @@ class GatePlan(_Handle):
 
     _destroy = "gab_gate_destroy"
     FIELDS = ("open", "close", "att", "rel", "g_open", "g_closed", "hold")
-
-    def __init__(self, tracks, bufsize, link=1):
-        self.tracks, self.bufsize, self.link = tracks, bufsize, link
-        self._h = C.c_void_p()
-        check(lib.gab_gate_create(C.byref(self._h), tracks, bufsize, link))
-
-    def set_params(self, table, ramp=True, first_track=None):
-        """table: device tensor [tracks][7], or [n][7] for tracks [first_track, first_track + n).
-        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
-        n, rest = divmod(table.numel(), len(self.FIELDS))
-        if rest or n == 0:
-            raise ValueError("table must hold whole rows of 7 values")
-        if first_track is None:
-            if n != self.tracks:
-                raise ValueError("table must hold a row per track (or give first_track)")
-            check(lib.gab_gate_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
-        else:
-            check(lib.gab_gate_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
+    _extra = torch.int32
 
     def reset(self):
         """Every gate shut at target's g_closed, current := target, a pending ramp dropped."""
-        check(lib.gab_gate_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, key=None, out=None, act=None):
         """One buffer, track-major [tracks*bufsize]; out may be x itself.  key: the side chain the detector reads instead
         of x (may not overlap out).  act: an int32 tensor [tracks] that receives the buffer's count of open samples."""
-        assert x.numel() == self.tracks * self.bufsize
-        out = torch.empty_like(x) if out is None else out
-        return self._run(lib.gab_gate_process, x, key, out, act, 1, ())
+        return self._run("process", x, key, out, act, None)
 
     def process_batch(self, xs, key=None, out=None, act=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch; key the same shape, act [n][tracks] int32."""
-        n = _n_buffers(self, xs)
-        out = torch.empty_like(xs) if out is None else out
-        return self._run(lib.gab_gate_process_batch, xs, key, out, act, n, (n,))
-
-    def _run(self, fn, x, key, out, act, n, extra):
-        assert out.numel() == x.numel() and (key is None or key.numel() == x.numel())
-        assert act is None or act.numel() == n * self.tracks
-        check(fn(self._h, _dev(x), None if key is None else _dev(key), _dev(out),
-                 None if act is None else _dev(act, torch.int32), *extra, _stream()))
-        return out
-
-    def params(self):
-        """Copies of (current, target), each [tracks][7]."""
-        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        check(lib.gab_gate_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
-        return _view(a.value, self.tracks, 7).clone(), _view(b.value, self.tracks, 7).clone()
+        return self._run("process_batch", xs, key, out, act, _n_buffers(self, xs))
 
     def state(self):
         """Copies of (the gain [tracks] float32, the count [tracks] int32: -1 while closed)."""
@@ -941,7 +914,7 @@ def reverb_params(rt60_s, rt60_hf_s=None, size_ms=21.5, lines=8, outs=2, wet_db=
     return np.ascontiguousarray(m.astype(np.int32)), np.ascontiguousarray(table)
 
 
-class ReverbPlan(_Handle, _Prepared):
+class ReverbPlan(_TrackPlan, _Prepared):
     """gab_reverb_plan: a feedback delay network per track: `lines` (4, 8, 16) delay lines of integer length fed back
     through a Hadamard matrix with a damping low-pass in the loop, `outs` (1, 2) outputs per track.  Parameters per
     track {g[N], damp[N], b[N], c[outs][N], dry} (reverb_params makes them from decay times) and a delay per line; a
@@ -951,62 +924,38 @@ class ReverbPlan(_Handle, _Prepared):
     _destroy = "gab_reverb_destroy"
 
     def __init__(self, tracks, bufsize, lines=8, outs=2, max_delay=8192):
-        self.tracks, self.bufsize, self.lines, self.outs, self.max_delay = tracks, bufsize, lines, outs, max_delay
+        self.lines, self.outs, self.max_delay = lines, outs, max_delay
         self.row_floats = lines * (3 + outs) + 1
-        self._h = C.c_void_p()
-        check(lib.gab_reverb_create(C.byref(self._h), tracks, bufsize, lines, outs, max_delay))
-
-    def _rows(self, t, width, first_track, what):
-        n, rest = divmod(t.numel(), width)
-        if rest or n == 0:
-            raise ValueError("%s must hold whole rows of %d values" % (what, width))
-        if first_track is None and n != self.tracks:
-            raise ValueError("%s must hold a row per track (or give first_track)" % what)
-        return n
+        self._create(tracks, bufsize, lines, outs, max_delay)
 
     def set_params(self, table, ramp=True, first_track=None):
         """table: device tensor [tracks][row_floats], or [n][row_floats] for tracks [first_track, first_track + n).
         ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
-        n = self._rows(table, self.row_floats, first_track, "table")
-        if first_track is None:
-            check(lib.gab_reverb_set_params(self._h, _dev(table), 1 if ramp else 0, _stream()))
-        else:
-            check(lib.gab_reverb_set_params_tracks(self._h, _dev(table), first_track, n, 1 if ramp else 0, _stream()))
+        n = self._rows(table, self.row_floats, first_track)
+        self._set("params", _dev(table), first_track, n, 1 if ramp else 0)
 
     def set_delays(self, delays, first_track=None):
         """delays: device int32 tensor [tracks][lines], or [n][lines] for tracks [first_track, first_track + n); they
         act from the next buffer and the lines keep their contents."""
         n = self._rows(delays, self.lines, first_track, "delays")
-        if first_track is None:
-            check(lib.gab_reverb_set_delays(self._h, _dev(delays, torch.int32), _stream()))
-        else:
-            check(lib.gab_reverb_set_delays_tracks(self._h, _dev(delays, torch.int32), first_track, n, _stream()))
+        self._set("delays", _dev(delays, torch.int32), first_track, n)
 
     def reset(self):
         """Zero lines, positions and low-pass states, current := target, a pending ramp dropped; the delays stay."""
-        check(lib.gab_reverb_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, out=None):
         """One buffer, track-major [tracks*bufsize] -> [tracks*outs*bufsize]; out may be x itself when outs == 1."""
-        assert x.numel() == self.tracks * self.bufsize
-        out = x.new_empty(x.numel() * self.outs) if out is None else out
-        assert out.numel() == x.numel() * self.outs
-        check(lib.gab_reverb_process(self._h, _dev(x), _dev(out), _stream()))
-        return out
+        return self._process("process", x, out, 1, (x.numel() * self.outs,))
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] -> [n][tracks*outs*bufsize] in one launch."""
         n = _n_buffers(self, xs)
-        out = xs.new_empty(xs.numel() * self.outs) if out is None else out
-        assert out.numel() == xs.numel() * self.outs
-        check(lib.gab_reverb_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
-        return out
+        return self._process("process_batch", xs, out, n, (xs.numel() * self.outs,), n)
 
     def params(self):
         """Copies of (current, target), each [tracks][row_floats]."""
-        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        check(lib.gab_reverb_params(self._h, C.byref(a), C.byref(b), C.byref(n)))
-        return _view(a.value, self.tracks, self.row_floats).clone(), _view(b.value, self.tracks, self.row_floats).clone()
+        return self._tables("params", self.row_floats)
 
     def state(self):
         """Copies of (lines [tracks][lines][capacity] float32, write positions [tracks] int64, low-pass states
@@ -1015,8 +964,8 @@ class ReverbPlan(_Handle, _Prepared):
         check(lib.gab_reverb_state(self._h, C.byref(r), C.byref(cap), C.byref(p), C.byref(q), C.byref(d)))
         T, N = self.tracks, self.lines
         ring = _view(r.value, T * N, cap.value).clone().view(T, N, cap.value)
-        pos = _view(p.value, T, 1).clone().view(torch.int32).to(torch.int64).view(T)
-        return ring, pos, _view(q.value, T, N).clone(), _view(d.value, T, N).clone().view(torch.int32)
+        delays = _view(d.value, T, N).clone().view(torch.int32)
+        return ring, _positions(p.value, T), _view(q.value, T, N).clone(), delays
 
     # prepare(x, out, stream=None): for a loop over the same buffers or a graph capture; all state that changes is on the
     # device, and which kernel form runs (steady, or the ramp form when a ramp is pending) is the host's choice at the
@@ -1024,7 +973,7 @@ class ReverbPlan(_Handle, _Prepared):
     launch = _launcher("gab_reverb_process")
 
 
-class MeterPlan(_Handle, _Prepared):
+class MeterPlan(_TrackPlan, _Prepared):
     """gab_meter_plan: one row of eight levels (FIELDS, all linear) per track and buffer, with carried state: the
     true-peak history, the weighting filter's state, the peak hold and a ring of the last `window` weighted mean
     squares.  The input is only read.  A new plan weighs with BS.1770's K curve at 48 kHz and holds its peak until
@@ -1034,9 +983,8 @@ class MeterPlan(_Handle, _Prepared):
     FIELDS = ("peak", "true_peak", "ms", "kms", "peak_hold", "true_peak_max", "kms_window", "nonfinite")
 
     def __init__(self, tracks, bufsize, window=1):
-        self.tracks, self.bufsize, self.window = tracks, bufsize, window
-        self._h = C.c_void_p()
-        check(lib.gab_meter_create(C.byref(self._h), tracks, bufsize, window))
+        self.window = window
+        self._create(tracks, bufsize, window)
 
     def set_weighting(self, sections):
         """sections: device tensor [2][5] = {b0, b1, b2, a1, a2} (a0 = 1), the same for every track; in force from
@@ -1050,39 +998,29 @@ class MeterPlan(_Handle, _Prepared):
 
     def reset(self):
         """Every carried value zero; the weighting and the decay stay."""
-        check(lib.gab_meter_reset(self._h, _stream()))
+        super().reset()
 
     def process(self, x, out=None):
         """One buffer, track-major [tracks*bufsize]; returns the rows [tracks][8]."""
-        assert x.numel() == self.tracks * self.bufsize
-        if out is None:
-            out = torch.empty(self.tracks, len(self.FIELDS), dtype=torch.float32, device=x.device)
-        assert out.numel() == self.tracks * len(self.FIELDS)
-        check(lib.gab_meter_process(self._h, _dev(x), _dev(out), _stream()))
-        return out
+        return self._process("process", x, out, 1, (self.tracks, len(self.FIELDS)))
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch; returns the rows [n][tracks][8]."""
         n = _n_buffers(self, xs)
-        if out is None:
-            out = torch.empty(n, self.tracks, len(self.FIELDS), dtype=torch.float32, device=xs.device)
-        assert out.numel() == n * self.tracks * len(self.FIELDS)
-        check(lib.gab_meter_process_batch(self._h, _dev(xs), _dev(out), n, _stream()))
-        return out
+        return self._process("process_batch", xs, out, n, (n, self.tracks, len(self.FIELDS)), n)
 
     def state(self):
         """Copies of (hist [tracks][16] = the last 11 samples, peak_hold, true_peak_max, 3 zeros; filter
         [tracks][2][2] = (s1, s2) per section; ring [tracks][window]; pos [tracks] int64)."""
         h, f, r, p = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         check(lib.gab_meter_state(self._h, C.byref(h), C.byref(f), C.byref(r), C.byref(p)))
-        pos = _view(p.value, self.tracks, 1).clone().view(torch.int32).to(torch.int64).view(self.tracks)
         return (_view(h.value, self.tracks, 16).clone(), _view(f.value, self.tracks, 4).clone().view(self.tracks, 2, 2),
-                _view(r.value, self.tracks, self.window).clone(), pos)
+                _view(r.value, self.tracks, self.window).clone(), _positions(p.value, self.tracks))
 
     launch = _launcher("gab_meter_process")
 
 
-class ResamplePlan(_Handle):
+class ResamplePlan(_TrackPlan):
     """gab_resample_plan: every track's stream from one sample rate to another by up / down (reduced by their gcd), a
     polyphase FIR of `ntaps` taps per phase with carried history and an exact carried position.  A buffer of `bufsize`
     input samples gives floor or ceil of bufsize * up / down output samples; `out_capacity` is the ceil, and the rest
@@ -1094,9 +1032,7 @@ class ResamplePlan(_Handle):
     def __init__(self, tracks, bufsize, up, down, taps=None):
         if taps is None:
             taps = self.default_taps(up, down)
-        self.tracks, self.bufsize = tracks, bufsize
-        self._h = C.c_void_p()
-        check(lib.gab_resample_create(C.byref(self._h), tracks, bufsize, up, down, taps))
+        self._create(tracks, bufsize, up, down, taps)
         v = [C.c_int(0) for _ in range(5)]
         check(lib.gab_resample_shape(self._h, *[C.byref(c) for c in v]))
         self.up, self.down, self.ntaps, self.out_capacity, self.period = (c.value for c in v)
@@ -1121,7 +1057,7 @@ class ResamplePlan(_Handle):
 
     def reset(self):
         """Zero history, position 0; the taps stay."""
-        check(lib.gab_resample_reset(self._h, _stream()))
+        super().reset()
 
     def set_taps(self, t):
         """t: device tensor [up][ntaps]; in force from the next buffer, history and position are kept."""
@@ -1131,22 +1067,14 @@ class ResamplePlan(_Handle):
     def process(self, x, out=None):
         """One buffer, track-major [tracks*bufsize]; returns (out [tracks][out_capacity], n_out): the first n_out
         elements of every row are samples, the rest zeros."""
-        assert x.numel() == self.tracks * self.bufsize
-        if out is None:
-            out = torch.empty(self.tracks, self.out_capacity, dtype=torch.float32, device=x.device)
-        assert out.numel() == self.tracks * self.out_capacity
         n = C.c_int(0)
-        check(lib.gab_resample_process(self._h, _dev(x), _dev(out), C.byref(n), _stream()))
-        return out, n.value
+        return self._process("process", x, out, 1, (self.tracks, self.out_capacity), C.byref(n)), n.value
 
     def process_batch(self, xs, out=None):
         """Consecutive buffers [n][tracks*bufsize] in one launch; returns (out [n][tracks][out_capacity], counts)."""
         n = _n_buffers(self, xs)
-        if out is None:
-            out = torch.empty(n, self.tracks, self.out_capacity, dtype=torch.float32, device=xs.device)
-        assert out.numel() == n * self.tracks * self.out_capacity
         counts = (C.c_int * max(n, 1))()
-        check(lib.gab_resample_process_batch(self._h, _dev(xs), _dev(out), n, counts, _stream()))
+        out = self._process("process_batch", xs, out, n, (n, self.tracks, self.out_capacity), n, counts)
         return out, list(counts[:n])
 
     def _state(self):

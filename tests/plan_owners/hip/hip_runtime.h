@@ -1,11 +1,13 @@
-// A stand-in for <hip/hip_runtime.h>, for tests/plan_owners/owners_main.cpp alone: the few entry points gab_plan.hpp
-// uses, as counting stubs, so that the owners can be exercised by a host compiler under a sanitizer without a GPU.
-// Every create hands out a fresh heap block as its handle and records it; every destroy must name a live handle of
-// its own kind.  stub::fail_after(n) makes the n-th create from now fail.
+// A stand-in for <hip/hip_runtime.h>, for the programs of tests/plan_owners alone: the few entry points gab_plan.hpp
+// uses, as counting stubs, so that the owners and the entries can be exercised by a host compiler under a sanitizer
+// without a GPU.  Every create hands out a fresh heap block as its handle and records it; every destroy must name a
+// live handle of its own kind; a blocking copy copies (device memory is the heap here).  stub::fail_after(n) makes the
+// n-th create from now fail.
 #pragma once
 
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 
 #define __host__
@@ -78,5 +80,8 @@ inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *
 inline hipError_t hipStreamDestroy(hipStream_t s) { return stub::destroy(stub::kStream, s); }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { return hipSuccess; }
-inline hipError_t hipMemcpy(void*, const void*, size_t, hipMemcpyKind) { return hipSuccess; }
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
 inline hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) { return hipSuccess; }

@@ -1,9 +1,12 @@
-"""The owners of gab_plan.hpp under AddressSanitizer and UBSan, on the host alone.
+"""The owners and the entry bodies of gab_plan.hpp under AddressSanitizer and UBSan, on the host alone.
 
 tests/plan_owners/owners_main.cpp includes gab_plan.hpp with tests/plan_owners/hip/hip_runtime.h standing in for the
 runtime (counting stubs, found first on the include path).  The program moves, re-allocates, swaps and half-builds
 every owner and asserts that creates equal destroys and that no handle is destroyed twice; the sanitizers watch the
-memory behind the handles.  Nothing here touches a GPU or is loaded into Python.
+memory behind the handles.  tests/plan_owners/entries_main.cpp drives the bodies of the plans' extern "C" functions
+(create_entry, entry, batch_entry, expose_entry) and the small helpers beside them with a fake plan: the texts, the
+codes, the order of the checks, and that a refused or half-built create leaves null and nothing else behind.  Nothing
+here touches a GPU or is loaded into Python.
 """
 import os
 import shutil
@@ -23,7 +26,8 @@ def _compiler():
     return None
 
 
-def test_plan_owners_under_sanitizers(tmp_path):
+def _run_under_sanitizers(tmp_path, source, ok):
+    """Builds tests/plan_owners/<source> with the sanitizers and runs it; its output starts with `ok`."""
     cxx = _compiler()
     if cxx is None:
         pytest.skip("no host C++ compiler")
@@ -38,11 +42,19 @@ def test_plan_owners_under_sanitizers(tmp_path):
     cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wno-self-move", "-Wno-unused-function"] + sanitize + [
         "-I" + HERE,                                          # hip/hip_runtime.h: the stand-in, ahead of any real one
         "-I" + os.path.join(ROOT, "gpuaudiobench_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-        os.path.join(HERE, "owners_main.cpp"), "-o", str(exe)]
+        os.path.join(HERE, source), "-o", str(exe)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    assert r.stdout.startswith("plan owners ok:"), r.stdout
+    assert r.stdout.startswith(ok), r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+
+
+def test_plan_owners_under_sanitizers(tmp_path):
+    _run_under_sanitizers(tmp_path, "owners_main.cpp", "plan owners ok:")
+
+
+def test_plan_entries_under_sanitizers(tmp_path):
+    _run_under_sanitizers(tmp_path, "entries_main.cpp", "plan entries ok:")
