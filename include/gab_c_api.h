@@ -210,7 +210,14 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd,
             gab_stream_t stream);
 
 /* cufftExecR2C, N=1024, batch = tracks (cuda/bench_fft.cu:63,105):
- * d_in tracks x 1024 real, d_out tracks x 513 interleaved complex.           */
+ * d_in tracks x 1024 real, d_out tracks x 513 interleaved complex.
+ * Channel pairs.  Tracks 2q and 2q+1 share one complex transform (z = x_a + i x_b; an odd last track beside
+ * zeros), so a track's absolute error in any bin is bounded by its PAIR's spectral peak, not its own: measured
+ * 2.7e-7 .. 3.5e-7 of (peak_a + peak_b), a plain float32 restatement 1.0e-7 .. 1.25e-7 (profiles/r18_conv_levels.txt;
+ * tests/test_fft_levels_gpu.py holds the kernel within four times the restatement).  A silent track beside a loud
+ * partner is not silent: it holds the partner's rounding error, -131 dB of the partner's peak.  A silent pair gives
+ * zeros.  A pair depends on nothing outside itself, bit for bit; a NaN or an infinity in one track makes its
+ * partner's spectrum non-finite too and touches no other pair.                                              */
 int gab_fft_r2c_1024(const float* d_in, float* d_out, int tracks,
                      gab_stream_t stream);
 
@@ -248,6 +255,31 @@ typedef struct gab_conv_plan gab_conv_plan;
  * previous block; the plan's scratch — partial sums, a stateless call's spectrum — is not counted).  The round-trip, newest-block and engine entries, and set_scheme to another cut, refuse
  * with GAB_ERR_INVALID_ARG and leave the plan usable.                                                 */
 #define GAB_CONV_SCHEME_FDL 2
+/* Channel pairs.  Every FFT route — CLASSIC, SPLIT (their batch, host-I/O, round-trip and engine launches too), the
+ * taps <= 512 cut, the uniform-partition kernel and FDL — packs channels 2q and 2q+1 into one complex transform,
+ * z = x_a + i x_b (an odd last channel beside zeros); the direct form packs nothing.  What follows from that, as
+ * measured per channel at unequal levels (profiles/r18_conv_levels.txt, tools/conv_levels.py) and held by
+ * tests/test_conv_levels_gpu.py:
+ *   - a channel's absolute error is bounded by its PAIR's level, not its own: a few 1e-7 of
+ *     (peak_a + peak_b), the two channels' output peaks (measured 3.0e-7 .. 4.2e-7 on the 512-sample cuts and FDL,
+ *     5.6e-7 .. 6.1e-7 on the uniform kernel; a plain float32 restatement of the same cuts loses 2.0e-7 .. 2.6e-7,
+ *     and the tests hold every route within four times its restatement).  A channel 2^-20 below its partner
+ *     therefore carries an error near 0.1 of its own peak; a pair whose channels are both quiet is as accurate,
+ *     relative to itself, as a loud one.  The direct form: 1.3e-6 of the channel's own peak at 700 taps.
+ *   - a silent channel beside a loud partner is NOT silent: it holds the partner's rounding error, -129 .. -140 dB
+ *     of the partner's peak (-138 .. -142 dB in the restatement).  On the direct form it is zeros.
+ *   - a pair whose two channels are silent gives zeros (of either sign), whatever the other pairs carry.
+ *   - a pair's output depends on nothing outside the pair, bit for bit: not on the other pair of a SPLIT duo (which
+ *     shares its workgroup and LDS), not on the level or content of any other channel.
+ *   - a NaN or an infinity in one input sample makes BOTH channels of its pair non-finite, in every buffer whose
+ *     transforms hold the sample, and touches no other pair.  The pair is the clean stream's bits again after
+ *     exactly 2 buffers (the struck one included) with taps <= 512, 9 on CLASSIC, 10 or 9 on SPLIT (its far window is
+ *     a block longer than its taps and is transformed a buffer ahead, for a pair every other buffer: which of the two
+ *     depends on whether the strike meets the pair's turn), (4096 + B + (J-2)(4096-B)) / B on the uniform kernel
+ *     with J > 1 partitions (4096 / B with one; 17, 17 and 129 buffers at 256 x 3000, 1024 x 16384 and 32 x 700),
+ *     K + 1 on FDL; the direct form keeps it at most ceil((ir_len-1) / bufsize) + 1 buffers, in the struck channel
+ *     alone.  While it lasts, gab_conv_process_batch and per-buffer launches agree in which values are NaN, not in
+ *     the NaNs' sign bits (SPLIT).                                                                              */
 int gab_conv_set_scheme(gab_conv_plan* plan, int scheme);
 int gab_conv_get_scheme(const gab_conv_plan* plan, int* scheme);
 #define GAB_CONV_STREAMING_HOST_IO 2  /* the same, d_in / d_out in pinned host memory: identical kernel
