@@ -631,7 +631,10 @@ int gab_eq_form(const gab_eq_plan* plan, int* samples_per_lane, int* segments);
  *                  current, the audible gains.
  *     set_gains(ramp = 0)  current := target := the new matrix, at once.
  *     set_gains_tracks     the same for rows [first_track, first_track + n_tracks), d_gains [n_tracks][buses]; the other
- *                  rows keep their current and target.
+ *                  rows keep their current and target.  Whether a ramp is pending is one fact of the whole plan, which a
+ *                  set with ramp = 0 does not change: on rows whose ramp is pending it puts current and target at the new
+ *                  values at once, and the next buffer still ramps every other row from its current to its target.  (So
+ *                  for every plan with a ramped table: delay, dynamics, reverb, gate.)
  *                  A value that is not finite: GAB_ERR_INVALID_ARG naming the first such (track, bus); the plan keeps
  *                  what it had.  Both are synchronous with respect to `stream` and take effect with the next buffer.
  *     reset        current := target (a pending ramp is dropped).      gains: the plan's own two arrays, for inspection.

@@ -8,13 +8,18 @@ payload.  Each tape runs twice, by per-buffer calls and with every run of consec
 cases marked `offset` pass every block through a pointer 4 bytes off 16-byte alignment.  That the cases hold subnormals,
 infinities, NaNs and -0.0 at all is established on the host (test_the_cases_reach_the_edge); nothing here asserts it.
 """
+import types
+
 import numpy as np
 import pytest
 
 from plan_helpers import dev, gab, host  # noqa: F401 (gab: the fixture)
 from strip_helpers import DeviceStrip, differing as strip_differing, same, schedule, states_differing
 from test_delay_host import capacity as delay_capacity
-from test_edges_host import CASES, case_id, differing, mix_form, play, reference, strip_tail
+from test_edges_host import (CASES, case_id, delay_first_refused, differing, dyn_first_refused, mix_first_refused,
+                             mix_form, play, reference, strip_tail)
+from test_gate_host import gate_first_refused
+from test_reverb_host import first_refused_param as reverb_first_refused
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +51,10 @@ class Blocks:
 
 
 class Dev:
-    """What the device actors share: run() is a process call, run_batch() one process_batch over the buffers."""
+    """What the device actors share: run() is a process call, run_batch() one process_batch over the buffers.
+    inplace (where the header allows d_out == d_in): a process call writes over its input block."""
+
+    inplace = False
 
     def __init__(self, gab, offset):
         self.gab, self.mem = gab, Blocks(offset)
@@ -63,6 +71,33 @@ class Dev:
     def params(self, p, ramp):
         self.p.set_params(dev(p), ramp=ramp)
 
+    def params_tracks(self, p, first_track, ramp):
+        self.p.set_params(dev(p), ramp=ramp, first_track=first_track)
+
+    def named(self, i, first_track, width):
+        """How the plan's refusal names value i of rows `width` wide (gab_plan.hpp, row_refusal)."""
+        return "track %d field %d (" % (first_track + i // width, i % width)
+
+    def refused(self, p, first_track, ramp):
+        """The tape's refused set: refused here too, and the text names the value the host rule names."""
+        i = self.rule(p)
+        assert i is not None
+        with pytest.raises(self.gab.GabError) as e:
+            (self.gains_tracks if hasattr(self, "gains_tracks") else self.params_tracks)(p, first_track, ramp)
+        assert e.value.code == -1 and self.named(i, first_track, p.shape[1]) in str(e.value), (str(e.value), i)
+
+    def check(self, want):
+        """The tape's check marker: the carried state here is the host actor's there.  (The windows of the delay and
+        reverb rings are found from the recorded position.)"""
+        sync()
+        assert differing([self.state(self.twin_at(want))], [want]) == []
+        self.checked = getattr(self, "checked", 0) + 1
+
+    def twin_at(self, want):
+        """What state() asks of the host actor, from a recorded state (the delay and reverb actors: where their rings
+        stand)."""
+        return None
+
     def close(self):
         self.p.close()
 
@@ -75,6 +110,15 @@ class DevMix(Dev):
 
     def gains(self, g, ramp):
         self.p.set_gains(dev(g), ramp=ramp)
+
+    def gains_tracks(self, g, first_track, ramp):
+        self.p.set_gains(dev(g), ramp=ramp, first_track=first_track)
+
+    def rule(self, g):
+        return mix_first_refused(g)
+
+    def named(self, i, first_track, width):
+        return "track %d bus %d is" % (first_track + i // width, i % width)
 
     def launch(self, xs, keys, batch):
         n, (M, B) = len(xs), self.shape
@@ -94,9 +138,17 @@ class DevDelay(Dev):
         Dev.__init__(self, gab, offset)
         self.p, self.shape = gab.DelayPlan(T, B, M, interp), (T, B, M)
 
+    def rule(self, p):
+        return delay_first_refused(p, self.p.interp, self.p.max_delay)
+
+    def twin_at(self, want):
+        line = types.SimpleNamespace(count=int(want["pos"][0]), hist=want["line"])   # (the count mod the capacity)
+        return types.SimpleNamespace(twin=types.SimpleNamespace(line=line))
+
     def launch(self, xs, keys, batch):
         n, (T, B, M) = len(xs), self.shape
-        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * B)
+        x = self.mem.put(np.stack(xs))
+        out = x if self.inplace else self.mem.blank(n * T * B)
         (self.p.process_batch if batch else self.p.process)(x, out=out)
         return [{"y": y} for y in host(out).reshape(n, T, B)]
 
@@ -137,6 +189,9 @@ class DevResample(Dev):
         self.p, self.shape = gab.ResamplePlan(T, B, up, down, K), (T, B)
         assert self.p.ntaps == K
 
+    def taps(self, t):
+        self.p.set_taps(dev(t))
+
     def launch(self, xs, keys, batch):
         n, (T, B), OC = len(xs), self.shape, self.p.out_capacity
         x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * OC)
@@ -156,10 +211,14 @@ class DevDyn(Dev):
         Dev.__init__(self, gab, offset)
         self.p, self.shape = gab.DynamicsPlan(T, B, link), (T, B)
 
+    def rule(self, p):
+        return dyn_first_refused(p)
+
     def launch(self, xs, keys, batch):
         n, (T, B) = len(xs), self.shape
         assert all(k is None for k in keys) or all(k is not None for k in keys)
-        x, out, gr = self.mem.put(np.stack(xs)), self.mem.blank(n * T * B), self.mem.blank(n * T)
+        x, gr = self.mem.put(np.stack(xs)), self.mem.blank(n * T)
+        out = x if self.inplace else self.mem.blank(n * T * B)
         key = None if keys[0] is None else self.mem.put(np.stack(keys))
         (self.p.process_batch if batch else self.p.process)(x, key=key, out=out, gr=gr)
         return [{"y": y, "gr": g} for y, g in zip(host(out).reshape(n, T, B), host(gr).reshape(n, T))]
@@ -177,9 +236,23 @@ class DevReverb(Dev):
     def delays(self, d):
         self.p.set_delays(dev(d))
 
+    def delays_tracks(self, d, first_track):
+        self.p.set_delays(dev(d), first_track=first_track)
+
+    def rule(self, p):
+        return reverb_first_refused(p, self.p.lines, self.shape[2])
+
+    def twin_at(self, want):
+        cap = 1
+        while cap < self.shape[3] + 64:
+            cap *= 2
+        return types.SimpleNamespace(twin=types.SimpleNamespace(pos=int(want["pos"][0]), cap=cap))
+
     def launch(self, xs, keys, batch):
         n, (T, B, O, M) = len(xs), self.shape
-        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * T * O * B)
+        x = self.mem.put(np.stack(xs))
+        assert O == 1 or not self.inplace
+        out = x if self.inplace else self.mem.blank(n * T * O * B)
         (self.p.process_batch if batch else self.p.process)(x, out=out)
         return [{"y": y} for y in host(out).reshape(n, T * O, B)]
 
@@ -193,7 +266,32 @@ class DevReverb(Dev):
                 "lines": ring[:, :, (rv.pos - M + np.arange(M)) & (cap - 1)]}   # the newest max_delay words
 
 
-DEVS = {"mix": DevMix, "delay": DevDelay, "meter": DevMeter, "resample": DevResample, "dyn": DevDyn, "reverb": DevReverb}
+class DevGate(Dev):
+    def __init__(self, gab, offset, T, B, link, keyed):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.GatePlan(T, B, link), (T, B)
+
+    def rule(self, p):
+        return gate_first_refused(p)
+
+    def launch(self, xs, keys, batch):
+        import torch
+        n, (T, B) = len(xs), self.shape
+        assert all(k is None for k in keys) or all(k is not None for k in keys)
+        x = self.mem.put(np.stack(xs))
+        out = x if self.inplace else self.mem.blank(n * T * B)
+        act = torch.full((n * T,), 7, dtype=torch.int32, device="cuda")
+        key = None if keys[0] is None else self.mem.put(np.stack(keys))
+        (self.p.process_batch if batch else self.p.process)(x, key=key, out=out, act=act)
+        return [{"y": y, "act": a} for y, a in zip(host(out).reshape(n, T, B), host(act).reshape(n, T))]
+
+    def state(self, twin):
+        (cur, tgt), (g, c) = self.p.params(), self.p.state()
+        return {"current": host(cur), "target": host(tgt), "gain": host(g), "count": host(c)}
+
+
+DEVS = {"mix": DevMix, "delay": DevDelay, "meter": DevMeter, "resample": DevResample, "dyn": DevDyn, "reverb": DevReverb,
+        "gate": DevGate}
 
 
 def run_on_device(gab, case, ops, batch):

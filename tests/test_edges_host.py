@@ -46,12 +46,15 @@ from test_delay_host import capacity as delay_capacity
 from test_delay_host import delay_mix
 from test_dynamics_host import Twin as DynTwin
 from test_dynamics_host import dyn_mix
+from test_gate_host import Twin as GateTwin
+from test_gate_host import gate_first_refused
 from test_meter_host import Twin as MeterTwin
 from test_mix_host import Twin as MixTwin
 from test_mix_host import gains, round32_exact
 from test_resample_host import Twin as ResampleTwin
 from test_reverb_host import MIN_DELAY as REVERB_MIN_DELAY
 from test_reverb_host import Twin as ReverbTwin
+from test_reverb_host import first_refused_param as reverb_first_refused
 from test_reverb_host import reverb_mix
 
 f32 = np.float32
@@ -223,12 +226,71 @@ def quiet(*arrays):
     return all(bool((np.abs(a) < TINY).all()) for a in arrays)
 
 
-class HostMix:
+def mix_first_refused(g):
+    """The host twins of the device rules that had none yet (k_mix.hip, k_delay.hip, k_dynamics.hip; the contract's
+    column `admitted` in include/gab_c_api.h): the index into the flat table of the first refused value, or None."""
+    hits = np.flatnonzero(~np.isfinite(np.asarray(g, np.float32).ravel()))
+    return int(hits[0]) if hits.size else None
+
+
+def delay_first_refused(p, interp, max_delay):
+    t = np.asarray(p, np.float32).reshape(-1, 4)
+    with np.errstate(invalid="ignore"):
+        bad = ~np.isfinite(t)
+        bad[:, 0] |= ~((t[:, 0] >= f32(2 if interp == "lagrange3" else 1)) & (t[:, 0] <= f32(max_delay)))
+        bad[:, 1] |= ~(np.abs(t[:, 1]) < f32(1.0))
+    hits = np.flatnonzero(bad.ravel())
+    return int(hits[0]) if hits.size else None
+
+
+def dyn_first_refused(p):
+    t = np.asarray(p, np.float32).reshape(-1, 8)
+    cap = f32(1.0 - 2.0 ** -20)
+    with np.errstate(invalid="ignore"):
+        bad = ~np.isfinite(t)
+        bad[:, 0] |= ~(np.abs(t[:, 0]) <= f32(128.0))
+        bad[:, 1] |= ~((t[:, 1] >= f32(-1.0)) & (t[:, 1] <= 0))
+        bad[:, 2] |= ~((t[:, 2] >= 0) & (t[:, 2] <= f32(64.0)))
+        bad[:, 3] |= ~(t[:, 3] >= 0)
+        bad[:, 4] |= ~((t[:, 4] >= 0) & (t[:, 4] <= cap))
+        bad[:, 5] |= ~((t[:, 5] >= 0) & (t[:, 5] <= cap))
+        bad[:, 7] |= ~(t[:, 7] <= 0)
+    hits = np.flatnonzero(bad.ravel())
+    return int(hits[0]) if hits.size else None
+
+
+class Host:
+    """What the host actors share: the two markers of a tape, a batch as its buffers one by one, and a refused set, which
+    the plan's host rule must refuse and which changes nothing."""
+
+    def cut(self):
+        pass
+
+    def check(self, want=None):
+        self.__dict__.setdefault("checks", []).append(self.state())
+
+    def run_batch(self, xs, keys):
+        return [self.run(x, k) for x, k in zip(xs, keys)]
+
+    def refused(self, p, first_track, ramp):
+        assert self.rule(p) is not None
+
+    def params_tracks(self, p, first_track, ramp):
+        self.twin.set_params(p, ramp=ramp, first_track=first_track)
+
+
+class HostMix(Host):
     def __init__(self, T, B, M, layout="track"):
         self.twin = MixTwin(T, B, M, *mix_form(M))
 
     def gains(self, g, ramp):
         self.twin.set_gains(g, ramp=ramp)
+
+    def gains_tracks(self, g, first_track, ramp):
+        self.twin.set_gains(g, ramp=ramp, first=first_track)
+
+    def rule(self, g):
+        return mix_first_refused(g)
 
     def reset(self):
         self.twin.reset()
@@ -244,12 +306,15 @@ class HostMix:
         return True
 
 
-class HostDelay:
+class HostDelay(Host):
     def __init__(self, T, B, M, interp):
         self.twin = DelayTwin(T, B, M, interp)
 
     def params(self, p, ramp):
         self.twin.set_params(p, ramp=ramp)
+
+    def rule(self, p):
+        return delay_first_refused(p, self.twin.interp, self.twin.M)
 
     def reset(self):
         self.twin.reset()
@@ -277,7 +342,7 @@ class FlushedDelay(HostDelay):
         return out
 
 
-class HostMeter:
+class HostMeter(Host):
     def __init__(self, T, B, W):
         self.twin = MeterTwin(T, B, W)
 
@@ -301,9 +366,12 @@ class HostMeter:
         return quiet(t.hist, t.hold, t.filter, t.ring)
 
 
-class HostResample:
+class HostResample(Host):
     def __init__(self, T, B, up, down, K):
         self.twin = ResampleTwin(T, B, up, down, K=K)
+
+    def taps(self, t):
+        self.twin.set_taps(t)
 
     def reset(self):
         self.twin.reset()
@@ -320,12 +388,15 @@ class HostResample:
         return True
 
 
-class HostDyn:
+class HostDyn(Host):
     def __init__(self, T, B, link, keyed):
         self.twin = DynTwin(T, B, link)
 
     def params(self, p, ramp):
         self.twin.set_params(p, ramp=ramp)
+
+    def rule(self, p):
+        return dyn_first_refused(p)
 
     def reset(self):
         self.twin.reset()
@@ -342,7 +413,7 @@ class HostDyn:
         return quiet(self.twin.s)
 
 
-class HostReverb:
+class HostReverb(Host):
     def __init__(self, T, B, N, O, M):
         self.twin = ReverbTwin(T, B, N, O, M)
 
@@ -351,6 +422,12 @@ class HostReverb:
 
     def delays(self, d):
         self.twin.set_delays(d)
+
+    def delays_tracks(self, d, first_track):
+        self.twin.set_delays(d, first_track=first_track)
+
+    def rule(self, p):
+        return reverb_first_refused(p, self.twin.N, self.twin.O)
 
     def reset(self):
         self.twin.reset()
@@ -367,8 +444,34 @@ class HostReverb:
         return quiet(self.twin.hist, self.twin.q)
 
 
+class HostGate(Host):
+    def __init__(self, T, B, link, keyed):
+        self.twin = GateTwin(T, B, link)
+
+    def params(self, p, ramp):
+        self.twin.set_params(p, ramp=ramp)
+
+    def rule(self, p):
+        return gate_first_refused(p)
+
+    def reset(self):
+        self.twin.reset()
+
+    def run(self, x, key=None):
+        with np.errstate(invalid="ignore", over="ignore"):
+            y, act = self.twin.process(x, key)
+        return {"y": y, "act": act}
+
+    def state(self):
+        t = self.twin
+        return {"current": t.cur.copy(), "target": t.tgt.copy(), "gain": t.g.copy(), "count": t.c.copy()}
+
+    def dead(self):
+        return True
+
+
 HOSTS = {"mix": HostMix, "delay": HostDelay, "meter": HostMeter, "resample": HostResample, "dyn": HostDyn,
-         "reverb": HostReverb}
+         "reverb": HostReverb, "gate": HostGate}
 
 
 def lvl(rng, shape, e):
@@ -621,7 +724,9 @@ def reference(case, dirty=True):
 
 
 def play(ops, actor, batch=False):
-    """The tape on another actor; batch: consecutive run() calls go to run_batch(xs, keys) as one.  Returns the outputs."""
+    """The tape on another actor; batch: consecutive run() calls go to run_batch(xs, keys) as one.  Returns the outputs.
+    Two markers (tests/walks.py): ("cut",) ends the current batch and is not passed on; ("check", state) is passed on
+    behind the batch, as every call that is not a run() is: a device actor compares its carried state there."""
     outs, pending = [], []
 
     def flush():
@@ -635,6 +740,8 @@ def play(ops, actor, batch=False):
             pending.append(op[1:])
             continue
         flush()
+        if op[0] == "cut":
+            continue
         r = getattr(actor, op[0])(*op[1:])
         if op[0] == "run":
             outs.append(r)

@@ -30,7 +30,17 @@ SHAPES = [(160, 147, None, 3, 7, 23),       # period 21
           (1, 1, None, 65, 64, 3),
           (4, 6, None, 3, 7, 5),
           (16, 1, 8, 3, 100, 2),            # 1024 outputs of a 64-sample chunk
-          (1, 1, 256, 3, 100, 3)]
+          (1, 1, 256, 3, 100, 3),
+          # positions the ratios above do not reach (tests/test_resample_host.py, TAPS)
+          (2, 5, 16, 66, 100, 5),           # M/L = 2 and M mod L = 1: both increments at once
+          (5, 2, 6, 66, 65, 3),             # M mod L = 2 of 5 at the row pitch of K mod 4 = 2; counts 163, 162, 163
+          (7, 3, 12, 130, 1, 9),            # bufsize 1: counts 3, 2, 2, period 3
+          (3, 200, 8, 3, 64, 12),           # M/L = 66: one output per 64-sample buffer at most, period 25
+          (3, 64, 64, 3, 65, 4),            # M/L = 21, M mod L = 1, period 64
+          (1, 65, 8, 65, 64, 4),            # one output per buffer, a sample later each time; period 65
+          (1, 1024, 4, 3, 100, 24),         # 21 of 24 buffers without an output
+          (64, 1, 256, 2, 7, 3),            # the largest table and tile; 448 outputs of a 7-sample chunk
+          (1000, 1024, 16, 3, 513, 2)]      # reduces to 125/128, period 128
 
 
 def ident(s):
@@ -104,7 +114,16 @@ def test_four_sixths_reports_two_thirds(gab):
 @pytest.mark.parametrize("shape,cut", [((160, 147, None, 3, 7, 23), 12),     # the second launch crosses the period
                                        ((147, 160, None, 65, 100, 10), 3),
                                        ((1, 2, None, 130, 1, 6), 1),
-                                       ((160, 147, None, 130, 513, 3), 2)], ids=lambda v: ident(v) if isinstance(v, tuple) else str(v))
+                                       ((160, 147, None, 130, 513, 3), 2),
+                                       ((2, 5, 16, 66, 100, 5), 2),
+                                       ((5, 2, 6, 66, 65, 3), 1),
+                                       ((7, 3, 12, 130, 1, 9), 4),          # across the period
+                                       ((3, 200, 8, 3, 64, 12), 5),
+                                       ((3, 64, 64, 3, 65, 4), 1),
+                                       ((1, 65, 8, 65, 64, 4), 3),
+                                       ((1, 1024, 4, 3, 100, 24), 11),      # both launches start between two outputs
+                                       ((64, 1, 256, 2, 7, 3), 2),
+                                       ((1000, 1024, 16, 3, 513, 2), 1)], ids=lambda v: ident(v) if isinstance(v, tuple) else str(v))
 def test_batch_equals_single_calls(gab, shape, cut):
     xs, rows, counts, hist, k = case(shape)
     plan = make(gab, shape)
@@ -159,7 +178,8 @@ def test_reset_gives_a_new_plan(gab, shape):
     plan.close()
 
 
-@pytest.mark.parametrize("shape", [(160, 147, None, 65, 64, 4), (3, 2, 6, 3, 100, 4)], ids=ident)
+@pytest.mark.parametrize("shape", [(160, 147, None, 65, 64, 4), (3, 2, 6, 3, 100, 4), (2, 5, 16, 66, 100, 5),
+                                   (3, 200, 8, 3, 64, 12)], ids=ident)
 def test_set_taps_mid_stream_one_hot_selects_exactly(gab, shape):
     """After two buffers the table becomes one-hot, row p at j = (3 p) mod K: every later output is the input sample
     w[i - j] itself, i and p from exact integers here, no restatement involved; history and position were kept."""
