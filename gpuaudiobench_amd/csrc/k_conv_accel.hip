@@ -921,8 +921,16 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 //     to the next, and no longer ask the L2 for 33 KB per duo and period;
 //   * the far waves keep the LAST pass's twiddle powers in registers (30) and read the middle pass's (16 distinct sets)
 //     from a 1.9 KB table in LDS, formed at entry by the same powers_of;
-//   * the A2 share waits in the hand-over image (written behind barrier 1, summed into behind barrier 5) instead of in
-//     32 registers; spectral products run in halves of eight bins.
+//   * spectral products run in halves of eight bins, and the two near products of a pair (A2 share, A product) are DIVIDED
+//     between the pair's two near waves: the forward wave forms bins 0-7 per lane, the inverse wave — which had 1.9 us of work
+//     in a 4.9 us period against the forward wave's 3.1, on another SIMD — bins 8-15, both from the spectrum in the forward
+//     wave's image (written BEFORE barrier 4, read by the inverse wave behind it and, for the A2 share, before the next
+//     period's barrier 1).  Same calls on the same values, only another wave: the same bits.  Each half's A2 share waits a
+//     period for its A product: the forward wave's in sixteen registers, the inverse wave's (which has none to spare while
+//     it transforms) in bins 8-15 of the hand-over image; the forward wave writes the sum of its bins into the hand-over
+//     image behind barrier 5, the inverse wave keeps the sum of its own bins in registers: they are its own input a period
+//     later.  One workgroup barrier per LAUNCH separates the forward waves' prologue from the first period, whose A2
+//     share the inverse wave forms from the prologue's spectrum (profiles/r19_near_products.txt).
 // The far role's schedule per transform (window nb, periods nb and nb + 1; the other group is one period out of step, so a
 // heavy interval of one meets a light one of the other):
 //   period nb:      pass 0 + write | read, pass 1 | write | read, pass 2 | partner write | partner read, product, inverse pass 0
@@ -952,6 +960,18 @@ __device__ __forceinline__ void spectral_product_part(cf (&z)[R], const cf (&zra
         if (r > R / 2 || (r == R / 2 && tid != 0)) z[r] = fft::cfma_cjcj(zraw[r - R0], M, fft::cmulc(z[r], P));
         else z[r] = fft::cfma_cj(zraw[r - R0], M, fft::cmul(z[r], P));
     }
+}
+// Bins [R0, R1) per lane of a near product W = Z x spectra, for whichever of a pair's two near waves holds them in v: the
+// partner values Z[(N - k) mod N] from the forward wave's image `fimg` (the spectrum as it lies there, padded), the spectra from LDS.
+// Partner values and spectra of one half (eight bins) are what a wave holds at a time.
+template <int R0, int R1>
+__device__ __forceinline__ void near_product_half(cf (&v)[16], const cf* fimg, const float4* sp_lds, int lane) {
+    cf zp[R1 - R0];
+    float4 ch[R1 - R0];
+#pragma unroll
+    for (int r = R0; r < R1; ++r) zp[r - R0] = fimg[PadA16::at((kNA - (lane + 64 * r)) & (kNA - 1))];
+    load_spectra_part<kNA, 16, R0, R1>(ch, sp_lds, lane);
+    spectral_product_part<kNA, 16, R0, R1>(v, zp, ch, lane);
 }
 
 #ifdef GAB_ABLATE
@@ -1196,12 +1216,14 @@ __device__ __forceinline__ void conv_split_batch12_resident(
         };
         const int first = (g - head0) & 1;                             // this group's first window
         int nb = 0;
+        if (first == 0 && n_buffers > 0) {
+            load_window(std::integral_constant<int, 0>{}, 0, zn);
+            load_window(std::integral_constant<int, 1>{}, 0, zn);
+        }
+        __syncthreads();                                               // once per launch: the forward waves' prologue (see there)
         if (first == 1) {
             second_half(0, -1, 1 < n_buffers ? 1 : -1);                   // period 0: nothing to finish, window 1 asked for
             nb = 1;
-        } else if (n_buffers > 0) {
-            load_window(std::integral_constant<int, 0>{}, 0, zn);
-            load_window(std::integral_constant<int, 1>{}, 0, zn);
         }
         for (;;) {                                                     // nb: a period in which a transform of this group starts
             if (nb > n_buffers) break;
@@ -1216,7 +1238,7 @@ __device__ __forceinline__ void conv_split_batch12_resident(
         const int q = 2 * d + w;
         cf* const hp = reinterpret_cast<cf*>(hist) + (size_t)q * kSlots * kB;
         cf* const img = lds + w * kWaveImg;                           // the transform's exchanges, then its spectrum
-        cf* const hand = lds + (2 + w) * kWaveImg;                    // A2 share, then the output spectrum for the inverse wave
+        cf* const hand = lds + (2 + w) * kWaveImg;                    // bins 0-7 of the output spectrum for the inverse wave
         const float4* const sa = spec + w * kBinsA;                   // taps [0,512)
         const float4* const sa2 = spec + (2 + w) * kBinsA;            // taps [512,1024)
         using WF = fft::WaveFFT1024<false>;
@@ -1224,26 +1246,6 @@ __device__ __forceinline__ void conv_split_batch12_resident(
         WF::load_twiddles(t, tw, lane);
         const size_t xoff = (size_t)(2 * q) * kB;                     // channel a of a buffer; channel b is kB further
         cf z[16], prev[8], nxt[8];
-        // W = Z x spectra (from LDS) in halves of eight bins: partner values and spectra of a half live in registers at a time
-        auto product_from_image = [&](cf (&v)[16], const float4* sp_lds) {
-            {
-                cf zp[8];
-                float4 ch[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) zp[r] = img[PadA16::at((kNA - (lane + 64 * r)) & (kNA - 1))];
-                load_spectra_part<kNA, 16, 0, 8>(ch, sp_lds, lane);
-                spectral_product_part<kNA, 16, 0, 8>(v, zp, ch, lane);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                cf zp[8];
-                float4 ch[8];
-#pragma unroll
-                for (int r = 0; r < 8; ++r) zp[r] = img[PadA16::at((kNA - (lane + 64 * (8 + r))) & (kNA - 1))];
-                load_spectra_part<kNA, 16, 8, 16>(ch, sp_lds, lane);
-                spectral_product_part<kNA, 16, 8, 16>(v, zp, ch, lane);
-            }
-        };
         {   // prologue: the spectrum of the ring's blocks [k-2 | k-1] into the image
             const int s1 = ((head0 + kSlots - 1) & (kSlots - 1)) * kB, s2 = ((head0 + kSlots - 2) & (kSlots - 1)) * kB;
 #pragma unroll
@@ -1260,20 +1262,18 @@ __device__ __forceinline__ void conv_split_batch12_resident(
             WF::run(z, img, t, lane, WF::NoHook());
 #pragma unroll
             for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];
-            __builtin_amdgcn_wave_barrier();
+            __syncthreads();                                          // once per launch: the inverse wave reads this image in period 0
         }
         for (int nb = 0; nb < n_buffers; ++nb) {
-            // A2 share | hand-over + window + pass 0 | pass 1 | pass 2 | spectrum + A product | sum into the hand-over
+            // A2 share, bins 0-7 | window + pass 0 | pass 1 | pass 2 + spectrum | A product, bins 0-7 | sum into the hand-over
             const int head = (head0 + nb) & (kSlots - 1);
-            {
-                cf share[16];                                         // taps [512,1024): last period's spectrum x its spectra
+            // taps [512,1024): last period's spectrum x its spectra.  The share waits in registers for the A product (the
+            // transform leaves room for sixteen more): it reaches the hand-over image once, as part of the sum
+            cf share[16];                                             // ([8..16) unused)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) share[r] = img[rb + 68 * r];
-                product_from_image(share, sa2);
-                GAB_B12BAR(nb, 0);                                   // barrier 1: the inverse wave has read the hand-over image
-#pragma unroll
-                for (int r = 0; r < 16; ++r) hand[rb + 68 * r] = share[r];
-            }
+            for (int r = 0; r < 8; ++r) share[r] = img[rb + 68 * r];
+            near_product_half<0, 8>(share, img, sa2, lane);
+            GAB_B12BAR(nb, 0);                                       // barrier 1: the inverse wave has read the hand-over image and this one
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { z[j] = prev[j]; z[8 + j] = nxt[j]; }
@@ -1291,36 +1291,78 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                 for (int j = 0; j < 8; ++j) nxt[j] = mk(xa[64 * j], xa[kB + 64 * j]);
             }
             WF::run(z, img, t, lane, [&](int i) { GAB_B12BAR(nb, 1 + i); });   // barriers 2, 3 from inside
-            GAB_B12BAR(nb, 3);                                       // barrier 4
+            // the spectrum goes into the image BEFORE barrier 4 (the transform's exchanges there are this wave's own and are done;
+            // nobody else writes the image): behind the barrier the inverse wave reads its half of it, and it stays for the next period
 #pragma unroll
-            for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];     // the spectrum stays here for the next period
-            __builtin_amdgcn_wave_barrier();
-            product_from_image(z, sa);
+            for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];
+            GAB_B12BAR(nb, 3);                                       // barrier 4
+            near_product_half<0, 8>(z, img, sa, lane);
             GAB_B12BAR(nb, 4);                                       // barrier 5
 #pragma unroll
-            for (int r = 0; r < 16; ++r) hand[rb + 68 * r] = fft::cadd(z[r], hand[rb + 68 * r]);   // A product + A2 share
+            for (int r = 0; r < 8; ++r) hand[rb + 68 * r] = fft::cadd(z[r], share[r]);   // A product + A2 share
             GAB_B12BAR(nb, 5);                                       // barrier 6 closes the period
         }
         idle_period();                                                // the pipeline's last period
     } else {
-        // ---- inverse waves: wave 2 + p turns the output spectrum of pair p into samples, one period later
+        // ---- inverse waves: wave 2 + p turns the output spectrum of pair p into samples, one period later, and forms bins 8-15 per
+        // lane of the pair's two near products of THIS period (the forward wave forms bins 0-7; it is the busier of the two).
+        // These bins are the wave's own a period later: the A2 share waits in the hand-over image while the wave transforms
+        // (held in registers across the transform it spilled), the sum (A product + A2 share, the forward wave's operand
+        // order) stays in registers.
         const int pr = w - 2;
-        const cf* const hand = lds + (2 + pr) * kWaveImg;
+        cf* const hand = lds + (2 + pr) * kWaveImg;                   // bins 0-7 of the output spectrum from the forward wave; bins 8-15: this wave's A2 share
+        const cf* const fimg = lds + pr * kWaveImg;                   // the forward wave's image: the pair's spectrum
+        const float4* const sa = spec + pr * kBinsA;                  // taps [0,512)
+        const float4* const sa2 = spec + (2 + pr) * kBinsA;           // taps [512,1024)
         cf* const img = lds + (4 + pr) * kWaveImg;                    // the transform's exchanges, then the output swap
         const cf* const other = lds + (4 + (1 - pr)) * kWaveImg;
         const cf* const cg = sp.carry + (size_t)(2 * d + pr) * kCarrySlots * kB;
         using WFi = fft::WaveFFT1024<true>;
         WFi::Lean t;
         WFi::load_twiddles(t, tw, lane);
-        idle_period();                                                // first period: nothing to turn yet
+        cf ws[16], sum[8];                                            // this wave's half of a near product: [8..16) ([0..8) unused); sum[j]: bin 8 + j
+        // the spectrum's bins 8-15 from the forward wave's image x the spectra's: the same calls on the same values as the
+        // forward wave made when it formed all sixteen
+        auto product_half = [&](const float4* sp_lds) {
+#pragma unroll
+            for (int r = 8; r < 16; ++r) ws[r] = fimg[rb + 68 * r];
+            near_product_half<8, 16>(ws, fimg, sp_lds, lane);
+        };
+        auto store_share = [&]() {
+#pragma unroll
+            for (int r = 8; r < 16; ++r) hand[rb + 68 * r] = ws[r];
+        };
+        auto sum_halves = [&]() {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sum[j] = fft::cadd(ws[8 + j], hand[rb + 68 * (8 + j)]);   // A product + A2 share
+        };
+        __syncthreads();                                              // once per launch: the forward wave's prologue spectrum is in its image
+        if (n_buffers > 0) {                                          // first period: nothing to turn yet, buffer 0's products
+            product_half(sa2);
+            GAB_B12BAR(0, 0);
+            store_share();
+            GAB_B12BAR(0, 1);
+            GAB_B12BAR(0, 2);
+            GAB_B12BAR(0, 3);
+            product_half(sa);
+            GAB_B12BAR(0, 4);
+            sum_halves();
+            GAB_B12BAR(0, 5);
+        } else {
+            idle_period();
+        }
         for (int nb = 1; nb <= n_buffers; ++nb) {
-            // hand-over read + far share asked for | pass 0 | pass 1 | pass 2 + far share | swap | stores
+            // hand-over read + far share asked for + A2 share, bins 8-15 | pass 0 | pass 1 | pass 2 + far share |
+            // swap + A product, bins 8-15 | stores + the two halves' sum  (the products: of buffer nb, not in the last period)
+            const bool products = nb < n_buffers;
             const int b = nb - 1;                                     // the buffer whose spectrum was handed over last period
             const int head = (head0 + b) & (kSlots - 1);
             float* const outb = out + (size_t)b * step;
             cf z[16], y[8], park[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) z[r] = hand[rb + 68 * r];
+            for (int r = 0; r < 8; ++r) z[r] = hand[rb + 68 * r];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) z[8 + j] = sum[j];
             {
                 int lo = lane;
                 asm volatile("" : "+v"(lo));
@@ -1333,7 +1375,11 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                     park[j] = mk(__uint_as_float((unsigned)v), __uint_as_float((unsigned)(v >> 32)));
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);
+            if (products) product_half(sa2);                          // before barrier 1: the forward transform then overwrites its image
             GAB_B12BAR(nb, 0);                                       // barrier 1
+            if (products) store_share();
+            __builtin_amdgcn_sched_barrier(0);
             WFi::run(z, img, t, lane, [&](int i) { GAB_B12BAR(nb, 1 + i); });  // barriers 2, 3 from inside
 #pragma unroll
             for (int j = 0; j < 8; ++j) y[j] = fft::cadd(z[8 + j], park[j]);
@@ -1345,6 +1391,8 @@ __device__ __forceinline__ void conv_split_batch12_resident(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) img[lane + 64 * j] = y[j];
             }
+            __builtin_amdgcn_sched_barrier(0);
+            if (products) product_half(sa);                           // behind barrier 4: buffer nb's spectrum is in the forward wave's image
             GAB_B12BAR(nb, 4);                                       // barrier 5: the swapped halves are in LDS
             {
                 float* const o0 = outb + 4 * (size_t)d;
@@ -1362,6 +1410,7 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                     }
                 }
             }
+            if (products) sum_halves();
             GAB_B12BAR(nb, 5);                                       // barrier 6 closes the period
         }
     }
