@@ -226,6 +226,16 @@ PROTOTYPES = {
     "gab_gate_process_batch": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "gab_gate_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_gate_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_xover_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_xover_destroy": (_I, [_P]),
+    "gab_xover_set_splits": (_I, [_P, _P, _P]),
+    "gab_xover_set_splits_tracks": (_I, [_P, _P, _I, _I, _P]),
+    "gab_xover_reset": (_I, [_P, _P]),
+    "gab_xover_process": (_I, [_P, _P, _P, _P]),
+    "gab_xover_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_xover_splits": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_xover_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_xover_sections": (_I, [_I]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

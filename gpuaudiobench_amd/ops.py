@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -851,6 +851,83 @@ class GatePlan(_KeyedPlan):
                 None if act is None else _dev(act, torch.int32), _stream(stream))
 
     launch = _launcher("gab_gate_process")
+
+
+XOVER_K32 = 1.41421353816986083984375      # (float)sqrt(2.0), GAB_XOVER_K32: the damping of a crossover section
+
+
+def crossover_rows(freqs_hz, fs=48000.0):
+    """CrossoverPlan's table from split frequencies: a scalar (one split), a list of S ascending frequencies (every
+    track the same) or [T][S]; each within (0, fs / 2).  Returns float32 [T or 1][S][3] = {a1, a2, a3} per split:
+    g = tan(pi f / fs), a1 = 1 / (1 + g (g + K32)), a2 = g a1, a3 = g a2, in float64, rounded once."""
+    import numpy as np
+    f = np.asarray(freqs_hz, np.float64)
+    if f.ndim > 2 or f.size == 0:
+        raise ValueError("freqs_hz must be a scalar, [S] or [T][S]")
+    f = f.reshape((1, -1)) if f.ndim < 2 else f
+    if not fs > 0.0 or not (np.isfinite(f).all() and (f > 0.0).all() and (f < fs / 2.0).all()):
+        raise ValueError("every split frequency must be within (0, fs / 2)")
+    if not (np.diff(f, axis=1) > 0.0).all():
+        raise ValueError("the split frequencies of a track must ascend")
+    g = np.tan(np.pi * f / fs)
+    a1 = 1.0 / (1.0 + g * (g + XOVER_K32))
+    a2 = g * a1
+    return np.stack([a1, a2, g * a2], axis=-1).astype(np.float32)
+
+
+class CrossoverPlan(_TrackPlan, _Prepared):
+    """gab_xover_plan: every track split into `bands` = 2..4 bands by Linkwitz-Riley (fourth-order) crossovers, band 0
+    the lowest; the bands sum to the input through an all-pass.  Rows {a1, a2, a3} per (track, split) come from
+    crossover_rows.  A new plan has no rows: set_splits comes before process.  Splits are not ramped."""
+
+    _destroy = "gab_xover_destroy"
+
+    def __init__(self, tracks, bufsize, bands):
+        self.bands = bands
+        self._create(tracks, bufsize, bands)
+        self.splits_per_track = bands - 1
+
+    @staticmethod
+    def sections(bands):
+        """The sections of a track: 3, 7, 12 for 2, 3, 4 bands (0: not a band count of the plan)."""
+        return lib.gab_xover_sections(bands)
+
+    def set_splits(self, rows, first_track=None, n_tracks=None):
+        """rows: device tensor [tracks][bands - 1][3], or [n_tracks][bands - 1][3] for tracks [first_track, first_track +
+        n_tracks) (n_tracks=None: as many as rows holds).  Acts from the next buffer; the state is kept."""
+        if first_track is None and n_tracks is not None:
+            raise ValueError("n_tracks needs first_track")
+        n = self._rows(rows, 3 * self.splits_per_track, first_track, "rows")
+        if n_tracks is not None and n != n_tracks:
+            raise ValueError("rows must hold n_tracks tracks")
+        self._set("splits", _dev(rows), first_track, n)
+
+    def reset(self):
+        """Every state to zero; the rows are kept."""
+        super().reset()
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize] -> [bands][tracks*bufsize], band-major; out may not overlap x."""
+        return self._process("process", x, out, 1, (self.bands * self.tracks * self.bufsize,))
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] -> [n][bands][tracks*bufsize] in one launch."""
+        n = _n_buffers(self, xs)
+        return self._process("process_batch", xs, out, n, (n * self.bands * self.tracks * self.bufsize,), n)
+
+    def splits(self):
+        """A copy of the table, [tracks][bands - 1][3]."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_xover_splits(self._h, C.byref(p), C.byref(n)))
+        return _view(p.value, n.value // 3, 3).clone().view(self.tracks, self.splits_per_track, 3)
+
+    def state(self):
+        """A copy of the carried state, [tracks][sections][2] = (ic1, ic2), the sections in the header's order."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_xover_state(self._h, C.byref(p), C.byref(n)))
+        return _view(p.value, n.value // 2, 2).clone().view(self.tracks, -1, 2)
+
+    launch = _launcher("gab_xover_process")
 
 
 _REVERB_SPREAD = 4.65     # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)

@@ -1136,6 +1136,76 @@ int gab_gate_process_batch(gab_gate_plan* plan, const float* d_in, const float* 
 int gab_gate_params(gab_gate_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_gate_state(gab_gate_plan* plan, float** d_gain, int** d_count, size_t* n_tracks);
 
+/* ---- crossover: a Linkwitz-Riley (fourth-order) split of every track into K = 2..4 bands whose sum is the input
+ * through an all-pass, made of trapezoidal state-variable sections with fixed arithmetic (additive; the reference has
+ * no crossover) -----------------------------------------------------------------------------------------------------
+ * The block in front of a multiband compressor, a de-esser or a bass manager: the band block it writes is a K T-track
+ * block as gab_dyn_process, gab_gate_process and gab_mix_process take it.  S = K - 1 splits per track.
+ *   rows           device, [tracks][S][3] float32 (GAB_XOVER_FIELDS): {a1, a2, a3} per (track, split), the splits of a
+ *                  track in ascending frequency.  Made on the host in float64 and rounded once:
+ *                      g = tan(pi f / fs),  k = (double)K32,  K32 = (float)sqrt(2.0) = GAB_XOVER_K32
+ *                      a1 = 1 / (1 + g (g + k)),  a2 = g a1,  a3 = g a2
+ *     set_splits   the whole table; set_splits_tracks: rows [first_track, first_track + n_tracks), d_rows
+ *                  [n_tracks][S][3], the other rows kept.  The values are checked on the device first.  Refused are
+ *                      a value that is not finite;
+ *                      field 0 unless 0 < a1 <= 1;    field 1 unless 0 <= a2 < 1;    field 2 unless 0 <= a3 < 1;
+ *                      field 2, read with the two before it, unless |(fmaf(K32, a2, a1) + a3) - 1| <= 2^-20
+ *                      and unless |fmaf(a2, a2, -(a1 * a3))| <= 2^-18 * (a2 * a2)      (every operation rounded once).
+ *                  A row that passes is the row of some g >= 0 to within those margins (host-made rows reach 2^-23 and
+ *                  2^-21.9), and the section below is stable for every such g.  A violation: GAB_ERR_INVALID_ARG naming
+ *                  the first (track, field) in index order, field = 3 split + {0, 1, 2}; the plan keeps what it had.
+ *                  Both calls are synchronous with respect to `stream`.  Coefficients are not ramped: as with
+ *                  gab_eq_set_coeffs a set takes effect with the next buffer and keeps the state.  The states are the
+ *                  integrators' own (twice the charge of the two capacitors of the analogue section), not a filter's
+ *                  delay line: they mean the same under any row, so a moved split does not rescale them and makes no
+ *                  click beyond the change of the filter itself.
+ *     reset        every state to +0; the rows are kept.
+ *     splits       the plan's own table, for inspection.     state: the plan's state array, [tracks][sections][2].
+ *     sections     3 S + S (S - 1) / 2 = 3, 7, 12 for K = 2, 3, 4; 0 for any other K.  Host arithmetic, no plan.
+ *   create         tracks >= 1, bufsize >= 1, bands 2..4.  Arguments are checked before any device call.  A new plan
+ *                  has no rows: process before the first accepted set is refused, with a text that says so.  (Rows that
+ *                  a first set_splits_tracks leaves out are {1, 0, 0}, g = 0: band K - 1 is the input.)
+ *   process        one buffer.  d_in track-major [t*B + s]; d_out band-major [K][T][B], band 0 the lowest.  d_out may
+ *                  not overlap d_in (refused).  Any bufsize, any alignment, any track count: the same bits; 16-byte
+ *                  aligned pointers with bufsize % 4 == 0 take a wider load.
+ *   process_batch  n_buffers buffers in one launch: d_in [n][T*B], d_out [n][K][T*B], the state running through; the
+ *                  same bits as n calls of process.  Neither call allocates or waits.
+ * One section.  State (ic1, ic2), input v0, its split's row; every written operation is rounded once:
+ *     v3 = v0 - ic2
+ *     v1 = fmaf(a2, v3, a1 * ic1)
+ *     v2 = fmaf(a3, v3, fmaf(a2, ic1, ic2))
+ *     ic1 = fmaf(2, v1, -ic1)
+ *     ic2 = fmaf(2, v2, -ic2)
+ *     low = v2      band = v1      high = fmaf(-K32, v1, v0) - v2
+ * The topology, per track and sample, from the bottom up.  r_0 = x.  For split j = 0..S-1, on split j's row:
+ *     (l, ., h) = A_j(r_j)        low_j = B_j(l).low        r_{j+1} = C_j(h).high
+ * then for m = j+1..S-1 in turn, on split m's row, the all-pass that the upper bands see and band j would not:
+ *     low_j = fmaf(-K2, D_{j,m}(low_j).band, low_j),      K2 = 2 * K32 (exact in float32)
+ * Band j is low_j, band K - 1 is r_S.  In exact arithmetic the bands sum to x through the product of the splits'
+ * second-order all-passes.  The order of the sections in the state array: split after split, and within split j
+ *     A_j, B_j, C_j, D_{j,j+1}, ..., D_{j,S-1}
+ * that is  K = 2: A0 B0 C0;  K = 3: A0 B0 C0 D01 A1 B1 C1;  K = 4: A0 B0 C0 D01 D02 A1 B1 C1 D12 A2 B2 C2.
+ * A NaN or an infinity in x enters that track's states and stays in that track's bands until reset; it reaches no
+ * other track.  Subnormals are kept: a tail runs down through them, and comes to rest not at zero but within a few
+ * units of 2^-149 (round-to-nearest: a section stops moving once a2 v3 and a3 v3 round to nothing against its states,
+ * about 1 / (2 a3) units); reset gives +0.  Every section is a deterministic recurrence, so nothing has rounding
+ * freedom: every launch form gives the same bits, and a shard of tracks run as its own plan gives those tracks' bits.  Out of scope: ramped splits, other slopes, linear-phase splits (a gab_conv plan per band).
+ * One thread at a time per plan.                                                                                     */
+typedef struct gab_xover_plan gab_xover_plan;
+#define GAB_XOVER_FIELDS 3
+#define GAB_XOVER_K32 0x1.6a09e6p+0f
+int gab_xover_create(gab_xover_plan** plan, int tracks, int bufsize, int bands);
+int gab_xover_destroy(gab_xover_plan* plan);
+int gab_xover_set_splits(gab_xover_plan* plan, const float* d_rows, gab_stream_t stream);
+int gab_xover_set_splits_tracks(gab_xover_plan* plan, const float* d_rows, int first_track, int n_tracks,
+                                gab_stream_t stream);
+int gab_xover_reset(gab_xover_plan* plan, gab_stream_t stream);
+int gab_xover_process(gab_xover_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_xover_process_batch(gab_xover_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_xover_splits(gab_xover_plan* plan, float** d_rows, size_t* n_floats);
+int gab_xover_state(gab_xover_plan* plan, float** d_state, size_t* n_floats);
+int gab_xover_sections(int bands);
+
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
 /* ===================================================================== */
