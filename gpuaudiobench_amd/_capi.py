@@ -236,6 +236,16 @@ PROTOTYPES = {
     "gab_xover_splits": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
     "gab_xover_state": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
     "gab_xover_sections": (_I, [_I]),
+    "gab_lim_create": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
+    "gab_lim_destroy": (_I, [_P]),
+    "gab_lim_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_lim_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_lim_reset": (_I, [_P, _P]),
+    "gab_lim_process": (_I, [_P, _P, _P, _P, _P]),
+    "gab_lim_process_batch": (_I, [_P, _P, _P, _P, _I, _P]),
+    "gab_lim_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_lim_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_lim_latency": (_I, [_P, C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -928,6 +928,85 @@ class CrossoverPlan(_TrackPlan, _Prepared):
         return _view(p.value, n.value // 2, 2).clone().view(self.tracks, -1, 2)
 
     launch = _launcher("gab_xover_process")
+
+
+def limiter_params(ceiling_db=-1.0, release_ms=100.0, drive_db=0.0, fs=48000.0):
+    """A row (all arguments scalars) or a table [n][3] float32 of LimiterPlan parameters {drive, ceil, rel} from the
+    knobs of a limiter; float64, rounded once.  Levels go from dB to linear; rel = 1 - exp(-1 / (release_s fs)), and
+    release_ms = 0 gives rel = 1 (the gain is back W samples behind a peak)."""
+    import numpy as np
+    args = [np.asarray(a, np.float64) for a in (ceiling_db, release_ms, drive_db)]
+    scalar = all(a.ndim == 0 for a in args)
+    ceil_db, rel_ms, drive_db = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    if (rel_ms < 0.0).any() or fs <= 0.0:
+        raise ValueError("needs release_ms >= 0 and fs > 0")
+    rel = np.where(rel_ms > 0.0, 1.0 - np.exp(-1.0 / np.where(rel_ms > 0.0, rel_ms * fs / 1000.0, 1.0)), 1.0)
+    table = np.stack([10.0 ** (drive_db / 20.0), 10.0 ** (ceil_db / 20.0), rel], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class LimiterPlan(_TrackPlan):
+    """gab_lim_plan: a brickwall look-ahead limiter per track: |y| <= ceil on every sample, bit for bit the contract of
+    gab_c_api.h.  `lookahead` is the window W, a power of two in 4..256; the plan delays by `.latency` = W - 1 samples.
+    Parameters per track {drive, ceil, rel} (limiter_params makes them from dB and ms); tracks [g link, (g + 1) link)
+    share one detector.  A new plan is a pure delay; new parameters are ramped in over the next buffer unless
+    ramp=False."""
+
+    _destroy = "gab_lim_destroy"
+    FIELDS = ("drive", "ceil", "rel")
+
+    def __init__(self, tracks, bufsize, lookahead=64, link=1):
+        k = int(lookahead).bit_length() - 1
+        if lookahead != 1 << max(k, 0):
+            raise ValueError("lookahead must be a power of two in 4..256")
+        self.lookahead, self.link = lookahead, link
+        self._create(tracks, bufsize, k, link)
+        n = C.c_int(0)
+        check(lib.gab_lim_latency(self._h, C.byref(n)))
+        self.latency = n.value
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][3], or [n][3] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n = self._rows(table, len(self.FIELDS), first_track)
+        self._set("params", _dev(table), first_track, n, 1 if ramp else 0)
+
+    def reset(self):
+        """The histories as in a new plan (xd = 0, t = 1, e = 1), current := target, a pending ramp dropped."""
+        super().reset()
+
+    def _gr(self, gr, n):
+        assert gr is None or gr.numel() == n * self.tracks
+        return None if gr is None else _dev(gr)
+
+    def process(self, x, out=None, gr=None):
+        """One buffer, track-major [tracks*bufsize]; out may be x itself.  gr: a tensor [tracks] that receives the
+        buffer's smallest gain."""
+        return self._process("process", x, out, 1, None, self._gr(gr, 1))
+
+    def process_batch(self, xs, out=None, gr=None):
+        """Consecutive buffers [n][tracks*bufsize]; gr [n][tracks]."""
+        n = _n_buffers(self, xs)
+        return self._process("process_batch", xs, out, n, None, self._gr(gr, n), n)
+
+    def params(self):
+        """Copies of (current, target), each [tracks][3]."""
+        return self._tables("params", len(self.FIELDS))
+
+    def state(self):
+        """Copies of the three histories (xd, t, e), each [tracks][W - 1], oldest first."""
+        x, t, e, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_lim_state(self._h, C.byref(x), C.byref(t), C.byref(e), C.byref(n)))
+        return tuple(_view(p.value, self.tracks, n.value).clone() for p in (x, t, e))
+
+    def prepare(self, x, out, gr=None, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  All state that changes is on the device; which kernel form runs (steady, or the ramp form when
+        a ramp is pending) is the host's choice at the call and what a capture replays, so capture only with no ramp
+        pending: gab_c_api.h, "Captured calls"."""
+        return (self._h, _dev(x), _dev(out), None if gr is None else _dev(gr), _stream(stream))
+
+    launch = _launcher("gab_lim_process")
 
 
 _REVERB_SPREAD = 4.65     # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)

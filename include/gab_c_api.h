@@ -934,7 +934,8 @@ int gab_resample_state(gab_resample_plan* plan, float** d_hist, float** d_taps,
  * (x times a finite gain) and nothing else; a NaN in the key is ignored and an infinity reads as L = 128.  (The meter's
  * filter state, by contrast, is poisoned by one such sample.)  Nothing else has rounding freedom: every launch form gives
  * the same bits, and a shard of tracks that is a multiple of link, run as its own plan, gives those tracks' bits.
- * Look-ahead is not part of the plan: a gab_delay plan in front of d_in, with the undelayed signal as d_key, gives it.
+ * Look-ahead is not part of the plan: a gab_delay plan in front of d_in, with the undelayed signal as d_key, gives it,
+ * but that only moves the attack's overshoot; for a ceiling that holds on every sample there is the gab_lim plan.
  * The launch works on 64 tracks x 64 samples per wave: fewer than 64 tracks x 1024 use a part of the device.  One thread
  * at a time per plan.                                                                                               */
 typedef struct gab_dyn_plan gab_dyn_plan;
@@ -1118,7 +1119,8 @@ float gab_reverb_gmax(int lines);
  * ignored and an infinity in the key opens the gate.  Nothing has rounding freedom: every launch form gives the same
  * bits, and a shard of tracks that is a multiple of link, run as its own plan, gives those tracks' bits.
  * Out of scope: downward expansion with a ratio (the dynamics plan's log2 domain), look-ahead (a gab_delay plan in
- * front of d_in, with the undelayed signal as d_key, gives it), a filtered key (a gab_eq plan on the key gives it).
+ * front of d_in, with the undelayed signal as d_key, gives it; a look-ahead ceiling is the gab_lim plan), a filtered
+ * key (a gab_eq plan on the key gives it).
  * The launch works on 16 tracks x 64 samples per wave, four waves to a workgroup: fewer than 16 x 1024 tracks use a
  * part of the device.  One thread at a time per plan.                                                               */
 typedef struct gab_gate_plan gab_gate_plan;
@@ -1205,6 +1207,109 @@ int gab_xover_process_batch(gab_xover_plan* plan, const float* d_in, float* d_ou
 int gab_xover_splits(gab_xover_plan* plan, float** d_rows, size_t* n_floats);
 int gab_xover_state(gab_xover_plan* plan, float** d_state, size_t* n_floats);
 int gab_xover_sections(int bands);
+
+/* ---- limiter: a brickwall look-ahead limiter per track, with a window of W = 2^k samples, ramped parameters, linked
+ * detectors and three carried histories (additive; the reference has no limiter) ------------------------------------
+ * The block at the very end of a bus, behind gab_mix: the one dynamics processor that GUARANTEES |y| <= ceil on every
+ * sample.  (gab_dyn with slope = -1 is a limiter only in name: its gain is smoothed by an attack and goes through a
+ * polynomial.)  No transcendental, no polynomial: a division, a window minimum, a release recursion and a box mean.
+ *   parameters     device, [tracks][3] float32 (GAB_LIM_FIELDS):
+ *                    0 drive   linear gain in front of the limiter           0 <= drive <= 2^32   (so finite)
+ *                    1 ceil    the ceiling, linear                           2^-32 <= ceil <= 2^32
+ *                    2 rel     release coefficient per sample                0 <= rel <= 1
+ *                  The plan carries two tables, `current` and `target`; a new plan has {1, 2^32, 0} in both on every
+ *                  track and the histories below: a pure delay of D = W - 1 samples, bit for bit, for every sample
+ *                  whose magnitude is at most 2^32 or that is not finite.
+ *     set_params(ramp = 1)  target := the new table, current stays.  On the next processed buffer every one of the
+ *                  three fields of every track is p[s] = fmaf(target - current, r[s], current), r[s] = (s + 1) /
+ *                  bufsize (the delay plan's table: float64 on the host, rounded once; target - current rounded
+ *                  once); after that buffer current := target by a copy.  Two sets before a buffer: the ramp still
+ *                  starts from current.
+ *     set_params(ramp = 0)  current := target := the new table, at once.
+ *     set_params_tracks     the same for rows [first_track, first_track + n_tracks), d_params [n_tracks][3]; the other
+ *                  rows keep their current and target.
+ *                  The values are checked on the device first, against the column `admitted` above.  A violation:
+ *                  GAB_ERR_INVALID_ARG naming the first (track, field) in index order; the plan keeps what it had.
+ *                  Both calls are synchronous with respect to `stream` and take effect with the next buffer.
+ *                  What a ramp can do to the ends: a ramped value is the rounding of current + fl(target - current) r
+ *                  with 0 < r <= 1.  fl(target - current) lies between -current and target by the monotonicity of
+ *                  rounding, so a ramped drive or ceil is never negative (a ceil may reach 0 on the last sample of a
+ *                  ramp from 2^32 down to 2^-32: the need is then 0 and the guarantee below holds with y = 0).  A
+ *                  ramped rel can land above the larger of its two ends, but by no more than 2^-24 (fl(target -
+ *                  current) is off by at most 2^-25, the fmaf's rounding of a value near 1 by at most 2^-25 more): up
+ *                  to 1 + 2^-24.  That is harmless: the release step's fminf holds e at or below m <= 1 whatever
+ *                  fmaf(rel, 1 - e, e) is.
+ *     reset        the histories as in a new plan, current := target, a pending ramp dropped.
+ *     params       the plan's own two tables, for inspection.
+ *     state        the three histories, each [tracks][W - 1] float32, oldest first, as they stand after every call:
+ *                  d_x the last W - 1 values of xd, d_t of t, d_e of e (below); *per_track = W - 1.  A new or reset plan
+ *                  has xd = 0, t = 1, e = 1.
+ *     latency      D = W - 1 samples, the same for every track: a desk compensates it once.
+ *   create         tracks >= 1, bufsize >= 1, lookahead_log2 = k in 2..8: W = 2^k = 4..256 samples (5.3 ms at 48 kHz);
+ *                  link a power of two in 1..64 with tracks % link == 0: tracks [g link, (g + 1) link) share one
+ *                  detector; every track keeps its own parameters and histories.  Arguments are checked before any
+ *                  device call.
+ *   process        one buffer.  d_in and d_out track-major [t*B + s]; d_out == d_in is allowed, any other overlap is
+ *                  refused.  d_gr is null or [tracks]: per track the smallest gain g of the buffer.  Any bufsize >= 1
+ *                  (those shorter than W - 1 included), any alignment, any track count: the same bits.
+ *   process_batch  n_buffers buffers back to back: d_in, d_out [n][T*B], d_gr [n][T]; a pending ramp runs through the
+ *                  first of them; same bits as n calls of process.  process and process_batch allocate nothing and
+ *                  wait for nothing, so they can be captured; the histories are device state.  One launch per call or
+ *                  batch for link <= 8; for link = 16, 32 and 64 two launches per buffer (the group's detector first).
+ * The bits of one sample.  On a buffer without a pending ramp p = target, on one with a ramp the formula above.  Every
+ * + - * / below is rounded once, fmaf only where written; fminf and fmaxf ignore a NaN operand; the division is IEEE
+ * (round to nearest even, subnormals kept).  For sample n of track j in link group G, x the input, p the parameters in
+ * force at n:
+ *     drive      xd = p.drive * x[n]
+ *     detector   d  = fmaxf over j' in G of (|xd[j']| if its bits are below 0x7f800000, else 0), from 0
+ *     need       t  = 1                          if d <= p_j.ceil
+ *                t  = p_j.ceil / d               otherwise;  if t * d > p_j.ceil:  t = the float one unit below t (bits - 1)
+ *     window     m  = fminf(t[n], t[n-1], ..., t[n-(W-1)])
+ *     release    e  = fminf(m, fmaf(p_j.rel, 1 - e[n-1], e[n-1]))
+ *     box        S1[n] = e[n];  S2h[n] = Sh[n] + Sh[n-h]  for h = 1, 2, ..., W/2;   s = SW[n] * 2^-k
+ *     gain       g  = fminf(s, t[n-(W-1)])
+ *     out        y[n] = g * xd[n-(W-1)]
+ *     gr         fminf of g over the buffer's samples, from +infinity
+ * (fminf is exact in any order; the box is the doubling tree as written, W - 1 additions in k levels.)
+ * The guarantee.  |y[n]| <= the ceil in force when sample n - (W-1) came in, exactly, for every input whose xd at
+ * n - (W-1) is finite.  In three steps, with n' = n - (W-1), d', c' the detector and the ceiling at n':
+ *   1. Every e[k], k in [n', n], is at most m[k] (the release step's fminf), and m[k] <= t[n'] because t[n'] is inside
+ *      the window of every such k.  So all W terms of the box are <= t[n'], and in exact arithmetic so is their mean.
+ *   2. The sum's roundings could lift s above t[n'] all the same; the final fminf(s, t[n']) takes the sum's rounding out
+ *      of the argument altogether: g <= t[n'], and g >= 0 because every t and so every e is.
+ *   3. t[n'] * d' <= c' in float32: if d' <= c', t = 1 and 1 * d' = d'; otherwise that is what the correction
+ *      established.  |xd_j[n']| <= d' (the track is in its own group), and rounding is monotone, so
+ *      |y| = fl(g |xd_j|) <= fl(t[n'] d') <= c'.
+ *   Why one unit is enough: q = fl(c / d) <= (c / d)(1 + 2^-24), so q d <= c (1 + 2^-24) before rounding, and one unit
+ *   takes at least 2^-24 of a normal q away: (q - ulp) d <= c, which rounds to at most c.  A subnormal q loses a larger
+ *   share; a q of +0 is never corrected, because 0 * d > c is false.
+ * Linearity below the ceiling.  A stretch in which no link group's d exceeds its ceilings has t = 1; once the histories
+ * hold t = e = 1 (a new plan, or W - 1 such samples with rel = 1, or the recovery of any rel > 0 run to its end), m = e =
+ * 1, the box sums W ones exactly, g = 1 and y is drive * x delayed by D, bit for bit, with gr = 1.
+ * Samples that are not finite.  An xd that is a NaN or an infinity is not seen by the detector (it reads as 0 there, for
+ * its own track and for its link group), so t, m, e, s and g are finite whatever the samples are.  It reaches y once, D
+ * samples later, times that sample's finite gain (infinity times a gain of 0 is a NaN).  Every other output sample and
+ * every state word but its own slot of the xd history is what it would be with a 0 in its place; it stays in its track,
+ * also inside a link group.
+ * No rounding freedom.  Every launch form gives the same bits; a shard of tracks that is a multiple of link, run as its
+ * own plan, gives those tracks' bits; any bufsize >= 1 and any cut of a stream into buffers gives the same bits; any
+ * alignment gives the same bits (16-byte aligned pointers with bufsize % 4 == 0 take a wider load).
+ * Out of scope: oversampled (true-peak) detection, a side-chain key, a look-ahead per track.
+ * The launch works on 8 tracks x 64 samples per wave, a wave to a workgroup.  One thread at a time per plan.         */
+typedef struct gab_lim_plan gab_lim_plan;
+#define GAB_LIM_FIELDS 3
+int gab_lim_create(gab_lim_plan** plan, int tracks, int bufsize, int lookahead_log2, int link);
+int gab_lim_destroy(gab_lim_plan* plan);
+int gab_lim_set_params(gab_lim_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_lim_set_params_tracks(gab_lim_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                              gab_stream_t stream);
+int gab_lim_reset(gab_lim_plan* plan, gab_stream_t stream);
+int gab_lim_process(gab_lim_plan* plan, const float* d_in, float* d_out, float* d_gr, gab_stream_t stream);
+int gab_lim_process_batch(gab_lim_plan* plan, const float* d_in, float* d_out, float* d_gr, int n_buffers,
+                          gab_stream_t stream);
+int gab_lim_params(gab_lim_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_lim_state(gab_lim_plan* plan, float** d_x, float** d_t, float** d_e, size_t* per_track);
+int gab_lim_latency(gab_lim_plan* plan, int* samples);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
