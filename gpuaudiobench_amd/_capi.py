@@ -25,6 +25,8 @@ MIX_TRACK_MAJOR = 0
 MIX_SAMPLE_MAJOR = 1
 DELAY_LINEAR = 0
 DELAY_LAGRANGE3 = 1
+SPEC_COMPLEX = 0
+SPEC_POWER = 1
 DWG_NAIVE = 0
 DWG_ACCEL = 1
 
@@ -246,6 +248,15 @@ PROTOTYPES = {
     "gab_lim_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_lim_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
     "gab_lim_latency": (_I, [_P, C.POINTER(_I)]),
+    "gab_spec_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I]),
+    "gab_spec_destroy": (_I, [_P]),
+    "gab_spec_set_window": (_I, [_P, _P, _P]),
+    "gab_spec_set_bands": (_I, [_P, C.POINTER(_I)]),
+    "gab_spec_reset": (_I, [_P, _P]),
+    "gab_spec_process": (_I, [_P, _P, _P, C.POINTER(_I), _P]),
+    "gab_spec_process_batch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
+    "gab_spec_frames": (_I, [_P, _I, C.POINTER(_I)]),
+    "gab_spec_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1,0 +1,394 @@
+// k_spectrum.hip — the spectrum plan: a short-time Fourier analyser per track (include/gab_c_api.h, gab_spec_*).
+// Frames of N = 1024 samples on a hop grid H, windowed, transformed, and written as complex bins, as powers per bin or
+// as powers per band; the last 1023 samples of every track are carried on the device, so a frame reaches back over the
+// calls before it.  The input is read and never written.  No counterpart in the reference, whose FFT benchmark is one
+// stateless transform of 1024 samples.
+//
+//   spectrum_kernel<MODE>   one wave per (pair of tracks, frame), four waves a workgroup, no workgroup barrier: lane j
+//                           gathers s[jH - N + j + 64 r] of both tracks (from the carried history where the index
+//                           lies before the call, else from the call's blocks, across the buffers of a batch),
+//                           multiplies by the window, runs gab_fft.hpp's wave-held 1024-point transform, unpacks the
+//                           pair as fft_r2c_1024_kernel does, and writes the bins, their powers, or (through the
+//                           wave's LDS image, lane b adding band b in order) the bands.
+//   spectrum_hist_kernel    behind it on the same stream: a wave per track forms the last 1023 samples of
+//                           history ++ call in registers and writes them only after every lane has read.
+//   SpectrumRule            refuses a window value that is not finite (gab_plan.hpp's check kernel).
+//
+// A frame's bits depend on its pair's 1024 windowed samples (and, for powers, on the window's sum) and on nothing else:
+// not on bufsize, the hop, the cut into calls, the alignment of d_in or the other frames of the launch.  Every frame
+// takes the same scalar gather; there is no 16-byte load form (a lane's sixteen values lie 64 samples
+// apart, so a float4 per lane would have to cross the wave through LDS first).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "gab_fft.hpp"
+#include "gab_plan.hpp"
+
+namespace gab {
+namespace {
+
+using fft::cf;
+
+constexpr int kSpecN = 1024;                              // the transform
+constexpr int kSpecBins = kSpecN / 2 + 1;                 // 513
+constexpr int kSpecHist = kSpecN - 1;                     // samples carried per track
+constexpr int kSpecMaxBands = 64;                         // a lane per band
+constexpr int kSpecMinHop = 32;
+constexpr int kSpecImg = fft::Pad<16>::size(kSpecN);      // cf entries of a wave's LDS image
+constexpr unsigned kSpecMaxBlocks = 1u << 23;             // workgroups of one launch: 2^31 threads
+enum { kSpecComplex = 0, kSpecBinsMode = 1, kSpecBandsMode = 2 };
+
+// Sample i (relative to the call's first sample; -1023 <= i < n_buffers B) of track t.
+__device__ __forceinline__ float spec_sample(const float* __restrict__ in, const float* __restrict__ hist, int T, int B,
+                                             bool one_buffer, int t, int i) {
+    if (i < 0) return hist[(size_t)t * kSpecHist + (kSpecHist + i)];
+    if (one_buffer) return in[(size_t)t * B + i];
+    const unsigned nb = (unsigned)i / (unsigned)B, s = (unsigned)i - nb * (unsigned)B;
+    return in[((size_t)nb * T + t) * B + s];
+}
+
+// Grid: x = (group of four pairs) * frames + frame.  in: [n][T][B], only read.  hist: [T][1023], only read.  window:
+// [1024].  Frame f ends `first_end + f H` samples behind the call's first (1 <= first_end; the last end <= n B).
+// rows: [frames][T][513][2], [frames][T][513] or [frames][T][bands].  edges: [bands + 1].
+template <int MODE>
+__global__ __launch_bounds__(256) void spectrum_kernel(const float* __restrict__ in, const float* __restrict__ hist,
+                                                      const float* __restrict__ window, const int* __restrict__ edges,
+                                                      float* __restrict__ rows, const cf* __restrict__ tw, int T, int B,
+                                                      int n_buffers, int H, int first_end, int frames, int bands,
+                                                      float inv_edge, float inv_mid) {
+    __shared__ cf lds[4 * kSpecImg];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    cf* const img = lds + w * kSpecImg;
+    const int f = (int)(blockIdx.x % (unsigned)frames);
+    const int q = (int)(blockIdx.x / (unsigned)frames) * 4 + w;
+    const int ta = 2 * q, tb = 2 * q + 1;
+    if (ta >= T) return;                                   // whole wave; no barriers below
+    const bool hasb = tb < T;
+    const bool one_buffer = n_buffers == 1;
+    const int start = first_end + f * H - kSpecN;          // of the frame, relative to the call's first sample
+
+    using WF = fft::WaveFFT1024<false>;
+    WF::Twiddles t;
+    WF::load_twiddles(t, tw, lane);
+    cf z[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int n = lane + 64 * r;
+        const float wn = window[n];
+        const float xa = spec_sample(in, hist, T, B, one_buffer, ta, start + n);
+        const float xb = hasb ? spec_sample(in, hist, T, B, one_buffer, tb, start + n) : 0.0f;
+        z[r] = fft::mk(__fmul_rn(wn, xa), __fmul_rn(wn, xb));
+    }
+    WF::run(z, img, t, lane);
+    // partner Z[(N - k) mod N], k = lane + 64 r: bins 0..512 are r < 8 plus (r = 8, lane 0)
+    const unsigned rb = (unsigned)lane + ((unsigned)lane >> 4);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];
+    __builtin_amdgcn_wave_barrier();
+    cf xa[9], xb[9];
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+        const int k = lane + 64 * r;
+        xa[r] = fft::mk(0.0f, 0.0f);
+        xb[r] = fft::mk(0.0f, 0.0f);
+        if (k <= kSpecN / 2) {
+            const cf zp = fft::conj(img[fft::Pad<16>::at((kSpecN - k) & (kSpecN - 1))]);
+            const cf s = fft::cadd(z[r], zp), d = fft::csub(z[r], zp);
+            xa[r] = fft::mk(0.5f * s.x, 0.5f * s.y);
+            xb[r] = fft::mk(0.5f * d.y, -0.5f * d.x);
+        }
+    }
+    if constexpr (MODE == kSpecComplex) {
+        float2* const oa = reinterpret_cast<float2*>(rows) + ((size_t)f * T + ta) * kSpecBins;
+        float2* const ob = oa + kSpecBins;
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+            const int k = lane + 64 * r;
+            if (k <= kSpecN / 2) {
+                oa[k] = make_float2(xa[r].x, xa[r].y);
+                if (hasb) ob[k] = make_float2(xb[r].x, xb[r].y);
+            }
+        }
+    } else {
+        // P[k] = (re re + im im) inv_k, every operation rounded once
+        float pa[9], pb[9];
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+            const int k = lane + 64 * r;
+            const float inv = (k == 0 || k == kSpecN / 2) ? inv_edge : inv_mid;
+            pa[r] = __fmul_rn(__fadd_rn(__fmul_rn(xa[r].x, xa[r].x), __fmul_rn(xa[r].y, xa[r].y)), inv);
+            pb[r] = __fmul_rn(__fadd_rn(__fmul_rn(xb[r].x, xb[r].x), __fmul_rn(xb[r].y, xb[r].y)), inv);
+        }
+        if constexpr (MODE == kSpecBinsMode) {
+            float* const oa = rows + ((size_t)f * T + ta) * kSpecBins;
+            float* const ob = oa + kSpecBins;
+#pragma unroll
+            for (int r = 0; r < 9; ++r) {
+                const int k = lane + 64 * r;
+                if (k <= kSpecN / 2) {
+                    oa[k] = pa[r];
+                    if (hasb) ob[k] = pb[r];
+                }
+            }
+        } else {
+            // the powers through the wave's image (every lane has read its partners), then lane b adds band b in order
+            float* const pw = reinterpret_cast<float*>(img);          // [2][576]
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int r = 0; r < 9; ++r) {
+                const int k = lane + 64 * r;
+                pw[k] = pa[r];
+                pw[576 + k] = pb[r];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lane < bands) {
+                const int e0 = edges[lane], e1 = edges[lane + 1];
+                float sa = 0.0f, sb = 0.0f;
+                for (int k = e0; k < e1; ++k) {
+                    sa = __fadd_rn(sa, pw[k]);
+                    sb = __fadd_rn(sb, pw[576 + k]);
+                }
+                float* const oa = rows + ((size_t)f * T + ta) * bands;
+                oa[lane] = sa;
+                if (hasb) oa[bands + lane] = sb;
+            }
+        }
+    }
+}
+
+// Grid: x = group of four tracks, a wave per track.  hist: [T][1023] becomes the last 1023 samples of hist ++ the call's
+// n B samples: every value is in a register before any is written.
+__global__ __launch_bounds__(256) void spectrum_hist_kernel(const float* __restrict__ in, float* hist, int T, int B,
+                                                           int n_buffers) {
+    const int lane = threadIdx.x & 63;
+    const int t = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const long long L = (long long)n_buffers * B;
+    const bool one_buffer = n_buffers == 1;
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int c = lane + 64 * r;                       // the new row's column: sample L - 1023 + c of the call
+        v[r] = 0.0f;
+        if (t < T && c < kSpecHist) {
+            const long long i = L - kSpecHist + c;
+            v[r] = spec_sample(in, hist, T, B, one_buffer, t, (int)i);
+        }
+    }
+    __syncthreads();
+    if (t < T) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int c = lane + 64 * r;
+            if (c < kSpecHist) hist[(size_t)t * kSpecHist + c] = v[r];
+        }
+    }
+}
+
+// src: [1024]
+struct SpectrumRule {
+    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
+    std::string refusal(unsigned i, int) const {
+        return "window value " + std::to_string(i) + " is not finite; the plan keeps its window";
+    }
+};
+
+}  // namespace
+}  // namespace gab
+
+struct gab_spec_plan {
+    int tracks = 0, bufsize = 0, hop = 0, mode = 0, bands = 0;
+    int phase = 0;                     // samples since the reset, mod hop
+    float inv_edge = 0.0f, inv_mid = 0.0f;     // (float)(1 / S^2), (float)(4 / S^2)
+    const gab::fft::cf* tw = nullptr;  // the device's twiddle table (the library's, not the plan's)
+    gab::DeviceBuf<float> window;      // [1024]
+    gab::DeviceBuf<float> hist;        // [T][1023]
+    gab::DeviceBuf<int> edges;         // [65]
+    gab::DeviceBuf<unsigned> flag;
+
+    int width() const {
+        return mode == GAB_SPEC_COMPLEX ? 2 * gab::kSpecBins : bands ? bands : gab::kSpecBins;
+    }
+    // frames of a call of n buffers from the plan's position
+    long long count(int n_buffers) const { return ((long long)phase + (long long)n_buffers * bufsize) / hop; }
+};
+
+namespace gab {
+namespace {
+
+// S = sum of w in float64, ascending n; the two factors of a power
+void spectrum_scale(gab_spec_plan* p, double S) {
+    p->inv_edge = (float)(1.0 / (S * S));
+    p->inv_mid = (float)(4.0 / (S * S));
+}
+
+// The edge rule: 0 <= e_0 < e_1 < ... < e_bands <= 513.  The first value that breaks it, or -1.
+int spectrum_bad_edge(const int* e, int bands) {
+    for (int b = 0; b <= bands; ++b) {
+        if (e[b] < 0 || e[b] > kSpecBins) return b;
+        if (b > 0 && e[b] <= e[b - 1]) return b;
+    }
+    return -1;
+}
+
+// n buffers in two launches on s (the frames, then the history), from the plan's position; nothing is allocated,
+// nothing waits.  *n_frames: host.
+int spectrum_launch(gab_spec_plan* p, const float* d_in, float* d_rows, int n_buffers, int* n_frames, hipStream_t s,
+                    const char* who) {
+    const long long L = (long long)n_buffers * p->bufsize;
+    if (L > 0x7fffffffLL - kSpecN) return refuse(who, "n_buffers * bufsize must be below 2^31 - 1024");
+    const long long frames = p->count(n_buffers);
+    const long long groups = ((p->tracks + 1) / 2 + 3) / 4;
+    if (frames * groups > (long long)kSpecMaxBlocks)
+        return refuse(who, "more than 2^23 workgroups (frames x tracks / 8) in one call");
+    if (frames > 0) {
+        const dim3 grid((unsigned)(frames * groups));
+        const int first_end = p->hop - p->phase;
+#define GAB_SPEC(MM)                                                                                                   \
+    spectrum_kernel<MM><<<grid, 256, 0, s>>>(d_in, p->hist.get(), p->window.get(), p->edges.get(), d_rows, p->tw,        \
+                                             p->tracks, p->bufsize, n_buffers, p->hop, first_end, (int)frames,           \
+                                             p->bands, p->inv_edge, p->inv_mid)
+        if (p->mode == GAB_SPEC_COMPLEX) GAB_SPEC(kSpecComplex);
+        else if (p->bands == 0) GAB_SPEC(kSpecBinsMode);
+        else GAB_SPEC(kSpecBandsMode);
+#undef GAB_SPEC
+        if (int rc = launch_status("spectrum_kernel")) return rc;
+    }
+    spectrum_hist_kernel<<<dim3((unsigned)((p->tracks + 3) / 4)), 256, 0, s>>>(d_in, p->hist.get(), p->tracks,
+                                                                              p->bufsize, n_buffers);
+    if (int rc = launch_status("spectrum_hist_kernel")) return rc;
+    p->phase = (int)(((long long)p->phase + L) % p->hop);
+    *n_frames = (int)frames;
+    return GAB_OK;
+}
+
+}  // namespace
+}  // namespace gab
+
+extern "C" {
+
+int gab_spec_create(gab_spec_plan** out, int tracks, int bufsize, int hop, int mode, int bands) {
+    return gab::create_entry("gab_spec_create", out, tracks, bufsize, [&] {
+        if (hop < gab::kSpecMinHop || hop > gab::kSpecN) return gab::bad_arg("gab_spec_create: hop must be 32..1024");
+        if (mode != GAB_SPEC_COMPLEX && mode != GAB_SPEC_POWER)
+            return gab::bad_arg("gab_spec_create: mode must be GAB_SPEC_COMPLEX or GAB_SPEC_POWER");
+        if (bands < 0 || bands > gab::kSpecMaxBands) return gab::bad_arg("gab_spec_create: bands must be 0..64");
+        if (mode == GAB_SPEC_COMPLEX && bands != 0)
+            return gab::bad_arg("gab_spec_create: bands need GAB_SPEC_POWER (complex rows have no band form)");
+        return GAB_OK;
+    }, [&](gab_spec_plan& p) {
+        p.hop = hop; p.mode = mode; p.bands = bands;
+        p.tw = gab::fft::device_twiddles();
+        p.window.alloc(gab::kSpecN);
+        p.hist.alloc((size_t)tracks * gab::kSpecHist);
+        p.edges.alloc(gab::kSpecMaxBands + 1);
+        p.flag.alloc(1);
+        // the periodic Hann window, float64, rounded once; S added in ascending n over the rounded values
+        const double pi = 3.14159265358979323846;
+        std::vector<float> w(gab::kSpecN);
+        double S = 0.0;
+        for (int n = 0; n < gab::kSpecN; ++n) {
+            w[(size_t)n] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (double)n / (double)gab::kSpecN));
+            S += (double)w[(size_t)n];
+        }
+        gab::spectrum_scale(&p, S);
+        int e[gab::kSpecMaxBands + 1] = {0};
+        for (int b = 0; b <= bands; ++b) e[b] = bands ? (int)((long long)gab::kSpecBins * b / bands) : 0;
+        GAB_HIP_CHECK(hipMemcpy(p.window.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemcpy(p.edges.get(), e, sizeof(e), hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMemset(p.hist.get(), 0, p.hist.size() * sizeof(float)));
+        GAB_HIP_CHECK(hipStreamSynchronize(nullptr));
+        return GAB_OK;
+    });
+}
+
+int gab_spec_destroy(gab_spec_plan* plan) { return gab::destroy_plan(plan, "gab_spec_destroy: null pointer"); }
+
+// check, then commit (gab_plan.hpp): a refused window, by the device's rule or by the host's on its sum, leaves the
+// plan's as it was
+int gab_spec_set_window(gab_spec_plan* plan, const float* d_window, gab_stream_t stream) {
+    return gab::set_entry("gab_spec_set_window",
+                          [&](gab_spec_plan* p, const float* d_src, int, int, const char* who) -> int {
+        hipStream_t s = gab::as_stream(stream);
+        bool zero_sum = false;
+        const int rc = gab::check_then(p->flag, s, who, d_src, (size_t)gab::kSpecN, gab::SpectrumRule{}, 0, [&] {
+            std::vector<float> w(gab::kSpecN);
+            GAB_HIP_CHECK(hipMemcpyAsync(w.data(), d_src, w.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+            GAB_HIP_CHECK(hipStreamSynchronize(s));
+            double S = 0.0;
+            for (int n = 0; n < gab::kSpecN; ++n) S += (double)w[(size_t)n];
+            if (S == 0.0) { zero_sum = true; return; }
+            GAB_HIP_CHECK(hipMemcpyAsync(p->window.get(), d_src, w.size() * sizeof(float), hipMemcpyDeviceToDevice, s));
+            GAB_HIP_CHECK(hipStreamSynchronize(s));
+            gab::spectrum_scale(p, S);
+        });
+        if (rc) return rc;
+        if (zero_sum) return gab::refuse(who, "the window's sum is zero; the plan keeps its window");
+        return GAB_OK;
+    }, plan, d_window, true, 0, 0);
+}
+
+int gab_spec_set_bands(gab_spec_plan* plan, const int* h_edges) {
+    return gab::entry("gab_spec_set_bands", {plan, h_edges}, [&]() -> int {
+        if (plan->bands == 0) return gab::refuse("gab_spec_set_bands", "the plan has no bands");
+        const int bad = gab::spectrum_bad_edge(h_edges, plan->bands);
+        if (bad >= 0) {
+            gab::set_last_error("gab_spec_set_bands: edge " + std::to_string(bad) + " (" + std::to_string(h_edges[bad]) +
+                                ") breaks 0 <= e_0 < e_1 < ... < e_bands <= 513; the plan keeps its edges");
+            return GAB_ERR_INVALID_ARG;
+        }
+        GAB_HIP_CHECK(hipMemcpy(plan->edges.get(), h_edges, (size_t)(plan->bands + 1) * sizeof(int),
+                                hipMemcpyHostToDevice));
+        return GAB_OK;
+    });
+}
+
+int gab_spec_reset(gab_spec_plan* plan, gab_stream_t stream) {
+    return gab::entry("gab_spec_reset", {plan}, [&] {
+        GAB_HIP_CHECK(hipMemsetAsync(plan->hist.get(), 0, plan->hist.size() * sizeof(float), gab::as_stream(stream)));
+        plan->phase = 0;
+        return GAB_OK;
+    });
+}
+
+int gab_spec_process(gab_spec_plan* plan, const float* d_in, float* d_rows, int* n_frames, gab_stream_t stream) {
+    return gab::entry("gab_spec_process", {plan, d_in, d_rows, n_frames}, [&] {
+        return gab::spectrum_launch(plan, d_in, d_rows, 1, n_frames, gab::as_stream(stream), "gab_spec_process");
+    });
+}
+
+int gab_spec_process_batch(gab_spec_plan* plan, const float* d_in, float* d_rows, int n_buffers, int* n_frames,
+                           gab_stream_t stream) {
+    return gab::batch_entry("gab_spec_process_batch", {plan, d_in, d_rows, n_frames}, n_buffers, [&] {
+        return gab::spectrum_launch(plan, d_in, d_rows, n_buffers, n_frames, gab::as_stream(stream),
+                                    "gab_spec_process_batch");
+    });
+}
+
+int gab_spec_frames(gab_spec_plan* plan, int n_buffers, int* capacity) {
+    return gab::batch_entry("gab_spec_frames", {plan, capacity}, n_buffers, [&]() -> int {
+        const long long L = (long long)n_buffers * plan->bufsize;
+        const long long cap = (L + plan->hop - 1) / plan->hop;
+        if (cap > 0x7fffffffLL) return gab::refuse("gab_spec_frames", "n_buffers * bufsize is too large");
+        *capacity = (int)cap;
+        return GAB_OK;
+    });
+}
+
+int gab_spec_state(gab_spec_plan* plan, float** d_hist, float** d_window, int* position_mod_hop) {
+    return gab::entry("gab_spec_state", {plan, d_hist, d_window, position_mod_hop}, [&] {
+        *d_hist = plan->hist.get();
+        *d_window = plan->window.get();
+        *position_mod_hop = plan->phase;
+        return GAB_OK;
+    });
+}
+
+}  // extern "C"

@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1247,6 +1247,123 @@ class ResamplePlan(_TrackPlan):
         mod period)."""
         h, _, k = self._state()
         return _view(h, self.tracks, self.ntaps - 1).clone(), k
+
+
+def spectrum_band_edges(bands, fs=48000.0, fmin=20.0, fmax=None):
+    """bands + 1 bin edges for SpectrumPlan.set_bands, logarithmically spaced from fmin to fmax (default fs / 2) on
+    the 1024-point grid of fs / 1024 Hz a bin: a fractional-octave display.  Edge b is the bin nearest
+    fmin (fmax / fmin) ** (b / bands), and the table is then made strictly increasing inside [0, 513]: low bands, where
+    the spacing is below a bin, take one bin each."""
+    if not 1 <= bands <= 64:
+        raise ValueError("bands must be 1..64")
+    fmax = fs / 2.0 if fmax is None else fmax
+    if not (0.0 < fmin < fmax <= fs / 2.0):
+        raise ValueError("needs 0 < fmin < fmax <= fs / 2")
+    e = [int(round(fmin * (fmax / fmin) ** (b / bands) * 1024.0 / fs)) for b in range(bands + 1)]
+    e[bands] += 1                                     # fmax's bin belongs to the last band
+    for b in range(1, bands + 1):                     # strictly increasing, upwards
+        e[b] = max(e[b], e[b - 1] + 1)
+    e[bands] = min(e[bands], 513)
+    for b in range(bands - 1, -1, -1):                # and back down below the ceiling
+        e[b] = min(e[b], e[b + 1] - 1)
+    assert e[0] >= 0
+    return e
+
+
+class SpectrumPlan(_TrackPlan):
+    """gab_spec_plan: a short-time Fourier analyser per track.  Frames of 1024 samples every `hop` samples of the
+    stream (the last 1023 samples are carried), under a window (a new plan: periodic Hann), as complex bins
+    (mode="complex": rows [frames][tracks][513][2]), as powers per bin (mode="power": [frames][tracks][513]; a sine of
+    amplitude A on a bin reads A * A) or as powers per band (bands 1..64: [frames][tracks][bands]).  A call emits the
+    frames that end inside it, possibly none; `counts` says how many without a GPU."""
+
+    _destroy = "gab_spec_destroy"
+    N = 1024
+    BINS = 513
+    MODES = {"complex": 0, "power": 1}
+
+    def __init__(self, tracks, bufsize, hop=512, mode="power", bands=0):
+        if mode not in self.MODES:
+            raise ValueError("mode must be 'complex' or 'power'")
+        self.hop, self.mode, self.bands = hop, mode, bands
+        self._create(tracks, bufsize, hop, self.MODES[mode], bands)
+        self.row_shape = (self.BINS, 2) if mode == "complex" else (bands or self.BINS,)
+
+    @staticmethod
+    def counts(bufsize, hop, first_buffer, n):
+        """The frame counts of buffers first_buffer .. first_buffer + n - 1 since a reset: host integers, no GPU."""
+        lo = [(k * bufsize) // hop for k in range(first_buffer, first_buffer + n + 1)]
+        return [b - a for a, b in zip(lo, lo[1:])]
+
+    def frames(self, n_buffers=1):
+        """The largest frame count a call of n_buffers buffers can return: the rows an `out` must hold."""
+        c = C.c_int(0)
+        check(lib.gab_spec_frames(self._h, n_buffers, C.byref(c)))
+        return c.value
+
+    def reset(self):
+        """Zero history, position 0; the window and the band edges stay."""
+        super().reset()
+
+    def set_window(self, w):
+        """w: device tensor [1024], the same for every track; every value finite and the sum not zero.  In force from
+        the next call, the history is kept."""
+        assert w.numel() == self.N
+        check(lib.gab_spec_set_window(self._h, _dev(w), _stream()))
+
+    def set_bands(self, edges):
+        """edges: bands + 1 host integers, 0 <= e_0 < e_1 < ... < e_bands <= 513 (spectrum_band_edges makes them)."""
+        edges = [int(e) for e in edges]
+        if len(edges) != self.bands + 1:
+            raise ValueError("edges must hold bands + 1 = %d integers" % (self.bands + 1))
+        check(lib.gab_spec_set_bands(self._h, (C.c_int * len(edges))(*edges)))
+
+    def _rows_out(self, out, n):
+        cap = self.frames(n)
+        if out is None:
+            out = torch.empty((cap, self.tracks) + self.row_shape, dtype=torch.float32, device="cuda")
+        assert out.numel() >= cap * self.tracks * torch.Size(self.row_shape).numel()
+        return out, cap
+
+    def _cut(self, out, frames):
+        return out.view(-1, self.tracks, *self.row_shape)[:frames]
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize]; returns the rows of the frames that ended in it,
+        [frames][tracks][...] (a view of `out`, or of a new tensor of frames(1) rows), possibly [0]."""
+        out, _ = self._rows_out(out, 1)
+        f = C.c_int(0)
+        self._process("process", x, out, 1, None, C.byref(f), sized=False)
+        return self._cut(out, f.value)
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one call; returns the rows of the frames that ended in them."""
+        n = _n_buffers(self, xs)
+        out, _ = self._rows_out(out, n)
+        f = C.c_int(0)
+        self._process("process_batch", xs, out, n, None, n, C.byref(f), sized=False)
+        return self._cut(out, f.value)
+
+    def state(self):
+        """(a copy of hist [tracks][1023] = the last 1023 samples, oldest first; a copy of the window [1024]; samples
+        since the reset mod hop)."""
+        h, w, p = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib.gab_spec_state(self._h, C.byref(h), C.byref(w), C.byref(p)))
+        return _view(h.value, self.tracks, self.N - 1).clone(), _view(w.value, 1, self.N).clone().view(self.N), p.value
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
+        there (phase 0, bufsize / hop frames a call) and nowhere else."""
+        if self.bufsize % self.hop:
+            raise ValueError("SpectrumPlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
+                             "frame count change from call to call and a prepared or captured call would repeat one "
+                             "of them" % (self.hop, self.bufsize))
+        assert out.numel() >= self.frames(1) * self.tracks * torch.Size(self.row_shape).numel()
+        self._n = C.c_int(0)
+        return (self._h, _dev(x), _dev(out), C.byref(self._n), _stream(stream))
+
+    launch = _launcher("gab_spec_process")
 
 
 def fdtd_default_params(nx, ny=None, nz=None):

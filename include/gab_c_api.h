@@ -547,6 +547,9 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *   resample's position a launch argument, (k mod period) at the capture: every replay resamples from that position.
  *                       The captured call also advanced the host's k by its buffers, as a call that ran; with
  *                       period == 1 both are without effect and the replays are the stream's next buffers.
+ *   spectrum's phase    launch arguments, (p mod H) and the frame count at the capture; the history behind the frames
+ *                       is the device's and moves with every replay.  Where H divides B the phase is 0 and the count
+ *                       B / H on every call, and the replays are the stream's next buffers (tests/test_spectrum_gpu.py).
  * set_* calls and reset synchronise or belong to the host and stay outside a capture.  Held by
  * tests/test_strip_gpu.py for the whole strip in one graph and for every plan alone. */
 
@@ -1310,6 +1313,80 @@ int gab_lim_process_batch(gab_lim_plan* plan, const float* d_in, float* d_out, f
 int gab_lim_params(gab_lim_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_lim_state(gab_lim_plan* plan, float** d_x, float** d_t, float** d_e, size_t* per_track);
 int gab_lim_latency(gab_lim_plan* plan, int* samples);
+
+/* ---- spectrum: a short-time Fourier analyser per track, with carried history (additive; the reference's FFT benchmark
+ * is one stateless transform of 1024 samples, gab_fft_r2c_1024 above) ------------------------------------------------
+ * The running spectrum a channel strip draws beside its equaliser and its meter, and the analysis half of any later
+ * spectral processor.  N = 1024 is the transform, B = bufsize, H the hop (fixed at create, 32 <= H <= 1024, any
+ * integer), T = tracks.
+ *   stream, frames  s[a] is a track's stream, a the absolute sample index since create or reset, s[a] = 0 for a < 0.
+ *                   Frame j >= 1 covers samples jH - N .. jH - 1:
+ *                     f_j[n] = w[n] * s[jH - N + n]                       one float32 product, rounded once
+ *                   A call that takes samples [p, p + n B) emits exactly the frames with p < jH <= p + n B, in ascending
+ *                   j: floor((p + n B) / H) - floor(p / H) of them, possibly none.  The count is host integer arithmetic
+ *                   on the carried p mod H and is returned in *n_frames without touching the device.  gab_spec_frames
+ *                   gives the largest count any call of n_buffers buffers can return, ceil(n_buffers B / H): what
+ *                   d_rows must hold.  Rows past *n_frames are not written; a call that emits no frame writes none.
+ *                   The plan carries the last 1023 samples of every track on the device.
+ *   window          w: 1024 floats, the same for every track.  A new plan holds the periodic Hann window
+ *                   0.5 - 0.5 cos(2 pi n / N), made in float64 on the host and rounded once.  S is the float64 sum of
+ *                   the float32 values, added in ascending n.  set_window takes d_window (device, [1024]); checked on
+ *                   the device first: the first value that is not finite is named with GAB_ERR_INVALID_ARG; then on the
+ *                   host: a table with S == 0 is refused.  A refused set leaves the plan as it was.  An accepted window
+ *                   is in force from the next call; the history is kept.  Synchronous with respect to `stream`.
+ *   modes           fixed at create.
+ *                   GAB_SPEC_COMPLEX (bands = 0): d_rows [frames][T][513][2], the unnormalised spectrum of f_j in the
+ *                     layout of gab_fft_r2c_1024 (bins 0..512, re then im).
+ *                   GAB_SPEC_POWER, bands = 0: d_rows [frames][T][513],
+ *                     P[k] = (re * re + im * im) * inv_k        every operation rounded once, no fused multiply-add
+ *                     inv_k = (float)(4 / S^2) for 0 < k < 512, (float)(1 / S^2) for k = 0 and k = 512    (in float64)
+ *                     with (re, im) the bits of the complex mode.  So a sine of amplitude A on a bin reads A^2 and a
+ *                     constant c reads c^2.  Linear; decibels are the caller's business.  (A window whose S^2 leaves
+ *                     float32's range gives an inv_k of 0 or infinity.)
+ *                   GAB_SPEC_POWER, 1 <= bands <= 64: d_rows [frames][T][bands]; band b is the float32 sum of P[k] for
+ *                     e_b <= k < e_(b+1), added in ascending k from 0.0f.  set_bands takes bands + 1 HOST integers,
+ *                     checked on the host: 0 <= e_0 < e_1 < ... < e_bands <= 513; the first edge that breaks the rule
+ *                     is named and the plan keeps its edges.  A new plan holds e_b = floor(513 b / bands).  set_bands is
+ *                     a blocking copy: in force from the next call; it is the caller's to have no call of the plan in
+ *                     flight on a non-blocking stream.
+ *   channel pairs   Tracks 2q and 2q + 1 share one complex transform (an odd last track beside zeros), as in
+ *                   gab_fft_r2c_1024: a track's absolute error in any bin follows its PAIR's spectral peak, not its own
+ *                   (tests/test_spectrum_gpu.py holds every frame within four times the float32 restatement of
+ *                   tests/spectrum_twin.py, over peak_a + peak_b).  A silent track beside a loud partner holds the
+ *                   partner's rounding error.  A silent pair gives zeros.  A pair depends on nothing outside itself,
+ *                   bit for bit; a NaN or an infinity in one track makes the frames of its pair that hold it non-finite
+ *                   (at most ceil(N / H) of them) and touches no other pair and no later frame.
+ *   determinism     A frame's bits depend on two things only: the 1024 windowed samples of its pair, and (powers) S.
+ *                   Not on B, on how the stream was cut into calls or batches, on the alignment of d_in, on the hop or
+ *                   on which other frames were in the launch.  The band form's bits are the ordered float32 sum of the
+ *                   bin form's bits.  A pair-aligned shard of tracks as its own plan gives those tracks' bits.
+ *   layout          d_in [n][T][B] float32, track-major per buffer, any 4-byte alignment, never written; d_rows may not
+ *                   overlap it.  process is process_batch with n = 1.
+ *   reset           zeroes the history and the position; the window and the edges stay.
+ *   state           the plan's own memory, for inspection: d_hist [T][1023], the last 1023 samples oldest first;
+ *                   d_window [1024]; the third value is p mod H.
+ * A call is two launches on `stream`, the frames and then (a wave per track, every value in a register before any is
+ * written) the history, so no frame races with the history it reads; it allocates nothing and waits for nothing, and all
+ * changing state but p mod H is on the device.  The frame phase p mod H and the count are launch arguments: a captured
+ * process replays one phase ("Captured calls", above) and is the stream's next buffer only where H divides B, where
+ * the phase is 0 and the count B / H on every call.  Arguments are checked before any device call: tracks >= 1,
+ * bufsize >= 1, 32 <= hop <= 1024, bands 0..64 and 0 with GAB_SPEC_COMPLEX, n_buffers B < 2^31 - 1024, and at most
+ * 2^23 workgroups (frames x ceil(T / 8)) a call.  Out of scope: averaging, peak hold or decay across frames (a line of
+ * torch on the rows), other transform sizes, a window per track, an inverse transform, complex rows in bands.
+ * One thread at a time per plan.                                                                                     */
+typedef struct gab_spec_plan gab_spec_plan;
+#define GAB_SPEC_COMPLEX 0
+#define GAB_SPEC_POWER 1
+int gab_spec_create(gab_spec_plan** plan, int tracks, int bufsize, int hop, int mode, int bands);
+int gab_spec_destroy(gab_spec_plan* plan);
+int gab_spec_set_window(gab_spec_plan* plan, const float* d_window, gab_stream_t stream);
+int gab_spec_set_bands(gab_spec_plan* plan, const int* h_edges);
+int gab_spec_reset(gab_spec_plan* plan, gab_stream_t stream);
+int gab_spec_process(gab_spec_plan* plan, const float* d_in, float* d_rows, int* n_frames, gab_stream_t stream);
+int gab_spec_process_batch(gab_spec_plan* plan, const float* d_in, float* d_rows, int n_buffers, int* n_frames,
+                           gab_stream_t stream);
+int gab_spec_frames(gab_spec_plan* plan, int n_buffers, int* capacity);
+int gab_spec_state(gab_spec_plan* plan, float** d_hist, float** d_window, int* position_mod_hop);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
