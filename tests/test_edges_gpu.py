@@ -1,4 +1,4 @@
-"""The six bit-exact plans on the device at the edges of float32: tails that die through the subnormals, sums across
+"""Eight bit-exact plans on the device at the edges of float32: tails that die through the subnormals, sums across
 FLT_MAX, signed zeros, NaN and infinity containment, and one strip case.
 
 Every case is a row of tests/test_edges_host.py's CASES.  Its tape of calls, recorded while the float32 twin ran it, is
@@ -13,11 +13,14 @@ import types
 import numpy as np
 import pytest
 
+import limiter_twin
+import spectrum_twin as st
 from plan_helpers import dev, gab, host  # noqa: F401 (gab: the fixture)
 from strip_helpers import DeviceStrip, differing as strip_differing, same, schedule, states_differing
 from test_delay_host import capacity as delay_capacity
-from test_edges_host import (CASES, case_id, delay_first_refused, differing, dyn_first_refused, mix_first_refused,
-                             mix_form, play, reference, strip_tail)
+from test_crossover_host import xover_first_refused
+from test_edges_host import (CASES, HostSpec, case_id, delay_first_refused, differing, dyn_first_refused,
+                             mix_first_refused, mix_form, play, reference, strip_tail)
 from test_gate_host import gate_first_refused
 from test_reverb_host import first_refused_param as reverb_first_refused
 
@@ -290,8 +293,149 @@ class DevGate(Dev):
         return {"current": host(cur), "target": host(tgt), "gain": host(g), "count": host(c)}
 
 
+class DevLim(Dev):
+    def __init__(self, gab, offset, T, B, W, link):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape = gab.LimiterPlan(T, B, W, link), (T, B)
+        assert self.p.latency == W - 1
+
+    def rule(self, p):
+        return limiter_twin.first_refused(p)
+
+    def launch(self, xs, keys, batch):
+        n, (T, B) = len(xs), self.shape
+        x, gr = self.mem.put(np.stack(xs)), self.mem.blank(n * T)
+        out = x if self.inplace else self.mem.blank(n * T * B)
+        (self.p.process_batch if batch else self.p.process)(x, out=out, gr=gr)
+        return [{"y": y, "gr": g} for y, g in zip(host(out).reshape(n, T, B), host(gr).reshape(n, T))]
+
+    def state(self, twin):
+        (cur, tgt), (xd, t, e) = self.p.params(), self.p.state()
+        return {"current": host(cur), "target": host(tgt), "xd": host(xd), "t": host(t), "e": host(e)}
+
+
+class DevXover(Dev):
+    """Whether the plan has rows is not exposed: the actor keeps count of the sets that were accepted, and holds the
+    plan to it by the refusal of process() for as long as there was none (a refused call launches nothing)."""
+
+    NO_SPLITS = "no splits have been set: gab_xover_set_splits comes first"
+
+    def __init__(self, gab, offset, T, B, K):
+        Dev.__init__(self, gab, offset)
+        self.p, self.shape, self.accepted = gab.CrossoverPlan(T, B, K), (T, B, K), 0
+
+    def splits(self, rows):
+        self.p.set_splits(dev(rows))
+        self.accepted += 1
+
+    def splits_tracks(self, rows, first_track):
+        self.p.set_splits(dev(rows), first_track=first_track, n_tracks=rows.shape[0])
+        self.accepted += 1
+
+    def refused(self, rows, first_track):
+        i, width = xover_first_refused(rows), 3 * (self.shape[2] - 1)
+        assert i is not None
+        with pytest.raises(self.gab.GabError) as e:
+            self.p.set_splits(dev(rows), first_track=first_track)
+        assert e.value.code == -1 and self.named(i, first_track, width) in str(e.value), (str(e.value), i)
+
+    def unset_run(self, x):
+        assert self.accepted == 0
+        for batch in (False, True):
+            with pytest.raises(self.gab.GabError) as e:
+                self.launch([x], [None], batch)
+            assert e.value.code == -1 and self.NO_SPLITS in str(e.value), str(e.value)
+
+    def launch(self, xs, keys, batch):
+        n, (T, B, K) = len(xs), self.shape
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(n * K * T * B)
+        (self.p.process_batch if batch else self.p.process)(x, out=out)
+        return [{"bands": y} for y in host(out).reshape(n, K, T, B)]
+
+    def state(self, twin):
+        if not self.accepted:
+            self.unset_run(np.zeros(self.shape[:2], np.float32))
+        return {"state": host(self.p.state()), "rows": host(self.p.splits()),
+                "has_rows": np.array([self.accepted > 0], np.int64)}
+
+
+class DevSpec(Dev):
+    """The transform is no bit twin, so the rows of a frame are held to a second device plan, `one`, of bufsize = hop =
+    1024 with the window and edges in force: reset before every frame and given the frame's 1024 raw samples as the host
+    actor holds them (history plus call), it must give the walked plan's rows bit for bit (a frame's bits depend only
+    on its pair's windowed samples).  The framing is the host's, so an error in it cannot be on both sides.  The frame
+    count of every call is exact.  `seen` keeps (raw samples, window, rows) of every frame for the accuracy bound."""
+
+    def __init__(self, gab, offset, T, B, H, mode, bands):
+        Dev.__init__(self, gab, offset)
+        self.p, self.one = gab.SpectrumPlan(T, B, H, mode, bands), gab.SpectrumPlan(T, st.N, st.N, mode, bands)
+        self.shape, self.bands, self.shadow, self.seen = (T, B, H), bands, HostSpec(T, B, H, mode, bands), []
+        assert self.one.frames(1) == 1
+
+    def window(self, w):
+        for p in (self.p, self.one):
+            p.set_window(dev(w))
+        self.shadow.window(w)
+
+    def edges(self, e):
+        for p in (self.p, self.one):
+            p.set_bands(e)
+        self.shadow.edges(e)
+
+    def refusal(self, call, text):
+        with pytest.raises(self.gab.GabError) as e:
+            call()
+        assert e.value.code == -1 and text in str(e.value), str(e.value)
+
+    def refused_window(self, w):
+        k = st.bad_window(w)
+        assert k is not None
+        text = "the window's sum is zero" if k == "sum" else "window value %d is not finite" % k
+        self.refusal(lambda: self.p.set_window(dev(w)), text + "; the plan keeps its window")
+
+    def refused_edges(self, e):
+        b = st.bad_edge(list(e), self.bands)
+        assert b >= 0
+        self.refusal(lambda: self.p.set_bands(e), "edge %d (%d) breaks 0 <= e_0 < e_1 < ... < e_bands <= 513; the plan "
+                                                  "keeps its edges" % (b, e[b]))
+
+    def reset(self):
+        self.p.reset()
+        self.shadow.reset()
+
+    def launch(self, xs, keys, batch):
+        n, (T, B, H) = len(xs), self.shape
+        want = [self.shadow.run(x) for x in xs]                     # the host's counts and raw frames
+        per_row = T * int(np.prod(self.p.row_shape))
+        x, out = self.mem.put(np.stack(xs)), self.mem.blank(self.p.frames(n) * per_row)
+        rows = (self.p.process_batch if batch else self.p.process)(x, out=out)
+        F = rows.shape[0]
+        counts = [int(w["count"][0]) for w in want]
+        if not batch:
+            counts = [F]                                             # (a batch returns one count: held as the sum)
+        assert F == sum(counts), (F, counts)
+        flat = host(out)
+        assert (flat[F * per_row:] == 7.0).all()                     # rows past the count are not written
+        got, raw = host(rows), np.concatenate([w["raw"] for w in want])
+        assert raw.shape[0] == F
+        for j in range(F):
+            self.one.reset()
+            single = self.one.process(self.mem.put(raw[j]))
+            assert single.shape[0] == 1 and same(host(single)[0], got[j]), (len(self.seen), j)
+            self.seen.append((raw[j], self.shadow.framer.w.copy(), got[j]))
+        return [{"count": np.array([c], np.int64), "raw": w["raw"]} for c, w in zip(counts, want)]
+
+    def state(self, twin):
+        hist, w, p = self.p.state()
+        return {"hist": host(hist), "window": host(w), "pos": np.array([p], np.int64)}
+
+    def close(self):
+        self.p.close()
+        self.one.close()
+
+
 DEVS = {"mix": DevMix, "delay": DevDelay, "meter": DevMeter, "resample": DevResample, "dyn": DevDyn, "reverb": DevReverb,
-        "gate": DevGate}
+        "gate": DevGate, "lim": DevLim, "xover": DevXover, "spec": DevSpec}
 
 
 def run_on_device(gab, case, ops, batch):

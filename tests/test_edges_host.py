@@ -1,5 +1,5 @@
-"""The six bit-exact plans (mix, delay, meter, resample, dynamics, reverb) at the edges of float32, without a GPU: the
-yardstick is shown to be exact there, and the cases are shown to reach the edge.
+"""Eight bit-exact plans (mix, delay, meter, resample, dynamics, reverb, limiter, crossover) at the edges of float32,
+without a GPU: the yardstick is shown to be exact there, and the cases are shown to reach the edge.
 
     1. numpy keeps subnormals in this process (nothing below means anything if it flushes).
     2. every fma32 the twins use (tests/test_mix_host.py, and the wrappers of test_meter_host.py, test_resample_host.py
@@ -18,10 +18,15 @@ The regimes:
              a few units up to -0 through the negative subnormals.
     quiet    dynamics only: noise at 2^-120 under gain reduction, the detector on its 2^-96 floor.
     flt_max  noise at 2^126 or 2^127: some samples overflow, their neighbours do not; an inf - inf in the loops; then
-             ordinary buffers while the damage lasts, a reset, and a buffer that must be finite again.
+             ordinary buffers while the damage lasts, a reset, and a buffer that must be finite again.  Limiter: drives
+             above 1, so that xd = drive x overflows, and every ceiling on a ramp from one end of its admitted range to
+             the other (2^-32, 2^32); a need of 2^-32 / 2^127 is zero, and zero times an infinite xd a NaN.  Its finite
+             outputs stay at or below the ceiling, so no finite value above 2^127 stands beside its infinities.
+             Crossover: splits at 20 Hz and at 23 kHz; the integrators overflow, inf - inf follows, and the NaN stays
+             in the state (a set keeps it) until the reset.
     zeros    blocks of +0.0, of -0.0 and of both, on a steady buffer, a ramp buffer and the buffer behind a ramp buffer;
              tables with negative values and -0.0 (rows that do not move keep their -0.0 across a ramp, which is where
-             fmaf(+0, r, -0.0) = +0.0 shows).
+             fmaf(+0, r, -0.0) = +0.0 shows).  Crossover: no ramp; the blocks stand on the buffers behind each set.
     contain  mix and delay: a NaN in track 64 and an infinity in the last track of buffer 1, beside the same case clean.
 
 A mix plan cannot produce a -0.0 (a leaf's chain starts from +0.0, and +0 + -0 is +0), and a meter's rows cannot either
@@ -41,6 +46,11 @@ import test_resample_host
 import test_reverb_host
 from plan_helpers import bits
 from strip_helpers import OUTPUTS, HostStrip, same, scenario, schedule
+import limiter_twin
+import spectrum_twin
+from test_crossover_host import Twin as XoverTwin
+from test_crossover_host import rows32 as xover_rows32
+from test_crossover_host import xover_first_refused
 from test_delay_host import Twin as DelayTwin
 from test_delay_host import capacity as delay_capacity
 from test_delay_host import delay_mix
@@ -470,8 +480,118 @@ class HostGate(Host):
         return True
 
 
+class HostLim(Host):
+    def __init__(self, T, B, W, link):
+        self.twin = limiter_twin.Twin(T, B, W, link)
+
+    def params(self, p, ramp):
+        self.twin.set_params(p, ramp=ramp)
+
+    def rule(self, p):
+        return limiter_twin.first_refused(p)
+
+    def reset(self):
+        self.twin.reset()
+
+    def run(self, x, key=None):
+        y, gr = self.twin.process(x)
+        return {"y": y, "gr": gr}
+
+    def state(self):
+        t = self.twin
+        xd, th, e = t.hist
+        return {"current": t.cur.copy(), "target": t.tgt.copy(), "xd": xd.copy(), "t": th.copy(), "e": e.copy()}
+
+    def dead(self):
+        return True
+
+
+XOVER_NO_ROW = np.array([1.0, 0.0, 0.0], np.float32)          # what a first ranged set leaves on the rows it did not name
+
+
+class HostXover(Host):
+    """The crossover's life-cycle on the host: no rows until a set is accepted (unset_run() is a run on such a plan:
+    refused, nothing changes), a refused set is no set, a set keeps the state."""
+
+    def __init__(self, T, B, K):
+        self.twin = XoverTwin(T, B, K)
+
+    def splits(self, rows):
+        self.twin.set_splits(rows)
+
+    def splits_tracks(self, rows, first_track):
+        self.twin.set_splits(rows, first_track=first_track)
+
+    def refused(self, rows, first_track):
+        assert xover_first_refused(rows) is not None
+
+    def unset_run(self, x):
+        assert self.twin.rows is None
+
+    def reset(self):
+        self.twin.reset()
+
+    def run(self, x, key=None):
+        return {"bands": self.twin.process(x)}
+
+    def state(self):
+        t = self.twin
+        rows = np.tile(XOVER_NO_ROW, (t.T, t.S, 1)) if t.rows is None else t.rows.copy()
+        return {"state": t.state.copy(), "rows": rows, "has_rows": np.array([t.rows is not None], np.int64)}
+
+    def dead(self):
+        return quiet(self.twin.state)
+
+
+class HostSpec(Host):
+    """The spectrum plan's carried state (spectrum_twin.Framer) with the window and the edges in force.  run() returns
+    the call's frame count and its frames' 1024 raw samples each (history plus call), which a device actor feeds to a
+    single-frame plan: the transform is no bit twin, the framing is."""
+
+    def __init__(self, T, B, H, mode, bands):
+        self.framer, self.mode, self.bands = spectrum_twin.Framer(T, B, H), mode, bands
+        self.band_edges = spectrum_twin.default_edges(bands) if bands else None
+
+    def window(self, w):
+        assert spectrum_twin.bad_window(w) is None
+        self.framer.w = np.array(w, np.float32)
+
+    def edges(self, e):
+        assert spectrum_twin.bad_edge(list(e), self.bands) == -1
+        self.band_edges = [int(v) for v in e]
+
+    def refused_window(self, w):
+        assert spectrum_twin.bad_window(w) is not None
+
+    def refused_edges(self, e):
+        assert spectrum_twin.bad_edge(list(e), self.bands) >= 0
+
+    def reset(self):
+        self.framer.reset()
+
+    def run(self, x, key=None):
+        f = self.framer
+        both = np.concatenate([f.hist, np.asarray(x, np.float32)], axis=1)
+        ends = spectrum_twin.frame_ends(f.p, f.B, f.H)
+        at = [e - f.p + spectrum_twin.HIST for e in ends]
+        raw = np.zeros((len(at), f.T, spectrum_twin.N), np.float32)
+        for j, c in enumerate(at):
+            raw[j] = both[:, c - spectrum_twin.N:c]
+        assert len(ends) == spectrum_twin.count(f.p, f.B, f.H)
+        taken = f.take(x[None])
+        assert same(taken, f.w[None, None, :] * raw)              # the Framer's own frames are these under its window
+        return {"count": np.array([len(ends)], np.int64), "raw": raw}
+
+    def state(self):
+        f = self.framer
+        return {"hist": f.hist.copy(), "window": f.w.copy(), "pos": np.array([f.p % f.H], np.int64)}
+
+    def dead(self):
+        return True
+
+
 HOSTS = {"mix": HostMix, "delay": HostDelay, "meter": HostMeter, "resample": HostResample, "dyn": HostDyn,
-         "reverb": HostReverb, "gate": HostGate}
+         "reverb": HostReverb, "gate": HostGate, "lim": HostLim, "xover": HostXover, "spec": HostSpec}
 
 
 def lvl(rng, shape, e):
@@ -695,8 +815,62 @@ def build_reverb(t, regime, rng, dirty, T, B, N, O, M):
         zeros_script(t, T, B, rng, t.params, p[0], some_rows(p[0], p[1], rng), some_rows(p[1], p[2], rng))
 
 
+def build_lim(t, regime, rng, dirty, T, B, W, link):
+    p = [limiter_twin.lim_mix(T, rng.randint(1 << 20)) for _ in range(3)]
+    if regime == "flt_max":
+        ends = np.where(np.arange(T) % 2 == 0, 2.0 ** -32, 2.0 ** 32).astype(np.float32)
+        for k, q in enumerate(p):
+            q[:, limiter_twin.DRIVE] = rng.uniform(1.0, 4.0, T)       # drive above 1: xd = drive x crosses FLT_MAX
+            q[:, limiter_twin.CEIL] = ends if k % 2 == 0 else ends[::-1]   # both ends of the admitted range, swapped
+        t.params(p[0], False)
+        t.run(lvl(rng, (T, B), 126), None)
+        t.params(p[1], True)                                      # every ceiling ramps from one end to the other
+        t.run(lvl(rng, (T, B), 127), None)
+        t.run(lvl(rng, (T, B), 126), None)
+        for _ in range(2):                                        # the infinities sit in the xd history for W - 1 samples
+            t.run(lvl(rng, (T, B), 0), None)
+        t.reset()
+        t.run(lvl(rng, (T, B), 0), None)
+    else:
+        p = [sprinkle(q, rng, cols=(limiter_twin.DRIVE, limiter_twin.REL)) for q in p]      # (no ceiling is -0.0)
+        zeros_script(t, T, B, rng, t.params, p[0], some_rows(p[0], p[1], rng), some_rows(p[1], p[2], rng))
+
+
+def xover_edge_rows(T, K, rng):
+    """[T][K - 1][3]: the splits of test_crossover_host.SETS that lie against both ends of the band (20 Hz and 23 kHz)
+    on the even tracks, splits drawn per track on the odd ones."""
+    S = K - 1
+    f = np.sort(np.exp(rng.uniform(np.log(30.0), np.log(18000.0), (T, S))), axis=1)
+    f[::2] = {1: [20.0], 2: [20.0, 23000.0], 3: [20.0, 25.0, 23000.0]}[S]
+    if S == 1:
+        f[::4] = 23000.0
+    return np.stack([xover_rows32(row) for row in f])
+
+
+def build_xover(t, regime, rng, dirty, T, B, K):
+    rows = [xover_edge_rows(T, K, rng) for _ in range(2)]
+    if regime == "flt_max":
+        t.splits(rows[0])
+        t.run(lvl(rng, (T, B), 126), None)
+        t.run(lvl(rng, (T, B), 127), None)                        # finite: the integrators overflow inside
+        t.splits(rows[1])                                         # a set keeps the state, the infinities in it too
+        t.run(lvl(rng, (T, B), 126), None)
+        for _ in range(2):
+            t.run(lvl(rng, (T, B), 0), None)                      # a NaN in an integrator stays for good
+        t.reset()
+        t.run(lvl(rng, (T, B), 0), None)
+    else:
+        pz, nz, ck = zero_blocks(T, B, rng)
+        t.splits(rows[0])
+        for x in (pz, nz, ck):
+            t.run(x, None)
+        t.splits(rows[1])
+        for x in (nz, ck, pz):                                    # the buffers behind a set
+            t.run(x, None)
+
+
 BUILDERS = {"mix": build_mix, "delay": build_delay, "meter": build_meter, "resample": build_resample, "dyn": build_dyn,
-            "reverb": build_reverb}
+            "reverb": build_reverb, "lim": build_lim, "xover": build_xover}
 
 Case = collections.namedtuple("Case", "plan regime shape seed offset want")
 COUNTS = ("subnormal outputs", "subnormal state words", "+inf", "-inf", "NaN", "-0.0")
@@ -766,8 +940,10 @@ def counts(outs, state):
 # plan, regime, shape, seed, a pointer 4 bytes off, the pinned counts (COUNTS' order).
 # Shapes.  mix: (tracks, bufsize, buses, layout); delay: (tracks, bufsize, max_delay, interp); meter: (tracks, bufsize,
 # window); resample: (tracks, bufsize, up, down, taps); dyn: (tracks, bufsize, link, keyed); reverb: (tracks, bufsize,
-# lines, outs, max_delay).  130 tracks: two full owners of 64 and a partial one; reverb gives a wave 64 / lines tracks:
-# 34 tracks of 4 lines, 9 of 16.  bufsize 100: scalar loads and a partial last chunk; 128: the vector forms.
+# lines, outs, max_delay); lim: (tracks, bufsize, W, link); xover: (tracks, bufsize, bands).  130 tracks: two full owners
+# of 64 and a partial one; reverb gives a wave 64 / lines tracks: 34 tracks of 4 lines, 9 of 16; a limiter's wave owns
+# 8 tracks, and 128 tracks at link 64 take its detector launch in front; a crossover's wave owns 64, 32 or 16 tracks
+# for 2, 3 or 4 bands.  bufsize 100: scalar loads and a partial last chunk; 128: the vector forms.
 CASES = [
     Case("mix", "tail", (130, 100, 2, "track"), 1, False, (68, 254, 0, 0, 0, 0)),
     Case("mix", "tail", (130, 128, 33, "sample"), 2, True, (1496, 4242, 0, 0, 0, 0)),
@@ -815,6 +991,14 @@ CASES = [
     Case("reverb", "flt_max", (34, 128, 4, 1, 64), 44, False, (0, 0, 398, 420, 1601, 0)),
     Case("reverb", "zeros", (34, 128, 4, 2, 64), 45, False, (0, 0, 0, 0, 0, 3457)),
     Case("reverb", "zeros", (9, 100, 16, 1, 64), 46, False, (0, 0, 0, 0, 0, 308)),
+    Case("lim", "flt_max", (130, 100, 32, 2), 47, False, (0, 0, 1352, 1346, 10, 7554)),
+    Case("lim", "flt_max", (128, 128, 256, 64), 48, True, (0, 0, 1348, 1298, 411, 9927)),
+    Case("lim", "zeros", (130, 128, 32, 2), 49, False, (0, 0, 0, 0, 0, 52204)),
+    Case("lim", "zeros", (128, 100, 256, 64), 50, False, (0, 0, 0, 0, 0, 17165)),
+    Case("xover", "flt_max", (130, 100, 2), 55, False, (0, 0, 13, 13, 31151, 0)),
+    Case("xover", "flt_max", (130, 128, 4), 52, True, (0, 0, 29, 32, 84263, 0)),
+    Case("xover", "zeros", (130, 100, 3), 53, False, (0, 0, 0, 0, 0, 38882)),
+    Case("xover", "zeros", (130, 128, 2), 54, False, (0, 0, 0, 0, 0, 50044)),
 ]
 
 
@@ -842,14 +1026,17 @@ def test_the_cases_reach_the_edge(case):
     if regime == "flt_max":
         assert pinf > 0 and (ninf > 0 or plan == "meter")         # a meter's fields are magnitudes
         assert nan > 0 or plan in ("dyn", "resample")             # neither can make a NaN of finite samples
-        # one buffer holds +inf, -inf and finite values above 2^127 side by side
-        assert any(any((a == np.inf).any() for a in floats(o)) and any(big(a).any() for a in floats(o))
+        # one buffer holds +inf, -inf and finite values above 2^127 side by side (the limiter: finite values that are
+        # not zero; whatever it puts out that is finite is at or below its ceiling, and no ceiling is above 2^32)
+        top = big if plan != "lim" else (lambda a: np.isfinite(a) & (a != 0))
+        assert plan != "lim" or all((np.abs(o["y"][np.isfinite(o["y"])]) <= f32(2.0 ** 32)).all() for o in outs)
+        assert any(any((a == np.inf).any() for a in floats(o)) and any(top(a).any() for a in floats(o))
                    and (plan == "meter" or any((a == -np.inf).any() for a in floats(o))) for o in outs)
     if regime == "flt_max" and any(op[0] == "reset" for op in ops):
         assert all(np.isfinite(a).all() for a in floats(outs[-1]))                   # after the reset: a new plan's
         fresh = HOSTS[plan](*case.shape)
         for op in ops:                                            # the tables in force, a new plan otherwise
-            if op[0] in ("params", "gains", "delays", "decay"):
+            if op[0] in ("params", "gains", "delays", "decay", "splits"):
                 getattr(fresh, op[0])(*(op[1:-1] + (False,) if op[0] in ("params", "gains") else op[1:]))
         last = [op for op in ops if op[0] == "run"][-1]
         assert differing([fresh.run(*last[1:])], outs[-1:]) == []
