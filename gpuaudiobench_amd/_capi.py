@@ -103,8 +103,10 @@ PROTOTYPES = {
     "gab_modal": (_I, [_P, _P, _I, _I, _I, _P]),
     "gab_modal_bank_workspace_bytes": (_Z, [_I, _I, _I]),
     "gab_modal_bank": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "gab_debug_modal_launch": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "gab_dwg_workspace_bytes": (_Z, [_I, _I]),
     "gab_dwg": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "gab_debug_dwg_route": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "gab_fft_r2c_1024": (_I, [_P, _P, _I, _P]),
     "gab_conv_create": (_I, [C.POINTER(_P), _I, _I, _I]),
     "gab_conv_create_scheme": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
@@ -142,6 +144,7 @@ PROTOTYPES = {
     "gab_fdtd_copy_pressure": (_I, [_P, _P, _P]),
     "gab_fdtd_resident": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "gab_fdtd_set_form": (_I, [_P, _I]),
+    "gab_debug_fdtd_form": (_I, [_P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I)]),
     "gab_fdtd_status": (_I, [_P, _P]),
     "gab_fdtd_set_track_positions": (_I, [_P, C.POINTER(_I), C.POINTER(_I), _I]),
     "gab_fdtd_create_slab": (_I, [C.POINTER(_P), C.POINTER(FdtdParams), _I, _I]),

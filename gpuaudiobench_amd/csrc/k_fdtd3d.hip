@@ -1151,8 +1151,58 @@ int create_slab(gab_fdtd_plan** out, const gab_fdtd_params* params, int z_begin,
 // 2 us stagger of odd planes that round 2 used to overlap loads and stores then only costs time)
 constexpr bool kFdtdHoist = true;
 
+// The kernel form of ONE leapfrog step over the plan's own planes, by the row width (see the kernels above): the one
+// place that decides it (launch_step follows it, gab_debug_fdtd_form reports it).
+int step_form(const gab_fdtd_plan* f) {
+    const gab_fdtd_params& P = f->P;
+    const int nzl = f->z_end - f->z_begin;
+#ifdef GAB_ABLATE
+    static const int tile_env = getenv("GAB_FDTD_TILE_THREADS") ? atoi(getenv("GAB_FDTD_TILE_THREADS")) : 0;
+#else
+    constexpr int tile_env = 0;
+#endif
+    const bool vec4 = (P.nx % 4) == 0;
+    const int tx = vec4 ? P.nx / 4 : P.nx;                    // threads along x
+    if (!vec4) return GAB_FDTD_KERNEL_STEP_SCALAR;
+    if (!(f->lds_tiles && tx > 16 && tx <= 64)) return GAB_FDTD_KERNEL_STEP_VEC4;
+    // whole x extent in one workgroup: LX x ROWS threads, (ROWS + 2) pressure rows in LDS.
+    // 512-thread tiles (half as many halo rows) once they still make >= 4 workgroups
+    // per CU; 256-thread tiles below that (measured: 13.6 vs 14.3 us/step at 128^3,
+    // 47.5 vs 49.6 at 200^3, but 9.5 vs 8.8 at 96^3)
+    const int lx = tx <= 32 ? 32 : 64;
+    bool big = (long)((P.ny + 512 / lx - 1) / (512 / lx)) * nzl >= 1024;
+    if (tile_env) big = tile_env == 512;
+    if (lx == 32) return big ? GAB_FDTD_KERNEL_LDS_32X16 : GAB_FDTD_KERNEL_LDS_32X8;
+    return big ? GAB_FDTD_KERNEL_LDS_64X8 : GAB_FDTD_KERNEL_LDS_64X4;
+}
+
+// What one gab_fdtd_process call does: the kernel form, how often the ping-pong pair swaps, and whether the launches go
+// through the plan's graph cache.  The one place that decides it (gab_fdtd_process follows it, gab_debug_fdtd_form
+// reports it).
+struct FdtdChoice {
+    int form;           // GAB_FDTD_KERNEL_*
+    long swaps;         // ping-pong swaps of the call (the resident kernel works in place: 0)
+    bool graph;
+};
+FdtdChoice choose_form(const gab_fdtd_plan* f, int n_samples, bool capturing) {
+    const gab_fdtd_params& P = f->P;
+    FdtdChoice c;
+    // (not inside a caller's stream capture: the exchange tags are a launch argument that a replay would freeze)
+    const bool resident = f->resident && !f->form_step && f->res_rpt > 0 && !f->pos_tracks && !capturing;
+    // rooms up to 56 cells wide (where one step is shorter than a kernel boundary) take one
+    // launch per SAMPLE: three steps inside a tile (fdtd_sample_tile_kernel).  Measured per step:
+    // 20^3 1.98 vs 3.8 us, 32^3 2.11 vs 3.7, 52^3 3.49 vs 4.2, 56^3 3.59; at 64^3 the one-step chain wins
+    const bool by_sample = f->sample_tiles && !f->pos_tracks && P.steps_per_sample == 3 && f->z_begin == 0 &&
+                           f->z_end == P.nz && P.nx <= 56 && P.ny <= 56 && P.nz <= 56;
+    c.form = resident ? GAB_FDTD_KERNEL_RESIDENT : by_sample ? GAB_FDTD_KERNEL_SAMPLE_TILE : step_form(f);
+    c.swaps = resident ? 0 : (long)n_samples * (by_sample ? 1 : P.steps_per_sample);
+    const long launches = 3L + c.swaps;
+    c.graph = f->use_graphs && launches >= 24 && !capturing;
+    return c;
+}
+
 // One leapfrog step old -> new over the plan's own planes, with the kernel form that suits the row
-// width (see the kernels above).
+// width (step_form).
 void launch_step(const gab_fdtd_plan* f, hipStream_t q, const gab::Fields& cur, const gab::Fields& nxt,
                  const float* add_next, float* strip_out) {
     const gab_fdtd_params& P = f->P;
@@ -1160,22 +1210,18 @@ void launch_step(const gab_fdtd_plan* f, hipStream_t q, const gab::Fields& cur, 
     gab::Grid g{P.nx, P.ny, P.nz, P.nx + 4, f->z_begin};
 #ifdef GAB_ABLATE
     static const bool hoist = getenv("GAB_FDTD_HOIST") ? atoi(getenv("GAB_FDTD_HOIST")) != 0 : kFdtdHoist;
-    static const int tile_env = getenv("GAB_FDTD_TILE_THREADS") ? atoi(getenv("GAB_FDTD_TILE_THREADS")) : 0;
 #else
     constexpr bool hoist = kFdtdHoist;
-    constexpr int tile_env = 0;
 #endif
     const size_t sxy = (size_t)P.nx * P.ny;
     const size_t src = P.source_z * sxy + (size_t)P.source_y * P.nx + P.source_x;
     const size_t rcv = P.receiver_z * sxy + (size_t)P.receiver_y * P.nx + P.receiver_x;
     const float damp = 1.0f - P.absorption_coeff;
-    const bool vec4 = (P.nx % 4) == 0;
-    const int tx = vec4 ? P.nx / 4 : P.nx;                    // threads along x
+    const int form = step_form(f);
+    const int tx = form == GAB_FDTD_KERNEL_STEP_SCALAR ? P.nx : P.nx / 4;     // threads along x
     const int bx = tx >= 64 ? 64 : (tx >= 32 ? 32 : 16);
     dim3 block(bx, 256 / bx, 1);
     dim3 grid((tx + bx - 1) / bx, (P.ny + block.y - 1) / block.y, nzl);
-    if (vec4 && f->lds_tiles && tx > 16 && tx <= 64) {
-        // whole x extent in one workgroup: LX x ROWS threads, (ROWS + 2) pressure rows in LDS
 #define GAB_FDTD_LDS_LAUNCH(LX, ROWS)                                                                 \
     do {                                                                                              \
         if (hoist)                                                                                    \
@@ -1185,24 +1231,21 @@ void launch_step(const gab_fdtd_plan* f, hipStream_t q, const gab::Fields& cur, 
             gab::fdtd_step_lds_kernel<LX, ROWS, false><<<dim3(1, (P.ny + ROWS - 1) / ROWS, nzl), dim3(LX, ROWS, 1), 0, q>>>( \
                 cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, damp, src, rcv, add_next, strip_out); \
     } while (0)
-        // 512-thread tiles (half as many halo rows) once they still make >= 4 workgroups
-        // per CU; 256-thread tiles below that (measured: 13.6 vs 14.3 us/step at 128^3,
-        // 47.5 vs 49.6 at 200^3, but 9.5 vs 8.8 at 96^3)
-        const int lx = tx <= 32 ? 32 : 64;
-        bool big = (long)((P.ny + 512 / lx - 1) / (512 / lx)) * nzl >= 1024;
-        if (tile_env) big = tile_env == 512;
-        if (lx == 32 && big) GAB_FDTD_LDS_LAUNCH(32, 16);
-        else if (lx == 32) GAB_FDTD_LDS_LAUNCH(32, 8);
-        else if (big) GAB_FDTD_LDS_LAUNCH(64, 8);
-        else GAB_FDTD_LDS_LAUNCH(64, 4);
-#undef GAB_FDTD_LDS_LAUNCH
-    } else if (vec4) {
-        gab::fdtd_step_vec4_kernel<<<grid, block, 0, q>>>(cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, damp,
-                                                         src, rcv, add_next, strip_out);
-    } else {
-        gab::fdtd_step_kernel<<<grid, block, 0, q>>>(cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, damp, src,
-                                                    rcv, add_next, strip_out);
+    switch (form) {
+        case GAB_FDTD_KERNEL_LDS_32X16: GAB_FDTD_LDS_LAUNCH(32, 16); break;
+        case GAB_FDTD_KERNEL_LDS_32X8: GAB_FDTD_LDS_LAUNCH(32, 8); break;
+        case GAB_FDTD_KERNEL_LDS_64X8: GAB_FDTD_LDS_LAUNCH(64, 8); break;
+        case GAB_FDTD_KERNEL_LDS_64X4: GAB_FDTD_LDS_LAUNCH(64, 4); break;
+        case GAB_FDTD_KERNEL_STEP_VEC4:
+            gab::fdtd_step_vec4_kernel<<<grid, block, 0, q>>>(cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, damp,
+                                                             src, rcv, add_next, strip_out);
+            break;
+        default:
+            gab::fdtd_step_kernel<<<grid, block, 0, q>>>(cur, nxt, g, P.dt_over_rho_dx, P.rho_c2_dt_over_dx, damp, src,
+                                                        rcv, add_next, strip_out);
+            break;
     }
+#undef GAB_FDTD_LDS_LAUNCH
 }
 
 void ensure_strips(gab_fdtd_plan* f, int bufsize, hipStream_t s) {
@@ -1309,9 +1352,21 @@ int gab_fdtd_status(gab_fdtd_plan* f, gab_stream_t stream) {
 
 int gab_fdtd_resident(const gab_fdtd_plan* f, int* resident, int* workgroups) {
     if (!f) return gab::bad_arg("gab_fdtd_resident: null plan");
-    const bool r = f->resident && !f->form_step && f->res_rpt > 0 && !f->pos_tracks;
+    const bool r = choose_form(f, 1, false).form == GAB_FDTD_KERNEL_RESIDENT;
     if (resident) *resident = r ? 1 : 0;
     if (workgroups) *workgroups = r ? f->rgeom.gy * f->rgeom.gz : 0;
+    return GAB_OK;
+}
+
+// What gab_fdtd_process would do with this call (choose_form, which it follows).  Host only: no device call.
+int gab_debug_fdtd_form(const gab_fdtd_plan* f, int tracks, int n_samples, int capturing, int* form, int* graph) {
+    if (!f) return gab::bad_arg("gab_debug_fdtd_form: null plan");
+    if (tracks <= 0 || n_samples <= 0) return gab::bad_arg("gab_debug_fdtd_form: tracks and n_samples must be > 0");
+    if (f->pos_tracks && f->pos_tracks != tracks)
+        return gab::bad_arg("gab_debug_fdtd_form: the plan has track positions for a different track count");
+    const FdtdChoice c = choose_form(f, n_samples, capturing != 0);
+    if (form) *form = c.form;
+    if (graph) *graph = c.graph ? 1 : 0;
     return GAB_OK;
 }
 
@@ -1326,15 +1381,22 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
         const gab_fdtd_params& P = f->P;
         if (f->z_begin != 0 || f->z_end != P.nz)
             return gab::bad_arg("gab_fdtd_process: a z-slab is stepped with gab_fdtd_step (halo exchange between steps)");
+        if (f->pos_tracks && f->pos_tracks != tracks)
+            return gab::bad_arg("gab_fdtd_process: the plan has track positions for a different track count");
         hipStream_t s = gab::as_stream(stream);
-        ensure_strips(f, bufsize, s);
-        const size_t sxy = (size_t)P.nx * P.ny;
-        const size_t src = P.source_z * sxy + (size_t)P.source_y * P.nx + P.source_x;
-        const int last = first_sample + n_samples;
-
-        // rooms up to 56 cells wide (where one step is shorter than a kernel boundary) take one
-        // launch per SAMPLE: three steps inside a tile (fdtd_sample_tile_kernel).  Measured per step:
-        // 20^3 1.98 vs 3.8 us, 32^3 2.11 vs 3.7, 52^3 3.49 vs 4.2, 56^3 3.59; at 64^3 the one-step chain wins
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(s, &cap);
+        const bool capturing = cap != hipStreamCaptureStatusNone;
+        // Inside a caller's capture nothing runs: the launches are recorded with the pointers of the ping-pong pair as
+        // they stand, and every replay repeats exactly them.  Refused here, before any host state or the capture is
+        // touched ("Captured calls" in the header):
+        if (capturing && f->strip_cap < bufsize)
+            return gab::bad_arg("gab_fdtd_process: inside a stream capture the plan's strips cannot grow (that synchronises the "
+                                "stream): make one plain call with this bufsize before the capture");
+        if (capturing && (choose_form(f, n_samples, true).swaps & 1))
+            return gab::bad_arg("gab_fdtd_process: a captured call must swap the ping-pong fields an even number of times, so that "
+                                "every replay starts where the last one ended: n_samples x steps_per_sample must be even "
+                                "(n_samples alone for rooms up to 56^3 at three steps per sample)");
         // a previous resident launch that gave up waiting for a neighbour workgroup left its word here
         if (const unsigned at = take_resident_timeout(f)) {
             gab::set_last_error("gab_fdtd_process: the LDS-resident kernel of the PREVIOUS call timed out at step " +
@@ -1342,16 +1404,16 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
                                 "work?); the plan's fields are undefined, reset it");
             return GAB_ERR_RUNTIME;
         }
-        // (not inside a caller's stream capture: the exchange tags are a launch argument that a replay would freeze)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &cap);
-        bool resident = f->resident && !f->form_step && f->res_rpt > 0 && !f->pos_tracks && cap == hipStreamCaptureStatusNone;
-        if (resident && !f->res) resident = prepare_resident(f, s);     // false: this device cannot hold the grid at once
-        const bool by_sample = f->sample_tiles && !f->pos_tracks && P.steps_per_sample == 3 && f->z_begin == 0 &&
-                               f->z_end == P.nz && P.nx <= 56 && P.ny <= 56 && P.nz <= 56;
+        ensure_strips(f, bufsize, s);
+        const size_t sxy = (size_t)P.nx * P.ny;
+        const size_t src = P.source_z * sxy + (size_t)P.source_y * P.nx + P.source_x;
+        const int last = first_sample + n_samples;
+        FdtdChoice choice = choose_form(f, n_samples, capturing);
+        // (a device that cannot hold the grid at once: prepare_resident takes the plan off the resident form for good)
+        if (choice.form == GAB_FDTD_KERNEL_RESIDENT && !f->res && !prepare_resident(f, s)) choice = choose_form(f, n_samples, capturing);
+        const bool resident = choice.form == GAB_FDTD_KERNEL_RESIDENT;
+        const bool by_sample = choice.form == GAB_FDTD_KERNEL_SAMPLE_TILE;
         // enqueue the whole chain on `q`, walking local copies of the ping-pong pair
-        if (f->pos_tracks && f->pos_tracks != tracks)
-            return gab::bad_arg("gab_fdtd_process: the plan has track positions for a different track count");
         auto enqueue = [&](hipStream_t q, gab::Fields cur, gab::Fields nxt) {
             if (f->pos_tracks) {
                 auto io = [&](float* p, int extract, int inject) {
@@ -1423,10 +1485,9 @@ int gab_fdtd_process(gab_fdtd_plan* f, const float* d_in, float* d_out, int trac
             gab::fdtd_broadcast_kernel<<<bgrid, 128, 0, q>>>(f->strip.get(), d_out, tracks, bufsize, first_sample,
                                                             n_samples);
         };
-        const long swaps = resident ? 0 : (long)n_samples * (by_sample ? 1 : P.steps_per_sample);
-        const long launches = 3L + swaps;
+        const long swaps = choice.swaps;
         bool replayed = false;
-        if (f->use_graphs && launches >= 24 && cap == hipStreamCaptureStatusNone) {
+        if (choice.graph) {
             const FdtdGraphKey key{d_in, d_out, tracks, bufsize, first_sample, n_samples, f->cur.p};
             hipGraphExec_t exec = nullptr;
             for (size_t i = 0; i < f->graphs.size(); ++i)

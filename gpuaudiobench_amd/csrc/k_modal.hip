@@ -197,6 +197,7 @@ __global__ __launch_bounds__(64 * kMrWaves) void modal_bank_reduce_kernel(const 
 
 struct ModalLaunch {
     int J, threads, grid;      // modes per lane, workgroup size, workgroups
+    bool fixed_tracks;         // the instantiation with the track count at compile time (32), else at run time
 };
 
 // Enough workgroups to cover the chip (one per CU: two waves per SIMD already saturate packed fp32) before a lane takes
@@ -210,7 +211,7 @@ ModalLaunch modal_launch(int n_modes, int tracks) {
     int J = 1;
     while (J < Jmax && (rows + rows_per_wg1 * J - 1) / (rows_per_wg1 * J) > 256) J *= 2;
     const long grid = (rows + rows_per_wg1 * J - 1) / (rows_per_wg1 * J);
-    return {J, kMbThreads, (int)(grid < 1 ? 1 : grid)};
+    return {J, kMbThreads, (int)(grid < 1 ? 1 : grid), tracks == 32};
 }
 
 }  // namespace
@@ -237,7 +238,7 @@ int gab_modal_bank(const float* d_params, float* d_out, int n_modes, int bufsize
         const gab::ModalLaunch L = gab::modal_launch(n_modes, out_tracks);
 #define GAB_MODAL_LAUNCH(JJ)                                                                          \
     do {                                                                                              \
-        if (out_tracks == 32)                                                                         \
+        if (L.fixed_tracks)                                                                           \
             gab::modal_bank_kernel<JJ, 32><<<L.grid, L.threads, 0, s>>>(d_params, d_workspace,         \
                                                                        n_modes, out_tracks, bufsize); \
         else                                                                                          \
@@ -248,6 +249,7 @@ int gab_modal_bank(const float* d_params, float* d_out, int n_modes, int bufsize
             case 1: GAB_MODAL_LAUNCH(1); break;
             case 2: GAB_MODAL_LAUNCH(2); break;
             case 8:                                  // 32 tracks only (modal_launch)
+                if (!L.fixed_tracks) return gab::bad_arg("gab_modal_bank: no eight-mode form for a run-time track count");
                 gab::modal_bank_kernel<8, 32><<<L.grid, L.threads, 0, s>>>(d_params, d_workspace, n_modes, out_tracks, bufsize);
                 break;
             default: GAB_MODAL_LAUNCH(4); break;
@@ -260,6 +262,17 @@ int gab_modal_bank(const float* d_params, float* d_out, int n_modes, int bufsize
                                                                                                L.grid, n_out);
         return gab::launch_status("modal_bank_reduce_kernel");
     });
+}
+
+// The launch gab_modal_bank makes for this shape (modal_launch, the one place that decides it): modes per lane, workgroups,
+// and whether the kernel has the track count at compile time.  Host only: no device call.
+int gab_debug_modal_launch(int n_modes, int out_tracks, int* J, int* grid, int* fixed_tracks) {
+    if (n_modes <= 0 || out_tracks <= 0 || out_tracks > 64) return gab::bad_arg("gab_debug_modal_launch: n_modes > 0, out_tracks in 1..64");
+    const gab::ModalLaunch L = gab::modal_launch(n_modes, out_tracks);
+    if (J) *J = L.J;
+    if (grid) *grid = L.grid;
+    if (fixed_tracks) *fixed_tracks = L.fixed_tracks ? 1 : 0;
+    return GAB_OK;
 }
 
 }  // extern "C"

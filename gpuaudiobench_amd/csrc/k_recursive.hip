@@ -972,6 +972,33 @@ __global__ __launch_bounds__(256) void dwg_cells_lean_kernel(const WG* __restric
     }
 }
 
+// Which kernels gab_dwg launches for a shape: decided here and nowhere else (gab_debug_dwg_route reports it).
+//   cells  the kernel that advances the delay lines     mix  how the ordered per-sample sum finds its contributions
+struct DwgRoute {
+    int cells, mix;
+    int n_mix;          // waveguides that reach the mix
+    bool sparse;        // per-sample hit lists instead of the scan over every waveguide
+};
+DwgRoute dwg_route(int n_waveguides, int bufsize, int max_len, int out_tracks, int variant) {
+    DwgRoute r;
+    r.n_mix = n_waveguides < out_tracks ? n_waveguides : out_tracks;
+    // the sparse mix pays from about two thousand waveguides on (8 192: 30.2 -> 10.7 us for the mix; at 128 its
+    // extra launch costs more than the scan it replaces: 3.3 -> 8.8 us)
+    r.sparse = r.n_mix >= 2048;
+    r.mix = r.sparse ? GAB_DWG_MIX_GATHER_SPARSE : GAB_DWG_MIX_SCAN;
+    if (variant == GAB_DWG_NAIVE) {
+        r.cells = GAB_DWG_CELLS_NAIVE;
+    } else if (r.sparse && bufsize <= kDwgMaxB) {                // large banks: the cells kernel appends to the hit lists itself
+        // delay lines of 4 GiB and more per array: the staged append form (a buffer resource's range is 32 bits)
+        const unsigned long long line_bytes = 4ull * (unsigned long long)n_waveguides * (unsigned long long)max_len;
+        r.cells = line_bytes >= 0xffffff00ull ? GAB_DWG_CELLS_APPEND_STAGED : GAB_DWG_CELLS_LEAN;
+        r.mix = GAB_DWG_MIX_APPENDED_SPARSE;
+    } else {
+        r.cells = n_waveguides >= 1024 ? GAB_DWG_CELLS_MULTI : GAB_DWG_CELLS_ONE_LINE;    // U lines per workgroup (see the kernel)
+    }
+    return r;
+}
+
 }  // namespace
 }  // namespace gab
 
@@ -1070,19 +1097,18 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd, const f
         const gab::WG* wgs = reinterpret_cast<const gab::WG*>(d_wg);
         float* ws = static_cast<float*>(d_workspace);
         int2* hits = reinterpret_cast<int2*>(ws + (((size_t)n_waveguides * bufsize + 1) & ~(size_t)1));
-        // the sparse mix pays from about two thousand waveguides on (8 192: 30.2 -> 10.7 us for the mix; at 128 its
-        // extra launch costs more than the scan it replaces: 3.3 -> 8.8 us)
-        const int n_mix = n_waveguides < out_tracks ? n_waveguides : out_tracks;
-        const bool sparse = n_mix >= 2048;
+        const gab::DwgRoute route = gab::dwg_route(n_waveguides, bufsize, max_len, out_tracks, variant);
+        const int n_mix = route.n_mix;
+        const bool sparse = route.sparse;
         int* mix_count = sparse ? reinterpret_cast<int*>(hits + n_waveguides) : nullptr;
         int2* mix_list = reinterpret_cast<int2*>(reinterpret_cast<int*>(hits + n_waveguides) + (((size_t)bufsize + 1) & ~(size_t)1));
-        if (variant == GAB_DWG_NAIVE) {
+        if (route.cells == GAB_DWG_CELLS_NAIVE) {
             gab::dwg_naive_kernel<<<(n_waveguides + 15) / 16, 16, 0, s>>>(wgs, d_fwd, d_bwd, d_in, ws, hits,
                                                                          n_waveguides, bufsize, max_len, mix_count);
         } else {
             int cells = max_len < bufsize ? max_len : bufsize;   // a buffer visits min(L, B) cells of a line
             constexpr int U = 8;
-            if (sparse && bufsize <= gab::kDwgMaxB) {            // large banks: the cells kernel appends to the hit lists itself
+            if (route.mix == GAB_DWG_MIX_APPENDED_SPARSE) {     // large banks: the cells kernel appends to the hit lists itself
                 // The per-sample counters live in a pool of kDwgSlots zeroed arrays in the code object; a call takes the next
                 // slot and its mix kernel zeroes it again.  What keeps a slot from being taken twice at once (more than
                 // kDwgSlots calls in flight over several streams) is an event per slot: a call on ANOTHER stream goes behind
@@ -1094,7 +1120,7 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd, const f
                 // 0: round 5's (8 lines per workgroup, staged input)   1, 2: no staging, 8 / 16 lines (r06: no faster — it was
                 // never the staging)   3, 4, 5, 6, 7: the lean kernel, 8 / 16 / 4 / 2 / 1 lines per workgroup: 15.5 / 19.6 / 14.0 /
                 // 14.6 / 16.9 us against 19.6 (profiles/r06_dwg.md); delay lines of 4 GiB and more per array: form 0
-                int form = 5;
+                int form = route.cells == GAB_DWG_CELLS_LEAN ? 5 : 0;
 #ifdef GAB_ABLATE
                 if (getenv("GAB_DWG_FORM")) form = atoi(getenv("GAB_DWG_FORM"));     // diagnostic builds: A/B on one box
 #endif
@@ -1136,7 +1162,7 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd, const f
                 GAB_HIP_CHECK(hipEventRecord(sl.busy, s));
                 return rc;
             }
-            if (n_waveguides >= 1024) {                          // U lines per workgroup (see the kernel)
+            if (route.cells == GAB_DWG_CELLS_MULTI) {            // U lines per workgroup (see the kernel)
                 dim3 grid((cells + 255) / 256, (n_waveguides + U - 1) / U);
                 gab::dwg_cells_multi_kernel<U><<<grid, 256, 0, s>>>(wgs, d_fwd, d_bwd, d_in, ws, hits, n_waveguides,
                                                                     bufsize, max_len, mix_count);
@@ -1157,6 +1183,16 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd, const f
                                                               out_tracks, mix_count, mix_list, false);
         return gab::launch_status("dwg_mix_kernel");
     });
+}
+
+// The kernels gab_dwg launches for this shape (dwg_route, which gab_dwg follows).  Host only: no device call.
+int gab_debug_dwg_route(int n_waveguides, int bufsize, int max_len, int out_tracks, int variant, int* cells, int* mix) {
+    if (n_waveguides <= 0 || bufsize <= 0 || max_len <= 0) return gab::bad_arg("gab_debug_dwg_route: sizes must be > 0");
+    if (variant != GAB_DWG_NAIVE && variant != GAB_DWG_ACCEL) return gab::bad_arg("gab_debug_dwg_route: unknown variant");
+    const gab::DwgRoute r = gab::dwg_route(n_waveguides, bufsize, max_len, out_tracks, variant);
+    if (cells) *cells = r.cells;
+    if (mix) *mix = r.mix;
+    return GAB_OK;
 }
 
 }  // extern "C"

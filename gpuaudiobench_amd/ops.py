@@ -324,6 +324,29 @@ def modal_bank(params, n_modes, bufsize, out_tracks=32, out=None, workspace=None
     return out
 
 
+MODAL_FORMS = tuple((J, fixed) for fixed in (1, 0) for J in (1, 2, 4, 8) if fixed or J < 8)
+
+
+def modal_launch(n_modes, out_tracks=32):
+    """(modes per lane, workgroups, 1 if the track count is the kernel's compile-time 32) of gab_modal_bank's launch
+    for this shape: gab_debug_modal_launch."""
+    J, grid, fixed = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib.gab_debug_modal_launch(n_modes, out_tracks, C.byref(J), C.byref(grid), C.byref(fixed)))
+    return J.value, grid.value, fixed.value
+
+
+DWG_CELLS = ("naive", "one_line", "multi", "lean", "append_staged")
+DWG_MIX = ("scan", "gather_sparse", "appended_sparse")
+
+
+def dwg_route(n_wg, bufsize, max_len=2000, out_tracks=None, variant=DWG_ACCEL):
+    """(cells kernel, mix form) gab_dwg takes for this shape, by name (DWG_CELLS, DWG_MIX): gab_debug_dwg_route."""
+    cells, mix = C.c_int(0), C.c_int(0)
+    check(lib.gab_debug_dwg_route(n_wg, bufsize, max_len, n_wg if out_tracks is None else out_tracks, variant,
+                                  C.byref(cells), C.byref(mix)))
+    return DWG_CELLS[cells.value], DWG_MIX[mix.value]
+
+
 def dwg(wg_bytes, fwd, bwd, x, bufsize, max_len=2000, out_tracks=None, variant=DWG_ACCEL):
     """wg_bytes: uint8 device tensor holding n_wg WaveguideState records (32 B each)."""
     n_wg = wg_bytes.numel() // C.sizeof(WaveguideState)
@@ -1373,6 +1396,9 @@ def fdtd_default_params(nx, ny=None, nz=None):
     return P
 
 
+FDTD_FORMS = ("resident", "sample_tile", "lds_32x8", "lds_32x16", "lds_64x4", "lds_64x8", "step_vec4", "step_scalar")
+
+
 class FdtdPlan(_Handle):
     _destroy = "gab_fdtd_destroy"
 
@@ -1392,6 +1418,13 @@ class FdtdPlan(_Handle):
     def set_form(self, form):
         """"auto" (resident in LDS where the room fits) or "step" (one launch per step): gab_fdtd_set_form."""
         check(lib.gab_fdtd_set_form(self._h, {"auto": 0, "step": 1}[form]))
+
+    def form(self, tracks, n_samples, capturing=False):
+        """(kernel form by name (FDTD_FORMS), True if through the plan's graph cache) of a process() call of n_samples:
+        gab_debug_fdtd_form."""
+        form, graph = C.c_int(0), C.c_int(0)
+        check(lib.gab_debug_fdtd_form(self._h, tracks, n_samples, 1 if capturing else 0, C.byref(form), C.byref(graph)))
+        return FDTD_FORMS[form.value], bool(graph.value)
 
     def status(self):
         """Synchronises the current stream; raises GabError if the last process() call's resident launch

@@ -184,6 +184,10 @@ int gab_modal(const float* d_params, float* d_out, int n_modes, int bufsize,
 size_t gab_modal_bank_workspace_bytes(int n_modes, int out_tracks, int bufsize);
 int gab_modal_bank(const float* d_params, float* d_out, int n_modes, int bufsize, int out_tracks,
                    float* d_workspace, gab_stream_t stream);
+/* The launch gab_modal_bank makes for a shape: *J modes per lane (1, 2, 4; 8 with 32 tracks only), *grid workgroups,
+ * *fixed_tracks = 1 for the instantiation with the track count at compile time (out_tracks == 32).  The same host
+ * function decides for gab_modal_bank; no device call (tests/test_launch_forms_gpu.py).                         */
+int gab_debug_modal_launch(int n_modes, int out_tracks, int* J, int* grid, int* fixed_tracks);
 
 /* WaveguideState (cuda/bench_dwg.cuh:19-28), 32 bytes.                       */
 typedef struct {
@@ -208,6 +212,17 @@ int gab_dwg(const gab_waveguide_state* d_wg, float* d_fwd, float* d_bwd,
             const float* d_in, float* d_out, void* d_workspace, int n_waveguides,
             int bufsize, int max_len, int out_tracks, int variant,
             gab_stream_t stream);
+/* The kernels gab_dwg launches for a shape: *cells advances the delay lines, *mix is how the ordered per-sample sum finds
+ * its contributions.  The same host function decides for gab_dwg; no device call (tests/test_launch_forms_gpu.py).  */
+#define GAB_DWG_CELLS_NAIVE         0   /* dwg_naive_kernel (GAB_DWG_NAIVE)                                        */
+#define GAB_DWG_CELLS_ONE_LINE      1   /* dwg_cells_kernel: one line per workgroup, fewer than 1024 lines         */
+#define GAB_DWG_CELLS_MULTI         2   /* dwg_cells_multi_kernel<8>: 1024 lines and more                          */
+#define GAB_DWG_CELLS_LEAN          3   /* dwg_cells_lean_kernel<4>: 2048 mixed lines and more, bufsize <= 2048    */
+#define GAB_DWG_CELLS_APPEND_STAGED 4   /* dwg_cells_append_kernel<8, true>: the same with 4 GiB of lines and more */
+#define GAB_DWG_MIX_SCAN            0   /* dwg_mix_kernel scanning every waveguide per sample                      */
+#define GAB_DWG_MIX_GATHER_SPARSE   1   /* dwg_gather_kernel, then dwg_mix_kernel on hit lists in the workspace    */
+#define GAB_DWG_MIX_APPENDED_SPARSE 2   /* the cells kernel appended the lists itself (counters in a library slot) */
+int gab_debug_dwg_route(int n_waveguides, int bufsize, int max_len, int out_tracks, int variant, int* cells, int* mix);
 
 /* cufftExecR2C, N=1024, batch = tracks (cuda/bench_fft.cu:63,105):
  * d_in tracks x 1024 real, d_out tracks x 513 interleaved complex.
@@ -478,6 +493,19 @@ int gab_fdtd_resident(const gab_fdtd_plan* plan, int* resident, int* workgroups)
 #define GAB_FDTD_FORM_AUTO 0
 #define GAB_FDTD_FORM_STEP 1
 int gab_fdtd_set_form(gab_fdtd_plan* plan, int form);
+/* The kernel a gab_fdtd_process call of n_samples (with `capturing` != 0: made inside a stream capture) would launch,
+ * and *graph = 1 if its launches would go through the plan's own graph cache (24 launches and more, outside a capture).
+ * The same host function decides for gab_fdtd_process; no device call.  tests/test_launch_forms_gpu.py holds a case
+ * per form to the oracle and fails when a form has none.                                                      */
+#define GAB_FDTD_KERNEL_RESIDENT    0   /* fdtd_resident_kernel: the buffer in one launch                         */
+#define GAB_FDTD_KERNEL_SAMPLE_TILE 1   /* fdtd_sample_tile_kernel: one launch per sample, rooms up to 56^3 at 3 steps */
+#define GAB_FDTD_KERNEL_LDS_32X8    2   /* fdtd_step_lds_kernel<32, 8>:  64 < nx <= 128, nx % 4 == 0               */
+#define GAB_FDTD_KERNEL_LDS_32X16   3   /*                     <32, 16>: the same, ceil(ny / 16) * nz >= 1024      */
+#define GAB_FDTD_KERNEL_LDS_64X4    4   /*                     <64, 4>:  128 < nx <= 256, nx % 4 == 0              */
+#define GAB_FDTD_KERNEL_LDS_64X8    5   /*                     <64, 8>:  the same, ceil(ny / 8) * nz >= 1024       */
+#define GAB_FDTD_KERNEL_STEP_VEC4   6   /* fdtd_step_vec4_kernel: every other nx % 4 == 0                         */
+#define GAB_FDTD_KERNEL_STEP_SCALAR 7   /* fdtd_step_kernel: nx % 4 != 0                                           */
+int gab_debug_fdtd_form(const gab_fdtd_plan* plan, int tracks, int n_samples, int capturing, int* form, int* graph);
 /* Errors at the call that failed (the reference throws from the failing iteration: synchronizeAndCheck,
  * cuda/bench_base.cu:177-179).  Synchronises `stream` and returns GAB_ERR_RUNTIME if the resident launch of the
  * last gab_fdtd_process on it gave up waiting for a neighbour workgroup.  That call's output is NaN in every
@@ -550,6 +578,16 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *   spectrum's phase    launch arguments, (p mod H) and the frame count at the capture; the history behind the frames
  *                       is the device's and moves with every replay.  Where H divides B the phase is 0 and the count
  *                       B / H on every call, and the replays are the stream's next buffers (tests/test_spectrum_gpu.py).
+ *   fdtd's ping-pong    gab_fdtd_process can be captured too (it then takes the step kernels, never the resident one).  The
+ *                       pointers of the two field sets are launch arguments: a replay starts in the set that was
+ *                       current at the capture.  So a captured call must swap the sets an EVEN number of times
+ *                       (n_samples x steps_per_sample even; n_samples even for rooms up to 56^3 at three steps per
+ *                       sample, which take one launch per sample): then every replay ends where the next one starts and
+ *                       the replays are successive calls on the fields.  A captured call with an odd count is refused
+ *                       with GAB_ERR_INVALID_ARG, and so is one that would have to grow the plan's strips (the first
+ *                       call with a bufsize larger than any before: make it outside the capture); a refusal touches
+ *                       neither the plan nor the capture.  Plain calls between two replays must leave the same set
+ *                       current (an even number of swaps in all).  Held by tests/test_launch_forms_gpu.py.
  * set_* calls and reset synchronise or belong to the host and stay outside a capture.  Held by
  * tests/test_strip_gpu.py for the whole strip in one graph and for every plan alone. */
 

@@ -20,7 +20,8 @@ def test_header_declares_the_expected_surface():
     names = declared_functions()
     for must in ("gab_gain", "gab_conv_process", "gab_fdtd_process", "gab_bench_create",
                  "gab_fft_r2c_1024", "gab_rndmem", "gab_dwg", "gab_iir", "gab_modal",
-                 "gab_datatransfer", "gab_gainstats", "gab_noop", "gab_conv1d"):
+                 "gab_datatransfer", "gab_gainstats", "gab_noop", "gab_conv1d",
+                 "gab_debug_fdtd_form", "gab_debug_dwg_route", "gab_debug_modal_launch"):
         assert must in names
     assert len(names) >= 40
 
@@ -87,6 +88,11 @@ def test_product_library_has_no_work_skipping_switches():
     driver = os.path.join(ROOT, "gpuaudiobench_amd", "gpubench")
     if os.path.exists(driver):
         blob += open(driver, "rb").read()
+    # the three form queries of the header are product symbols: host functions that report what a launcher would do and
+    # make no device call.  Every other gab_debug_ entry stays a diagnostic build's.
+    for query in (b"gab_debug_fdtd_form", b"gab_debug_dwg_route", b"gab_debug_modal_launch"):
+        assert query in blob, query
+        blob = blob.replace(query, b"")
     for name in (b"GAB_CONV_SPLIT_DEBUG", b"GAB_CONV_STAMP_AT", b"GAB_CONV_RANGE_THREADS", b"GAB_CONV_ABLATE",
                  b"GAB_CONV_SCHEME", b"GAB_FDTD_GRAPH", b"GAB_FDTD_LDS", b"GAB_FDTD_TILE", b"GAB_FDTD_STAGGER",
                  b"g_split_stamps", b"gab_debug_"):

@@ -1195,7 +1195,7 @@ def test_modal(gab, orc):
 # relative to the output's peak, against BOTH the fp32 golden and its float64-accumulated twin.
 @pytest.mark.parametrize("n_modes,bufsize,tracks", [
     (65536, 512, 32),        # J = 1
-    (262144, 512, 32),       # J = 1, 512 workgroups
+    (262144, 512, 32),       # J = 2, 256 workgroups
     (1 << 20, 64, 32),       # the reference size (min(1024*tracks, 2^20)), short buffer
     (4096, 512, 32), (1000, 100, 32),     # ragged: rows and chunks both partial
     (5000, 37, 1), (5000, 48, 2), (5000, 512, 24), (3333, 33, 7), (2048, 16, 64),
@@ -1363,9 +1363,9 @@ def test_dwg_large_bank_cells_kernel_appends_to_the_hit_lists(gab, orc, n_wg, B,
 
 
 @pytest.mark.parametrize("n,T,B,samples", [(20, 4, 16, 16), (52, 128, 512, 24), (33, 3, 8, 8),
-                                          (128, 16, 8, 6),       # C4's grid, a few samples (LDS-halo kernel, 32 x 8)
-                                          (100, 3, 6, 6),        # 32 x 8 tiles with a partial last tile row
-                                          (148, 2, 4, 4)])       # 64 x 4 tiles
+                                          (128, 16, 8, 6),       # C4's grid, a few samples (the resident kernel; in step form 32 x 16 tiles)
+                                          (100, 3, 6, 6),        # resident too (in step form 32 x 8 tiles with a partial last tile row)
+                                          (148, 2, 4, 4)])       # past the resident kernel's 128: 64 x 8 tiles
 def test_fdtd_bit_exact(gab, orc, n, T, B, samples):
     import torch
     P = orc.fdtd_params(n)
