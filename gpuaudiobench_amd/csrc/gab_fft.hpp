@@ -496,34 +496,74 @@ struct BlockFFT {
 
 // A 1024-point transform held by ONE wave: 64 lanes x 16 values, lane j enters with
 // v[r] = x[j + 64 r] and leaves with v[r] = X[j + 64 r].  Passes: four radix-4
-// butterflies per lane (Ns = 1), radix-16 (Ns = 4), radix-16 (Ns = 64).  The two
-// exchanges go through a wave-private LDS image of Pad<16>::size(1024) entries and
-// need no workgroup barrier: a wave's LDS instructions execute in order.
+// butterflies per lane (Ns = 1), radix-16 (Ns = 4), radix-16 (Ns = 64).
+//
+// Exchange 1 (pass 0 -> pass 1) stays in registers.  Pass 0 leaves output k0 of butterfly
+// lane + 64 m in v[m + 4 k0]; as y[4 lane + 256 m + k0] it is wanted as v'[r'] = y[L' + 64 r'] by
+// L' = 4 (lane & 15) + k0 with r' = 4 m + (lane >> 4): k0 (register bits 3:2) and lane bits 5:4
+// change places, everything else is a renaming.  That 4 x 4 transpose is two stages of gfx950's
+// lane-half swaps (v_permlane32_swap: register bit 3 against lane bit 5; v_permlane16_swap:
+// register bit 2 against lane bit 4), 32 VALU instructions on the sixteen values in place.
+// Afterwards PHYSICAL lane p works as virtual lane L'(p) = 4 (p & 15) + (p >> 4) and v[m + 4 k] is
+// v'[4 m + k].  Pass 1 runs under that name — its twiddle base is W64^(L' & 3) = W64^(p >> 4), its
+// stores go to row L' >> 2 = p & 15, column (L' & 3) + 4 k of the second exchange — and the second
+// exchange's reader is the physical lane again, so the transform leaves v[r] = X[lane + 64 r].
+// The swaps need EXEC all ones: every caller runs whole waves (block sizes are multiples of 64
+// and the call sits in wave-uniform control flow; a lane that is masked off would hand its
+// partner whatever its registers hold).
+//
+// Exchange 2 (pass 1 -> pass 2) moves lane bits 3:0 and goes through a wave-private LDS image
+// (callers reserve Pad<16>::size(1024) entries; 16 rows at a stride of 65 are used): the
+// sixteen lanes of a store group write sixteen ROWS, which a stride of 65 entries (2 banks) keeps
+// on 32 different banks where Pad<16>'s 68 (8 banks) would put them four deep; a read group is 16
+// or 32 consecutive entries of one row.  No workgroup barrier: a wave's LDS instructions execute
+// in order.
 struct Wave1024Twiddles {
-    cf w1;         // W64^(j&3): its powers are re-formed in the pass (registers)
+    cf w1;         // W64^(L' & 3), L' the lane pass 1 runs as (load_w1): its powers are re-formed in the pass (registers)
     cf w2[15];     // W1024^(j i), i = 1..15
+#ifdef GAB_ABLATE
+    unsigned lds_x1;   // diagnostic builds: exchange 1 through LDS (the form before the swaps), wave-uniform
+#endif
 };
 // Two registers instead of sixteen: both passes re-form their powers from the base (the same
 // powers_of, so the same values) — for kernels whose waves carry other state across transforms.
 struct Wave1024TwiddlesLean {
-    cf w1;         // W64^(j&3)
+    cf w1;         // W64^(L' & 3)
     cf w2b;        // W1024^j
+#ifdef GAB_ABLATE
+    unsigned lds_x1;
+#endif
 };
 
-template <bool INV>
+// SWAP1 = false keeps exchange 1 in the image too (a store, a wave barrier and a load in Pad<16>'s layout, as both
+// exchanges were before the swaps): for a kernel whose period is set by ONE wave's dependent chain instead of by the
+// compute unit's LDS and issue cycles — 32 swaps take a wave about 340 clocks, longer than the LDS round trip they
+// replace (profiles/r24_wave_exchange.txt).  Same arithmetic, same bits.
+template <bool INV, bool SWAP1 = true>
 struct WaveFFT1024 {
     static constexpr int N = 1024;
     using P = Pad<16>;
     using Twiddles = Wave1024Twiddles;
 
+    // Pass 1's twiddle base of PHYSICAL lane `lane`: W64^(L' & 3) with L' & 3 = lane >> 4 (through LDS: L' = lane).
+    template <class TW>
+    __device__ static __forceinline__ void load_w1(TW& t, const cf* __restrict__ tw, int lane) {
+#ifdef GAB_ABLATE
+        // diagnostic builds: the entry behind the table can send every transform of the process through LDS (device_twiddles())
+        t.lds_x1 = SWAP1 ? (unsigned)__builtin_amdgcn_readfirstlane(tw[kTwiddleN].x != 0.0f ? 1 : 0) : 1u;
+        t.w1 = tw[(t.lds_x1 ? lane & 3 : lane >> 4) * (kTwiddleN / 64)];
+#else
+        t.w1 = tw[(SWAP1 ? lane >> 4 : lane & 3) * (kTwiddleN / 64)];
+#endif
+    }
     __device__ static __forceinline__ void load_twiddles(Twiddles& t, const cf* __restrict__ tw, int lane) {
-        t.w1 = tw[(lane & 3) * (kTwiddleN / 64)];
+        load_w1(t, tw, lane);
         powers_of<16>(tw[lane * (kTwiddleN / 1024)], t.w2);
     }
     // The same in two steps, for callers that want the two table reads at the head of their
     // request stream and the power expansion later: raw leaves W1024^lane in w2[0].
     __device__ static __forceinline__ void load_twiddles_raw(Twiddles& t, const cf* __restrict__ tw, int lane) {
-        t.w1 = tw[(lane & 3) * (kTwiddleN / 64)];
+        load_w1(t, tw, lane);
         t.w2[0] = tw[lane * (kTwiddleN / 1024)];
     }
     __device__ static __forceinline__ void expand_twiddles(Twiddles& t) {
@@ -532,7 +572,7 @@ struct WaveFFT1024 {
     }
     using Lean = Wave1024TwiddlesLean;
     __device__ static __forceinline__ void load_twiddles(Lean& t, const cf* __restrict__ tw, int lane) {
-        t.w1 = tw[(lane & 3) * (kTwiddleN / 64)];
+        load_w1(t, tw, lane);
         t.w2b = tw[lane * (kTwiddleN / 1024)];
     }
     __device__ static __forceinline__ void last_pass_twiddles(const Twiddles& t, cf (&w)[15]) {
@@ -547,30 +587,95 @@ struct WaveFFT1024 {
 
     struct NoHook { __device__ __forceinline__ void operator()(int) const {} };
 
-    // `hook(i)` runs at the transform's two exchange points (i = 0, 1), after the wave's LDS writes and
-    // before its reads: a caller whose workgroup shares ONE hardware barrier between roles arrives at
-    // that barrier there, so that a transform spans three barrier intervals instead of one.
+    // a <- {a's low lanes, b's low lanes}, b <- {a's high lanes, b's high lanes}: over the wave's 32-lane halves
+    // (HALF = 32), or over the 16-lane rows of each half (HALF = 16).  One instruction per dword; EXEC all ones.
+    template <int HALF>
+    __device__ static __forceinline__ void swap_lane_halves(cf& a, cf& b) {
+        static_assert(HALF == 32 || HALF == 16, "lane-half swaps exist for 32 and 16 lanes");
+        if constexpr (HALF == 32) {
+            const auto x = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
+            const auto y = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
+            a = mk(__uint_as_float(x[0]), __uint_as_float(y[0]));
+            b = mk(__uint_as_float(x[1]), __uint_as_float(y[1]));
+        } else {
+            const auto x = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
+            const auto y = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
+            a = mk(__uint_as_float(x[0]), __uint_as_float(y[0]));
+            b = mk(__uint_as_float(x[1]), __uint_as_float(y[1]));
+        }
+    }
+
+    // `hook(i)` runs at the transform's two exchange points (i = 0, 1): hook(0) between pass 0 and pass 1 (with the swaps
+    // the image is not touched before it: the transform's first LDS write is the second exchange's; with SWAP1 = false
+    // it sits between the first exchange's writes and reads), hook(1) after the wave's LDS writes of the second exchange
+    // and before its reads.  A caller whose workgroup shares ONE hardware barrier between
+    // roles arrives at that barrier there, so that a transform spans three barrier intervals instead of one.
     template <class Hook = NoHook, class TW = Twiddles>
     __device__ static __forceinline__ void run(cf (&v)[16], cf* __restrict__ img, const TW& t,
                                                int lane_in, Hook hook = Hook()) {
+#ifdef GAB_ABLATE
+        if (SWAP1 && t.lds_x1) {                         // wave-uniform; in the product library the form is the caller's SWAP1 alone
+            run_form<true>(v, img, t, lane_in, hook);
+            return;
+        }
+#endif
+        run_form<!SWAP1>(v, img, t, lane_in, hook);
+    }
+
+    // LDSX1: exchange 1 through the image and both exchanges in Pad<16>'s layout, as the transform was before the
+    // swaps — the same arithmetic, lane for lane renamed.
+    template <bool LDSX1, class Hook, class TW>
+    __device__ static __forceinline__ void run_form(cf (&v)[16], cf* __restrict__ img, const TW& t,
+                                                    int lane_in, Hook hook) {
         unsigned lane = (unsigned)lane_in;
         asm volatile("" : "+v"(lane));
         // pass 0: butterflies b = lane + 64 m on v[m + 4 i]; y[4 b + i]
 #pragma unroll
         for (int m = 0; m < 4; ++m) bfly4<INV>(v[m], v[m + 4], v[m + 8], v[m + 12]);
-        {
-            // Pad(4 lane + 256 m + i) = 4 lane + (lane >> 2) + 272 m + i
-            const unsigned wb = 4u * lane + (lane >> 2);
+        unsigned wb2, rb2;                               // exchange 2: this lane's store and load base
+        constexpr unsigned RS2 = LDSX1 ? 68u : 65u;      // and the stride of its rows
+        static_assert(15 * 65 + 63 < P::size(N), "the second exchange stays inside the image");
+        if constexpr (LDSX1) {
+            {
+                // Pad(4 lane + 256 m + i) = 4 lane + (lane >> 2) + 272 m + i
+                const unsigned wb = 4u * lane + (lane >> 2);
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) img[wb + 272 * m + i] = v[m + 4 * i];
+            }
+            __builtin_amdgcn_wave_barrier();
+            hook(0);
+            rb2 = lane + (lane >> 4);                    // Pad(lane + 64 r) = rb2 + 68 r
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = img[rb2 + 68 * r];
+            // y[(lane/4) 64 + (lane&3) + 4 k]; Pad = (lane>>2) 68 + (lane&3) + 4 k + (k >> 2)
+            wb2 = (lane >> 2) * 68u + (lane & 3u);
+        } else {
+            // exchange 1: v[m + 4 k0] — k0 bit 1 against lane bit 5, k0 bit 0 against lane bit 4
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                swap_lane_halves<32>(v[m], v[m + 8]);
+                swap_lane_halves<32>(v[m + 4], v[m + 12]);
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                swap_lane_halves<16>(v[m], v[m + 4]);
+                swap_lane_halves<16>(v[m + 8], v[m + 12]);
+            }
+            hook(0);
+            // this lane is now L' = 4 (lane & 15) + (lane >> 4) and v[m + 4 k] is v'[4 m + k]
+            cf u[16];
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) img[wb + 272 * m + i] = v[m + 4 * i];
-        }
-        __builtin_amdgcn_wave_barrier();
-        hook(0);
-        const unsigned rb = lane + (lane >> 4);         // Pad(lane + 64 r) = rb + 68 r
+                for (int k = 0; k < 4; ++k) u[4 * m + k] = v[m + 4 * k];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = img[rb + 68 * r];
+            for (int r = 0; r < 16; ++r) v[r] = u[r];
+            // y[(L'/4) 64 + (L'&3) + 4 k] = row lane & 15, column (lane >> 4) + 4 k; read back as row r, column lane
+            wb2 = (lane & 15u) * 65u + (lane >> 4);
+            rb2 = lane;
+        }
         {
             cf b = t.w1, w1[15];
             asm volatile("" : "+v"(b.x), "+v"(b.y));
@@ -580,16 +685,12 @@ struct WaveFFT1024 {
         }
         Butterfly<16, INV>::run(v);
         __builtin_amdgcn_wave_barrier();
-        {
-            // y[(lane/4) 64 + (lane&3) + 4 k]; Pad = (lane>>2) 68 + (lane&3) + 4 k + (k >> 2)
-            const unsigned wb = (lane >> 2) * 68u + (lane & 3u);
 #pragma unroll
-            for (int k = 0; k < 16; ++k) img[wb + 4 * k + (k >> 2)] = v[Butterfly<16, INV>::out_slot(k)];
-        }
+        for (int k = 0; k < 16; ++k) img[wb2 + 4 * k + (LDSX1 ? k >> 2 : 0)] = v[Butterfly<16, INV>::out_slot(k)];
         __builtin_amdgcn_wave_barrier();
         hook(1);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = img[rb + 68 * r];
+        for (int r = 0; r < 16; ++r) v[r] = img[rb2 + RS2 * r];
         {
             cf w2[15];
             last_pass_twiddles(t, w2);

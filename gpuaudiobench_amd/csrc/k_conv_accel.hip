@@ -70,11 +70,19 @@ const cf* device_twiddles() {
     std::lock_guard<std::mutex> lock(mu);
     if (dev >= (int)per_device.size()) per_device.resize(dev + 1, nullptr);
     if (!per_device[dev]) {
-        std::vector<float> host(2 * kTwiddleN);
+        size_t n = kTwiddleN;
+        std::vector<float> host(2 * (n + 1));
         build_twiddles(host.data());
+#ifdef GAB_ABLATE
+        // diagnostic builds: one entry behind the table, read by WaveFFT1024's load_w1 — GAB_WAVE_XCHG_LDS=1 runs the wave-held
+        // transform's first exchange through LDS (the A/B partner of the lane-half swaps) in every kernel of the process
+        host[2 * n] = getenv("GAB_WAVE_XCHG_LDS") && atoi(getenv("GAB_WAVE_XCHG_LDS")) ? 1.0f : 0.0f;
+        host[2 * n + 1] = 0.0f;
+        n += 1;
+#endif
         cf* d = nullptr;
-        GAB_HIP_CHECK(hipMalloc(&d, sizeof(cf) * kTwiddleN));
-        GAB_HIP_CHECK(hipMemcpy(d, host.data(), sizeof(cf) * kTwiddleN, hipMemcpyHostToDevice));
+        GAB_HIP_CHECK(hipMalloc(&d, sizeof(cf) * n));
+        GAB_HIP_CHECK(hipMemcpy(d, host.data(), sizeof(cf) * n, hipMemcpyHostToDevice));
         per_device[dev] = d;
     }
     return per_device[dev];
@@ -382,8 +390,10 @@ __device__ __forceinline__ void conv_split_buffer(
     cf* const img = lds + w * kWaveImg;
     const int s1 = ((head + kSlots - 1) & (kSlots - 1)) * kB;         // block k-1
     const int s2 = ((head + kSlots - 2) & (kSlots - 1)) * kB;         // block k-2
-    using WF = fft::WaveFFT1024<false>;
-    using WFi = fft::WaveFFT1024<true>;
+    // exchange 1 through LDS: a launch per buffer is one dependent chain per wave (transform, product, barrier, inverse), which
+    // the swaps lengthen — 9.22-9.25 us per launch against 9.25-9.27 with them (profiles/r24_wave_exchange.txt)
+    using WF = fft::WaveFFT1024<false, false>;
+    using WFi = fft::WaveFFT1024<true, false>;
 
     WF::Twiddles t;
     WF::load_twiddles_raw(t, tw, lane);          // requested first: a wave's loads return in order, and
@@ -1376,7 +1386,7 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (products) product_half(sa2);                          // before barrier 1: the forward transform then overwrites its image
+            if (products) product_half(sa2);                          // before barrier 1: the forward transform overwrites its image behind barrier 2 (its second exchange)
             GAB_B12BAR(nb, 0);                                       // barrier 1
             if (products) store_share();
             __builtin_amdgcn_sched_barrier(0);
@@ -1841,7 +1851,9 @@ __device__ __forceinline__ void conv_split_engine12_resident(
         cf* const hand = lds + (2 + w) * kWaveImg;                    // A2 share, then the output spectrum for the inverse wave
         const float4* const sa = spec + w * kBinsA;                   // taps [0,512)
         const float4* const sa2 = spec + (2 + w) * kBinsA;            // taps [512,1024)
-        using WF = fft::WaveFFT1024<false>;
+        // exchange 1 through LDS: the engine's period follows its near waves' chain (doorbell, transform, product), and the swaps
+        // lengthen it — 5.9-6.0 us per buffer against 6.1-6.3 with them (profiles/r24_wave_exchange.txt)
+        using WF = fft::WaveFFT1024<false, false>;
         WF::Lean t;
         WF::load_twiddles(t, tw, lane);
         const size_t xoff = (size_t)(2 * q) * kB;                     // channel a of a buffer; channel b is kB further
@@ -1949,10 +1961,10 @@ __device__ __forceinline__ void conv_split_engine12_resident(
         cf* const img = lds + (4 + pr) * kWaveImg;                    // the transform's exchanges, then the output swap
         const cf* const other = lds + (4 + (1 - pr)) * kWaveImg;
         const cf* const cg = sp.carry + (size_t)(2 * d + pr) * kCarrySlots * kB;   // the far share comes through memory (agent-scope loads)
-        using WFi = fft::WaveFFT1024<true>;
+        using WFi = fft::WaveFFT1024<true, false>;                    // exchange 1 through LDS, as the forward waves'
         WFi::Lean t;
         WFi::load_twiddles(t, tw, lane);
-        int oslot = 0;                                                // of the next buffer to leave
+        int oslot = 0;                                               // of the next buffer to leave
         int nb = 0, avail = 0, base = 0;                              // the period, buffers that may be touched, the burst's first buffer
         bool boundary = true;                                         // between bursts (the launch's start is a boundary)
         for (;;) {                                                    // periods base .. end of every burst; in a burst's last one only this role works (the drain)
