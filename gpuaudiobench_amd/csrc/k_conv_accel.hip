@@ -943,8 +943,17 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 //     share the inverse wave forms from the prologue's spectrum (profiles/r19_near_products.txt).
 // The far role's schedule per transform (window nb, periods nb and nb + 1; the other group is one period out of step, so a
 // heavy interval of one meets a light one of the other):
-//   period nb:      pass 0 + write | read, pass 1 | write | read, pass 2 | partner write | partner read, product, inverse pass 0
-//   period nb + 1:  (next window's requests) | write | read, pass 1 | write | read, last pass (4 of 16), carry out | -
+//   period nb:      pass 0 + write | read, pass 1 | write (+ spectra of bins 0-7) | read, pass 2 | Z exchange write |
+//                   Z exchange read, products by bin pairs, W exchange write
+//   period nb + 1:  (next window's requests) W exchange read, inverse pass 0 | write | read, pass 1 | write | read, last pass (4 of 16), carry out | -
+// The far product runs by BIN PAIRS (round 25, profiles/r25_far_pair_product.txt): thread t forms its eight low bins k = t + 256 r
+// and their partners N - k from ONE fetch of pm[k] (load_spectra's rule gives the partner's holder, thread 256 - t, the same entry:
+// every entry of the far spectra was asked for twice per transform).  The operands cross in one 2048-entry region of the group's
+// image (the eight high Z at position k - 2048; Z[N - k] read at 2048 - k), the partners' results in a second one (written at
+// (N - k) - 2048; read by the bin's holder behind the period's closing barrier): both lane-consecutive and unpadded, 4096 of the
+// image's 4352 entries, and the region read in an interval is never written in it.  Thread 0: bin 0 is its own partner; bin 2048 —
+// its own, nobody's partner — takes that place (pm[2048], the branch without conjugation, position 0 of the second region).  The
+// same calls on the same operands as the bins' holders made (spectral_product_partner_part): the same bits.
 constexpr int kB12Threads = 768;
 constexpr int kB12SpecCf = 4 * kBinsA * 2;                         // [A pair 0, A pair 1, A2 pair 0, A2 pair 1][513] float4, in cf entries
 constexpr int kB12Tw1Cf = 16 * 15;
@@ -969,6 +978,18 @@ __device__ __forceinline__ void spectral_product_part(cf (&z)[R], const cf (&zra
         cf P = mk(c[r - R0].x, c[r - R0].y), M = mk(c[r - R0].z, c[r - R0].w);
         if (r > R / 2 || (r == R / 2 && tid != 0)) z[r] = fft::cfma_cjcj(zraw[r - R0], M, fft::cmulc(z[r], P));
         else z[r] = fft::cfma_cj(zraw[r - R0], M, fft::cmul(z[r], P));
+    }
+}
+// The PARTNERS of bins [R0, R1) (R1 <= R / 2, bin k > 0): W[N - k] from the operands the thread holds for bin k — z[r] = Z[k],
+// zp = Z[N - k], c = pm[k] — the call spectral_product_part makes for bin N - k in the thread that holds it in z (its z is
+// this zp, its zraw this z[r], its c = pm[N - (N - k)] the same entry): the same bits, from one fetch of the entry.
+template <int N, int R, int R0, int R1>
+__device__ __forceinline__ void spectral_product_partner_part(cf (&wp)[R1 - R0], const cf (&z)[R], const cf (&zp)[R1 - R0], const float4 (&c)[R1 - R0]) {
+    static_assert(R1 <= R / 2, "the partners of the low bins");
+#pragma unroll
+    for (int r = R0; r < R1; ++r) {
+        cf P = mk(c[r - R0].x, c[r - R0].y), M = mk(c[r - R0].z, c[r - R0].w);
+        wp[r - R0] = fft::cfma_cjcj(z[r], M, fft::cmulc(zp[r - R0], P));
     }
 }
 // Bins [R0, R1) per lane of a near product W = Z x spectra, for whichever of a pair's two near waves holds them in v: the
@@ -1083,12 +1104,17 @@ __device__ __forceinline__ void conv_split_batch12_resident(
             }
         };
         cf z[16], zn[16];
+#ifdef GAB_ABLATE
+        const bool own_bins = (sp.debug & 128) != 0;                  // diagnostic bit 128: every thread forms its own sixteen bins' products
+#else
+        constexpr bool own_bins = false;
+#endif
         // The requests ride on the lighter steps (every instruction of a step costs the wave about a dozen clocks beside two
         // others on its SIMD: thirty-two requests in one interval made it the period's longest), the wait for the carry's stores
         // stands in the idle interval.  (Measured and not kept, profiles/r06_batch12_stamps.txt: steps cut as read + twiddle |
         // butterfly + write, so that no step is a bare write — 5.08 against 5.01 us per buffer.)
-        // first half of a transform (period nb):   pass 0, write | read, twiddle, pass 1 | write (+ spectra 0-7) |
-        //                                          read, twiddle (+ spectra 8-15), pass 2 | partner write | partner read, product, inverse pass 0
+        // first half of a transform (period nb):   pass 0, write | read, twiddle, pass 1 | write (+ spectra of bins 0-7) |
+        //                                          read, twiddle, pass 2 | Z exchange write | Z exchange read, products by bin pairs, W exchange write
         auto first_half = [&](int nb) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = zn[r];
@@ -1115,11 +1141,14 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                 for (int r = 0; r < 16; ++r) img[w1 + 17 * r] = z[B16::out_slot(r)];
             }
             __builtin_amdgcn_sched_barrier(0);
-            float4 clo[8], chi[8];                                    // the far spectra: bins r < 8 asked for here, r >= 8 an interval later
+            // the far spectra of the thread's eight LOW bins, pm[t + 256 r]: each entry serves bin k and its partner N - k, so
+            // every entry of the pair's spectra is asked for once per transform (thread 0: and pm[N / 2] for bin N / 2)
+            float4 clo[8], cny = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             {
                 int fo = ft;
                 asm volatile("" : "+v"(fo));
                 load_spectra_part<kNB, 16, 0, 8>(clo, pf, fo);
+                if (fo == 0) cny = pf[kNB / 2];
             }
             __builtin_amdgcn_sched_barrier(0);
             GAB_B12BAR(nb, 2);                                          // 3
@@ -1130,29 +1159,21 @@ __device__ __forceinline__ void conv_split_batch12_resident(
             }
 #pragma unroll
             for (int r = 1; r < 16; ++r) z[r] = fft::cmul(z[r], tw2[r - 1]);
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                int fo = ft;
-                asm volatile("" : "+v"(fo));
-                load_spectra_part<kNB, 16, 8, 16>(chi, pf, fo);
-            }
-            __builtin_amdgcn_sched_barrier(0);
             B16::run(z);
             GAB_B12BAR(nb, 3);                                          // 4
-            {
-                const unsigned t = opaque_t();
+#ifdef GAB_ABLATE
+            if (own_bins) {                                           // the parent's product: every thread its own sixteen bins
+                {
+                    const unsigned t = opaque_t();
 #pragma unroll
-                for (int r = 0; r < 16; ++r) img[t + 256u * r] = z[B16::out_slot(r)];   // Z[t + 256 r]: the partner exchange, raw
-            }
-            GAB_B12BAR(nb, 4);                                          // 5
-            {
-                // the thread's own bins back in order, and Z[(N - k) mod N], k = t + 256 r: one base and constant offsets for
-                // r >= 1 (N - k > 0 there); bin k = t alone wraps
+                    for (int r = 0; r < 16; ++r) img[t + 256u * r] = z[B16::out_slot(r)];   // Z[t + 256 r], raw
+                }
+                GAB_B12BAR(nb, 4);                                      // 5
                 cf o[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[r] = z[B16::out_slot(r)];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) z[r] = o[r];            // z[r] = Z[t + 256 r]
+                for (int r = 0; r < 16; ++r) z[r] = o[r];
                 const unsigned t = opaque_t();
                 const cf* const pb = img + (kNB - 256 * 15) - t;      // pb[256 (15 - r)] = img[N - t - 256 r]
                 cf zp[8];
@@ -1160,21 +1181,73 @@ __device__ __forceinline__ void conv_split_batch12_resident(
 #pragma unroll
                 for (int r = 1; r < 8; ++r) zp[r] = pb[256 * (15 - r)];
                 spectral_product_part<kNB, 16, 0, 8>(z, zp, clo, ft);
+                load_spectra_part<kNB, 16, 8, 16>(clo, pf, ft);
 #pragma unroll
                 for (int r = 0; r < 8; ++r) zp[r] = pb[256 * (7 - r)];
-                spectral_product_part<kNB, 16, 8, 16>(z, zp, chi, ft);
+                spectral_product_part<kNB, 16, 8, 16>(z, zp, clo, ft);
+                GAB_B12BAR(nb, 5);                                      // 6 (all sixteen results stay in registers)
+                return;
             }
-            B16i::run(z);
+#endif
+            // Z exchange: the eight HIGH values Z[t + 256 r], r >= 8, at position k - N / 2 of the image's first region (N / 2
+            // entries, lane-consecutive, unpadded)
+            {
+                const unsigned t = opaque_t();
+#pragma unroll
+                for (int r = 8; r < 16; ++r) img[t + 256u * (r - 8)] = z[B16::out_slot(r)];
+            }
+            GAB_B12BAR(nb, 4);                                          // 5
+            {
+                // the thread's own bins back in order; Z[N - k] of its low bins k = t + 256 r from position N / 2 - k (thread
+                // 0's bin 0 is its own partner; the position wraps to an entry nobody else reads); the low bins' products and
+                // their partners' from the same operands and the same entry of the spectra
+                cf o[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[r] = z[B16::out_slot(r)];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) z[r] = o[r];            // z[r] = Z[t + 256 r]
+                const unsigned t = opaque_t();
+                const cf* const pb = img + (kNB / 2 - 256 * 7) - t;   // pb[256 (7 - r)] = region 0 [N / 2 - t - 256 r]
+                cf zp[8], wp[8];
+                zp[0] = img[(kNB / 2 - t) & (kNB / 2 - 1)];
+                if (t == 0) zp[0] = z[0];
+#pragma unroll
+                for (int r = 1; r < 8; ++r) zp[r] = pb[256 * (7 - r)];
+                spectral_product_partner_part<kNB, 16, 0, 8>(wp, z, zp, clo);
+                spectral_product_part<kNB, 16, 0, 8>(z, zp, clo, ft);
+                if (t == 0) {                                         // bin N / 2 stands where bin 0's partner would: thread 0's own, nobody's partner
+                    const cf P = mk(cny.x, cny.y), M = mk(cny.z, cny.w);
+                    wp[0] = fft::cfma_cj(z[8], M, fft::cmul(z[8], P));
+                }
+                // W exchange: the partners' results at position (N - k) - N / 2 of the second region (bin N / 2 at position 0)
+                cf* const qb = img + kNB / 2 + (kNB / 2 - 256 * 7) - t;
+                img[kNB / 2 + ((kNB / 2 - t) & (kNB / 2 - 1))] = wp[0];
+#pragma unroll
+                for (int r = 1; r < 8; ++r) qb[256 * (7 - r)] = wp[r];
+            }
             GAB_B12BAR(nb, 5);                                          // 6
         };
-        // second half (period nb + 1):   (half of the next window's requests) | write | read, twiddle, pass 1 |
+        // second half (period nb + 1):   (half of the next window's requests) W exchange read, inverse pass 0 | write | read, twiddle, pass 1 |
         //                                write (+ the other half) | read, twiddle, last pass (4 of 16), carry out | (the carry's stores leave)
+        // (Measured and not kept, profiles/r25_far_pair_product.txt: that half of the requests in the idle interval instead, one
+        // interval before pass 0 uses them — 4.85 against 4.73 us per buffer.)
         auto second_half = [&](int period, int nb_done, int nb_next) {
             if (nb_next >= 0) {
                 load_window(std::integral_constant<int, 0>{}, nb_next, zn);
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) zn[r] = mk(0.0f, 0.0f);  // (no value survives from the last window: registers)
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (nb_done >= 0) {
+                // the thread's own eight high results W[t + 256 r], r >= 8, from the second region (written by the partners'
+                // threads before the last period's closing barrier); the low ones are in z
+                if (!own_bins) {
+                    const unsigned t = opaque_t();
+#pragma unroll
+                    for (int r = 8; r < 16; ++r) z[r] = img[kNB / 2 + t + 256u * (r - 8)];
+                }
+                B16i::run(z);
             }
             GAB_B12BAR(period, 0);                                          // 1
             if (nb_done >= 0) {
