@@ -260,6 +260,16 @@ PROTOTYPES = {
     "gab_spec_process_batch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
     "gab_spec_frames": (_I, [_P, _I, C.POINTER(_I)]),
     "gab_spec_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
+    "gab_resyn_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_resyn_destroy": (_I, [_P]),
+    "gab_resyn_set_window": (_I, [_P, _P, _P]),
+    "gab_resyn_reset": (_I, [_P, _P]),
+    "gab_resyn_process": (_I, [_P, _P, _P, C.POINTER(_I), _P]),
+    "gab_resyn_process_batch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
+    "gab_resyn_frames": (_I, [_P, _I, C.POINTER(_I)]),
+    "gab_resyn_count": (_I, [_P, _I, C.POINTER(_I)]),
+    "gab_resyn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
+    "gab_resyn_latency": (_I, [_P, C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

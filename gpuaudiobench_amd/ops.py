@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1387,6 +1387,122 @@ class SpectrumPlan(_TrackPlan):
         return (self._h, _dev(x), _dev(out), C.byref(self._n), _stream(stream))
 
     launch = _launcher("gab_spec_process")
+
+
+def synthesis_window(w, hop):
+    """The least-squares dual of an analysis window w [1024] at `hop`, for ResynthesisPlan.set_window:
+    g[n] = w[n] / sum_m w[n + m hop]^2, m over every index inside 0..1023 in ascending order, 0 where that sum is 0; in
+    float64 on w's values, rounded once to float32.  Then sum_j w g = 1 on the hop grid, and SpectrumPlan (window w) ->
+    ResynthesisPlan (window g) returns the stream delayed by 1024 samples.  A float32 tensor on w's device (the CPU for
+    anything that is not a tensor).  The dual is ill-conditioned as hop approaches 1024, where frames overlap only in
+    the window's skirts: for the periodic Hann window the largest |g| is 0.67 / 1.2 / 2.6 / 430 / 1e5 at hop 256 / 512 /
+    700 / 1000 / 1023, and at hop 1024 the window's zero at n = 0 cannot be undone."""
+    if not 32 <= hop <= 1024:
+        raise ValueError("hop must be 32..1024")
+    device = w.device if isinstance(w, torch.Tensor) else "cpu"
+    w64 = torch.as_tensor(w).detach().to("cpu", torch.float64).reshape(-1)
+    if w64.numel() != 1024:
+        raise ValueError("the window must hold 1024 values")
+    sq, den = w64 * w64, torch.zeros(hop, dtype=torch.float64)
+    for m in range(0, 1024, hop):                         # ascending index, one addition each
+        seg = sq[m:m + hop]
+        den[:seg.numel()] += seg
+    den = den.repeat(-(-1024 // hop))[:1024]
+    g = torch.where(den == 0, torch.zeros_like(w64), w64 / torch.where(den == 0, torch.ones_like(den), den))
+    return g.to(torch.float32).to(device)
+
+
+class ResynthesisPlan(_TrackPlan):
+    """gab_resyn_plan: the overlap-add inverse of SpectrumPlan(mode="complex").  Rows [frames][tracks][513][2] become
+    the stream again: every frame is inverse-transformed, multiplied by the synthesis window (a new plan: the dual of
+    the periodic Hann window at `hop`, see synthesis_window) and added on the hop grid in a fixed order; the 1024 samples
+    later frames still add to are carried on the device.  The output is the resynthesised stream delayed by `latency` =
+    1024 samples, whatever the cut.  A call of n buffers takes exactly the `count(n)` frames that a SpectrumPlan of the
+    same bufsize and hop emits for the same call, possibly none; `counts` says how many without a GPU."""
+
+    _destroy = "gab_resyn_destroy"
+    N = 1024
+    BINS = 513
+    counts = staticmethod(SpectrumPlan.counts)
+
+    def __init__(self, tracks, bufsize, hop=512):
+        self.hop = hop
+        self._create(tracks, bufsize, hop)
+        c = C.c_int(0)
+        check(lib.gab_resyn_latency(self._h, C.byref(c)))
+        self.latency = c.value                              # samples
+        self._none = torch.zeros(2, dtype=torch.float32, device="cuda")     # what a call that takes no frame points at
+
+    def frames(self, n_buffers=1):
+        """The largest frame count a call of n_buffers buffers can take."""
+        c = C.c_int(0)
+        check(lib.gab_resyn_frames(self._h, n_buffers, C.byref(c)))
+        return c.value
+
+    def count(self, n_buffers=1):
+        """The frame count the NEXT call of n_buffers buffers takes; the plan does not move."""
+        c = C.c_int(0)
+        check(lib.gab_resyn_count(self._h, n_buffers, C.byref(c)))
+        return c.value
+
+    def reset(self):
+        """Zero accumulator, position 0; the window stays."""
+        super().reset()
+
+    def set_window(self, g):
+        """g: device tensor [1024], the same for every track; every value finite.  Acts on the frames of the next
+        call; what is in the accumulator stays."""
+        assert g.numel() == self.N
+        check(lib.gab_resyn_set_window(self._h, _dev(g), _stream()))
+
+    def _rows_in(self, rows, n, who):
+        f = self.count(n)
+        if rows.numel() != f * self.tracks * self.BINS * 2:
+            raise ValueError("ResynthesisPlan.%s: this call takes exactly %d frames of [%d][513][2] values, rows holds "
+                             "%d values" % (who, f, self.tracks, rows.numel()))
+        return _dev(rows) if f else _dev(self._none)
+
+    def _run(self, what, rows, out, n, *rest):
+        ptr = self._rows_in(rows, n, what)
+        shape = (self.tracks, self.bufsize) if n == 1 and not rest else (n, self.tracks, self.bufsize)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device="cuda")
+        assert out.numel() == n * self.tracks * self.bufsize
+        f = C.c_int(0)
+        check(self._fn(what)(self._h, ptr, _dev(out), *rest, C.byref(f), _stream()))
+        return out
+
+    def process(self, rows, out=None):
+        """One buffer: rows [count(1)][tracks][513][2] in, the next bufsize samples of every track out,
+        [tracks][bufsize] (`out`, or a new tensor)."""
+        return self._run("process", rows, out, 1)
+
+    def process_batch(self, rows, n_buffers, out=None):
+        """n_buffers consecutive buffers in one call: rows [count(n_buffers)][tracks][513][2] in, [n_buffers][tracks]
+        [bufsize] out."""
+        return self._run("process_batch", rows, out, n_buffers, n_buffers)
+
+    def state(self):
+        """(a copy of acc [tracks][1024]: acc[i] the partial sum of the output sample i places behind the position; a
+        copy of the window [1024]; samples since the reset mod hop)."""
+        a, w, p = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib.gab_resyn_state(self._h, C.byref(a), C.byref(w), C.byref(p)))
+        return _view(a.value, self.tracks, self.N).clone(), _view(w.value, 1, self.N).clone().view(self.N), p.value
+
+    def prepare(self, rows, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
+        there (phase 0, bufsize / hop frames a call) and nowhere else."""
+        if self.bufsize % self.hop:
+            raise ValueError("ResynthesisPlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
+                             "frame count change from call to call and a prepared or captured call would repeat one "
+                             "of them" % (self.hop, self.bufsize))
+        assert rows.numel() == (self.bufsize // self.hop) * self.tracks * self.BINS * 2
+        assert out.numel() == self.tracks * self.bufsize
+        self._n = C.c_int(0)
+        return (self._h, _dev(rows), _dev(out), C.byref(self._n), _stream(stream))
+
+    launch = _launcher("gab_resyn_process")
 
 
 def fdtd_default_params(nx, ny=None, nz=None):

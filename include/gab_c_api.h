@@ -1410,8 +1410,8 @@ int gab_lim_latency(gab_lim_plan* plan, int* samples);
  * the phase is 0 and the count B / H on every call.  Arguments are checked before any device call: tracks >= 1,
  * bufsize >= 1, 32 <= hop <= 1024, bands 0..64 and 0 with GAB_SPEC_COMPLEX, n_buffers B < 2^31 - 1024, and at most
  * 2^23 workgroups (frames x ceil(T / 8)) a call.  Out of scope: averaging, peak hold or decay across frames (a line of
- * torch on the rows), other transform sizes, a window per track, an inverse transform, complex rows in bands.
- * One thread at a time per plan.                                                                                     */
+ * torch on the rows), other transform sizes, a window per track, complex rows in bands.  (The inverse is the resynthesis
+ * plan, gab_resyn_*, below.)  One thread at a time per plan.                                                         */
 typedef struct gab_spec_plan gab_spec_plan;
 #define GAB_SPEC_COMPLEX 0
 #define GAB_SPEC_POWER 1
@@ -1425,6 +1425,86 @@ int gab_spec_process_batch(gab_spec_plan* plan, const float* d_in, float* d_rows
                            gab_stream_t stream);
 int gab_spec_frames(gab_spec_plan* plan, int n_buffers, int* capacity);
 int gab_spec_state(gab_spec_plan* plan, float** d_hist, float** d_window, int* position_mod_hop);
+
+/* ---- resynthesis: the overlap-add inverse of the spectrum plan, with a carried accumulator (additive; no counterpart in
+ * the reference) -----------------------------------------------------------------------------------------------------
+ * The synthesis half: the complex rows of a spectrum plan, whatever was done to them in between (a gate, a per-bin
+ * equaliser, a freeze, any torch operation on [frames][T][513][2]), become a stream again.  N = 1024 is the transform,
+ * B = bufsize, H the hop (fixed at create, 32 <= H <= 1024, any integer), T = tracks.
+ *   rows in         d_rows [frames][T][513][2] float32, exactly what GAB_SPEC_COMPLEX writes (bins 0..512, re then im),
+ *                   on an 8-byte boundary, never written; it may not overlap d_out.  The imaginary parts of bins 0 and
+ *                   512 are READ AS ZERO, whatever the row holds (in the packed pair below they would otherwise leak
+ *                   from one track of a pair into the other).
+ *   frames taken    A call that produces the output samples [p, p + n B) takes exactly the frames j with
+ *                   p < jH <= p + n B, in ascending j: the frames a spectrum plan of the same B and H emits for the same
+ *                   call of the same cut.  floor((p + n B) / H) - floor(p / H) of them, possibly none.  The count is
+ *                   host integer arithmetic on the carried p mod H and is returned in *n_frames without touching the
+ *                   device; d_rows must hold that many frames (and is not read in a call that takes none).
+ *                   gab_resyn_frames gives the largest count any call of n_buffers buffers can take,
+ *                   ceil(n_buffers B / H); gab_resyn_count gives the count the NEXT call of n_buffers buffers takes,
+ *                   without moving the plan.
+ *   a frame         u_j[n] = x_j[n] * 2^-10, x_j the unnormalised real inverse 1024-point transform of the Hermitian
+ *                   extension of the track's row of frame j, in float32;
+ *                   v_j[n] = g[n] * u_j[n]                                one float32 product, rounded once
+ *                   with g the synthesis window.
+ *   the sum         y[a], a >= -N, is the float32 sum of v_j[a - (jH - N)] over the frames j >= 1 with
+ *                   jH - N <= a < jH, added in ascending j starting from +0.0f, one addition per frame, rounded once and
+ *                   never fused with the product.
+ *   output, latency d_out [n][T][B] float32, the layout of the analyser's input, any 4-byte alignment.  Output sample o
+ *                   (absolute since create or reset) is y[o - N]: the latency is 1024 samples (gab_resyn_latency), the
+ *                   same for every H and B, and to within one sample the smallest that holds for every cut (the frame
+ *                   that ends one sample past a call's end still adds to the sample 1023 places before it).  The
+ *                   shorter N - H that a plan whose hop divides its buffer could have is out of scope.  The first H
+ *                   outputs after a reset are +0.0f; outputs H .. N - 1 are y at negative indices exactly as the sum
+ *                   gives them (rounding-level values for an analyser's rows: its first frames reach back before the
+ *                   stream), and nothing special-cases them.
+ *   state           One accumulator d_acc [T][1024].  After a call that ends at position P, acc[i] is the partial sum of
+ *                   y[P - N + i] over every frame with jH <= P; acc[0] is then complete.  Also carried: the window
+ *                   [1024] and p mod H.  gab_resyn_state exposes all three, the plan's own memory, for inspection.
+ *                   reset zeroes the accumulator and the position; the window stays.
+ *   window          g: 1024 floats, the same for every track.  set_window takes d_window (device, [1024]), checked on
+ *                   the device: the first value that is not finite is named with GAB_ERR_INVALID_ARG, and a refused set
+ *                   leaves the plan as it was.  There is no rule on a sum.  An accepted window acts on the frames of the
+ *                   next call; what is in the accumulator stays.  Synchronous with respect to `stream`.
+ *                   A new plan holds the least-squares dual of the spectrum plan's periodic Hann window w at its hop,
+ *                     g[n] = w[n] / sum_m w[n + m H]^2      m over every index inside 0..1023, ascending; 0 where the
+ *                                                           sum is 0
+ *                   in float64 on the float32 values of w, rounded once: sum_j w[a - jH + N] g[a - jH + N] = 1 for every
+ *                   a, so analyser -> resynthesis returns the stream delayed by 1024 samples.  The dual is
+ *                   ILL-CONDITIONED as H approaches 1024, where the frames overlap only in the window's skirts: the
+ *                   largest |g| is 0.67 / 1.2 / 2.6 / 430 / 1e5 at H = 256 / 512 / 700 / 1000 / 1023, and at H = 1024
+ *                   Hann's zero at n = 0 cannot be undone: sample 0 of every frame is lost.
+ *   channel pairs   Tracks 2q and 2q + 1 share one complex inverse (an odd last track beside zeros):
+ *                   Z[k] = Xa[k] + i Xb[k] for k <= 512, Z[N - k] = conj(Xa[k]) + i conj(Xb[k]) for 0 < k < 512; the real
+ *                   part of the inverse is track a, the imaginary part track b.  A track's absolute error follows its
+ *                   PAIR's peak (tests/test_resynthesis_gpu.py holds every frame within four times the float32
+ *                   restatement of tests/resynthesis_twin.py, over peak_a + peak_b in time).  A silent pair gives zeros.
+ *                   A pair depends on nothing outside itself, bit for bit.  A NaN or an infinity in one row makes that
+ *                   frame's 1024 output samples of its pair non-finite and touches nothing else: an emitted sample's
+ *                   accumulator slot is STORED as zero, not scaled, so nothing lingers.
+ *   determinism     u_j's bits depend on the pair's two rows of frame j alone (bins 0 and 512 as ruled above).  The
+ *                   output's bits depend on the u_j, on g and on the order above; not on B, on how the stream was cut
+ *                   into calls or batches, on the alignment of d_out or on which frames share a launch.  A pair-aligned
+ *                   shard of tracks as its own plan gives those tracks' bits.
+ * A call is one launch on `stream` (a wave per pair walks the call's frames in ascending j: that walk is the order of the
+ * sum; no atomics, no scratch); it allocates nothing and waits for nothing, and all changing state but p mod H is on the
+ * device.  The frame phase p mod H and the count are launch arguments: a captured process replays one phase ("Captured
+ * calls", above) and is the stream's next buffer only where H divides B.  Arguments are checked before any device call:
+ * tracks >= 1, bufsize >= 1, 32 <= hop <= 1024, tracks <= 2^26 (2^23 workgroups of eight tracks), n_buffers B <
+ * 2^31 - 1024, null pointers, d_rows on an 8-byte boundary and apart from d_out.  Out of scope: other transform sizes,
+ * a window per track, the N - H latency, any spectral processor itself.  One thread at a time per plan.            */
+typedef struct gab_resyn_plan gab_resyn_plan;
+int gab_resyn_create(gab_resyn_plan** plan, int tracks, int bufsize, int hop);
+int gab_resyn_destroy(gab_resyn_plan* plan);
+int gab_resyn_set_window(gab_resyn_plan* plan, const float* d_window, gab_stream_t stream);
+int gab_resyn_reset(gab_resyn_plan* plan, gab_stream_t stream);
+int gab_resyn_process(gab_resyn_plan* plan, const float* d_rows, float* d_out, int* n_frames, gab_stream_t stream);
+int gab_resyn_process_batch(gab_resyn_plan* plan, const float* d_rows, float* d_out, int n_buffers, int* n_frames,
+                            gab_stream_t stream);
+int gab_resyn_frames(gab_resyn_plan* plan, int n_buffers, int* capacity);
+int gab_resyn_count(gab_resyn_plan* plan, int n_buffers, int* frames);
+int gab_resyn_state(gab_resyn_plan* plan, float** d_acc, float** d_window, int* position_mod_hop);
+int gab_resyn_latency(gab_resyn_plan* plan, int* samples);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
