@@ -270,6 +270,18 @@ PROTOTYPES = {
     "gab_resyn_count": (_I, [_P, _I, C.POINTER(_I)]),
     "gab_resyn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
     "gab_resyn_latency": (_I, [_P, C.POINTER(_I)]),
+    "gab_dn_create": (_I, [C.POINTER(_P), _I, _I, _I]),
+    "gab_dn_destroy": (_I, [_P]),
+    "gab_dn_set_thresholds": (_I, [_P, _P, _I, _I, _P]),
+    "gab_dn_set_params": (_I, [_P, _P, _I, _I, _P]),
+    "gab_dn_set_windows": (_I, [_P, _P, _P, _P]),
+    "gab_dn_reset": (_I, [_P, _P]),
+    "gab_dn_process": (_I, [_P, _P, _P, _P]),
+    "gab_dn_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_dn_process_rows": (_I, [_P, _P, _P, _I, _P]),
+    "gab_dn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
+    "gab_dn_tables": (_I, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "gab_dn_latency": (_I, [_P, C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

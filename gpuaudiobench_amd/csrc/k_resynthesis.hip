@@ -28,6 +28,7 @@
 
 #include "gab_fft.hpp"
 #include "gab_plan.hpp"
+#include "gab_stft.hpp"
 
 namespace gab {
 namespace {
@@ -187,22 +188,6 @@ struct gab_resyn_plan {
 namespace gab {
 namespace {
 
-// g[n] = w[n] / sum_m w[n + m H]^2, m over every index inside 0..1023 in ascending order, 0 where the sum is 0: float64,
-// rounded once.  w: the periodic Hann window as the spectrum plan holds it (float64, rounded once to float32).
-std::vector<float> resyn_hann_dual(int H) {
-    const double pi = 3.14159265358979323846;
-    std::vector<double> w((size_t)kResynN);
-    for (int n = 0; n < kResynN; ++n)
-        w[(size_t)n] = (double)(float)(0.5 - 0.5 * std::cos(2.0 * pi * (double)n / (double)kResynN));
-    std::vector<float> g((size_t)kResynN);
-    for (int n = 0; n < kResynN; ++n) {
-        double s = 0.0;
-        for (int i = n % H; i < kResynN; i += H) s += w[(size_t)i] * w[(size_t)i];
-        g[(size_t)n] = s == 0.0 ? 0.0f : (float)(w[(size_t)n] / s);
-    }
-    return g;
-}
-
 // n buffers in one launch on s, from the plan's position; nothing is allocated, nothing waits.  *n_frames: host.
 int resyn_launch(gab_resyn_plan* p, const float* d_rows, float* d_out, int n_buffers, int* n_frames, hipStream_t s,
                  const char* who) {
@@ -243,7 +228,7 @@ int gab_resyn_create(gab_resyn_plan** out, int tracks, int bufsize, int hop) {
         p.window.alloc(gab::kResynN);
         p.acc.alloc((size_t)tracks * gab::kResynN);
         p.flag.alloc(1);
-        const std::vector<float> g = gab::resyn_hann_dual(hop);
+        const std::vector<float> g = gab::stft_hann_dual(hop);  // of the spectrum plan's periodic Hann window
         GAB_HIP_CHECK(hipMemcpy(p.window.get(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
         GAB_HIP_CHECK(hipMemset(p.acc.get(), 0, p.acc.size() * sizeof(float)));
         GAB_HIP_CHECK(hipStreamSynchronize(nullptr));

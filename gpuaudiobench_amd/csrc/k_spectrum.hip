@@ -28,6 +28,7 @@
 
 #include "gab_fft.hpp"
 #include "gab_plan.hpp"
+#include "gab_stft.hpp"
 
 namespace gab {
 namespace {
@@ -291,14 +292,8 @@ int gab_spec_create(gab_spec_plan** out, int tracks, int bufsize, int hop, int m
         p.edges.alloc(gab::kSpecMaxBands + 1);
         p.flag.alloc(1);
         // the periodic Hann window, float64, rounded once; S added in ascending n over the rounded values
-        const double pi = 3.14159265358979323846;
-        std::vector<float> w(gab::kSpecN);
-        double S = 0.0;
-        for (int n = 0; n < gab::kSpecN; ++n) {
-            w[(size_t)n] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (double)n / (double)gab::kSpecN));
-            S += (double)w[(size_t)n];
-        }
-        gab::spectrum_scale(&p, S);
+        const std::vector<float> w = gab::stft_hann();
+        gab::spectrum_scale(&p, gab::stft_window_sum(w));
         int e[gab::kSpecMaxBands + 1] = {0};
         for (int b = 0; b <= bands; ++b) e[b] = bands ? (int)((long long)gab::kSpecBins * b / bands) : 0;
         GAB_HIP_CHECK(hipMemcpy(p.window.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));

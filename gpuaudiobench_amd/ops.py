@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1503,6 +1503,131 @@ class ResynthesisPlan(_TrackPlan):
         return (self._h, _dev(rows), _dev(out), C.byref(self._n), _stream(stream))
 
     launch = _launcher("gab_resyn_process")
+
+
+def denoise_params(floor_db=-24.0, attack_ms=5.0, release_ms=80.0, hop=256, fs=48000.0):
+    """A row (all arguments scalars) or a table [n][3] float32 of DenoisePlan parameters {floor, att, rel} from the knobs
+    of a noise reduction; float64, rounded once.  floor = 10^(floor_db / 20) is the gain of a shut bin (floor_db <= 0;
+    -inf shuts it completely); att and rel are per FRAME, exp(-hop / (fs t)) for the time constant t of an opening and
+    of a closing bin, and a time of 0 is a coefficient of 0 (the gain jumps)."""
+    import numpy as np
+    args = [np.asarray(a, np.float64) for a in (floor_db, attack_ms, release_ms)]
+    scalar = all(a.ndim == 0 for a in args)
+    floor_db, att_ms, rel_ms = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    if (floor_db > 0.0).any() or (att_ms < 0.0).any() or (rel_ms < 0.0).any() or fs <= 0.0 or hop <= 0:
+        raise ValueError("needs floor_db <= 0, attack_ms and release_ms >= 0, fs > 0 and hop > 0")
+    att = np.where(att_ms > 0.0, np.exp(-hop / (fs * np.where(att_ms > 0.0, att_ms / 1000.0, 1.0))), 0.0)
+    rel = np.where(rel_ms > 0.0, np.exp(-hop / (fs * np.where(rel_ms > 0.0, rel_ms / 1000.0, 1.0))), 0.0)
+    table = np.stack([10.0 ** (floor_db / 20.0), att, rel], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+def denoise_thresholds(power_rows, sensitivity_db=6.0):
+    """The "learn a noise profile" step: power_rows [frames][tracks][513] of SpectrumPlan(mode="power"), recorded over a
+    stretch of noise alone, become DenoisePlan thresholds [tracks][513]: the float64 mean over the frames times
+    10^(sensitivity_db / 10), rounded once to float32.  A tensor on power_rows' device (a numpy array for anything that
+    is not a tensor)."""
+    import numpy as np
+    is_tensor = isinstance(power_rows, torch.Tensor)
+    p = (power_rows.detach().to("cpu").numpy() if is_tensor else np.asarray(power_rows)).astype(np.float64)
+    if p.ndim != 3 or p.shape[0] == 0 or p.shape[2] != 513:
+        raise ValueError("power_rows must be [frames][tracks][513] with at least one frame")
+    thr = (p.mean(axis=0) * 10.0 ** (float(sensitivity_db) / 10.0)).astype(np.float32)
+    return torch.from_numpy(thr).to(power_rows.device) if is_tensor else thr
+
+
+class DenoisePlan(_TrackPlan):
+    """gab_dn_plan: a spectral noise gate per (track, bin) with a smoothed gain.  process / process_batch take the stream
+    and return it gated and delayed by `latency` = 1024 samples in ONE launch: SpectrumPlan(mode="complex")'s analysis,
+    the gate, ResynthesisPlan's overlap-add, bit for bit that composition.  process_rows is the gate alone, complex rows
+    [frames][tracks][513][2] in and out, for rows one already holds; it moves the mask only.  Tables: thresholds
+    [tracks][513] on the power of a bin (denoise_thresholds learns them from noise) and {floor, att, rel} per track
+    (denoise_params).  A new plan is transparent."""
+
+    _destroy = "gab_dn_destroy"
+    N = 1024
+    BINS = 513
+    FIELDS = ("floor", "att", "rel")
+    counts = staticmethod(SpectrumPlan.counts)
+
+    def __init__(self, tracks, bufsize, hop=256):
+        self.hop = hop
+        self._create(tracks, bufsize, hop)
+        c = C.c_int(0)
+        check(lib.gab_dn_latency(self._h, C.byref(c)))
+        self.latency = c.value                              # samples
+        self._none = torch.zeros(2, dtype=torch.float32, device="cuda")     # what a call of no frame points at
+
+    def reset(self):
+        """Zero history and accumulator, a mask of ones, position 0; the tables and the windows stay."""
+        super().reset()
+
+    def set_thresholds(self, thr, first_track=0):
+        """thr: device tensor [n][513] for tracks [first_track, first_track + n): every value >= 0 or +inf (always
+        shut).  Acts from the next frame processed; the mask is kept."""
+        n = self._rows(thr, self.BINS, first_track, "thr")
+        check(lib.gab_dn_set_thresholds(self._h, _dev(thr), first_track, n, _stream()))
+
+    def set_params(self, rows, first_track=0):
+        """rows: device tensor [n][3] of {floor, att, rel} for tracks [first_track, first_track + n): 0 <= floor <= 1,
+        0 <= att < 1, 0 <= rel < 1.  Acts from the next frame processed, unramped; the mask is kept."""
+        n = self._rows(rows, len(self.FIELDS), first_track, "rows")
+        check(lib.gab_dn_set_params(self._h, _dev(rows), first_track, n, _stream()))
+
+    def set_windows(self, w, g):
+        """w, g: device tensors [1024], the analysis and the synthesis window, the same for every track; every value
+        finite and w's sum not zero (synthesis_window makes g from w).  A refused set keeps both."""
+        assert w.numel() == self.N and g.numel() == self.N
+        check(lib.gab_dn_set_windows(self._h, _dev(w), _dev(g), _stream()))
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize] in, the next bufsize samples of every track out (`out`, or a new
+        tensor like x); x and out may not overlap."""
+        return self._process("process", x, out, 1, None)
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch, [n][tracks][bufsize] both ways."""
+        n = _n_buffers(self, xs)
+        return self._process("process_batch", xs, out, n, None, n)
+
+    def process_rows(self, rows, out=None):
+        """The gate alone on rows [frames][tracks][513][2] (any number of frames, none too): returns the gated rows in
+        `out` (rows itself for in place; None: a new tensor).  Moves the mask, nothing else."""
+        f, rest = divmod(rows.numel(), self.tracks * self.BINS * 2)
+        if rest:
+            raise ValueError("DenoisePlan.process_rows: rows must hold whole frames of [%d][513][2] values" % self.tracks)
+        out = torch.empty_like(rows) if out is None else out
+        assert out.numel() == rows.numel()
+        a, b = (_dev(rows), _dev(out)) if f else (_dev(self._none), _dev(self._none))
+        check(lib.gab_dn_process_rows(self._h, a, b, f, _stream()))
+        return out
+
+    def state(self):
+        """Copies of (hist [tracks][1023], the last 1023 samples oldest first; acc [tracks][1024], the partial sums
+        behind the position; mask [tracks][513]; samples since the reset mod hop)."""
+        h, a, m, p = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib.gab_dn_state(self._h, C.byref(h), C.byref(a), C.byref(m), C.byref(p)))
+        return (_view(h.value, self.tracks, self.N - 1).clone(), _view(a.value, self.tracks, self.N).clone(),
+                _view(m.value, self.tracks, self.BINS).clone(), p.value)
+
+    def tables(self):
+        """Copies of (thr [tracks][513], params [tracks][3])."""
+        t, p = C.c_void_p(), C.c_void_p()
+        check(lib.gab_dn_tables(self._h, C.byref(t), C.byref(p)))
+        return _view(t.value, self.tracks, self.BINS).clone(), _view(p.value, self.tracks, len(self.FIELDS)).clone()
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
+        there (phase 0, bufsize / hop frames a call) and nowhere else."""
+        if self.bufsize % self.hop:
+            raise ValueError("DenoisePlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
+                             "frame count change from call to call and a prepared or captured call would repeat one "
+                             "of them" % (self.hop, self.bufsize))
+        assert x.numel() == out.numel() == self.tracks * self.bufsize
+        return (self._h, _dev(x), _dev(out), _stream(stream))
+
+    launch = _launcher("gab_dn_process")
 
 
 def fdtd_default_params(nx, ny=None, nz=None):

@@ -1492,7 +1492,8 @@ int gab_spec_state(gab_spec_plan* plan, float** d_hist, float** d_window, int* p
  * calls", above) and is the stream's next buffer only where H divides B.  Arguments are checked before any device call:
  * tracks >= 1, bufsize >= 1, 32 <= hop <= 1024, tracks <= 2^26 (2^23 workgroups of eight tracks), n_buffers B <
  * 2^31 - 1024, null pointers, d_rows on an 8-byte boundary and apart from d_out.  Out of scope: other transform sizes,
- * a window per track, the N - H latency, any spectral processor itself.  One thread at a time per plan.            */
+ * a window per track, the N - H latency, any spectral processor itself (a gate per bin between the two plans, and both
+ * fused around it, is the denoise plan, gab_dn_*, below).  One thread at a time per plan.                           */
 typedef struct gab_resyn_plan gab_resyn_plan;
 int gab_resyn_create(gab_resyn_plan** plan, int tracks, int bufsize, int hop);
 int gab_resyn_destroy(gab_resyn_plan* plan);
@@ -1505,6 +1506,88 @@ int gab_resyn_frames(gab_resyn_plan* plan, int n_buffers, int* capacity);
 int gab_resyn_count(gab_resyn_plan* plan, int n_buffers, int* frames);
 int gab_resyn_state(gab_resyn_plan* plan, float** d_acc, float** d_window, int* position_mod_hop);
 int gab_resyn_latency(gab_resyn_plan* plan, int* samples);
+
+/* ---- denoise: a spectral noise gate per track and bin, fused between analysis and resynthesis (additive; no
+ * counterpart in the reference) ---------------------------------------------------------------------------------------
+ * Broadband noise reduction in the style of "take a noise profile, then reduce": every bin of every frame is compared
+ * with its own threshold, and a smoothed gain per (track, bin) follows the verdict.  Two forms share one state and one
+ * arithmetic: the FUSED form (process, process_batch) takes the stream and returns the stream in one launch, the rows
+ * never leaving the wave; the ROWS form (process_rows) takes the complex rows of a spectrum plan and returns rows for a
+ * resynthesis plan.  N = 1024 is the transform, B = bufsize, H the hop (fixed at create, 32 <= H <= 1024, any integer),
+ * T = tracks.
+ *   the contract    On one device, the fused form equals
+ *                     gab_spec_* (GAB_SPEC_COMPLEX, same B and H) -> gab_dn_process_rows -> gab_resyn_* (same B and H)
+ *                   with the same tables and windows BIT FOR BIT: the outputs, d_hist against the analyser's history,
+ *                   d_acc against the resynthesiser's accumulator, d_mask and p mod H, after every call of any cut.
+ *   analysis        exactly the spectrum plan's: frame j is the 1024 samples that end at stream position jH, the last
+ *                   1023 samples per track are carried in d_hist [T][1023], the windowed sample is one float32 product
+ *                   w[n] * x, tracks 2q and 2q + 1 share one complex transform and are unpacked as gab_fft_r2c_1024
+ *                   does it.  A new plan holds the spectrum plan's periodic Hann window, bit for bit, and its
+ *                   inv_k = (float)(4 / S^2) for 0 < k < 512, (float)(1 / S^2) for k = 0 and 512.
+ *   the gate        per frame j in ascending order, track t, bin k = 0..512, on the bin (re, im); every operation is
+ *                   rounded once and nothing is fused but the one fmaf:
+ *                     P   = ((re * re) + (im * im)) * inv_k        bit for bit GAB_SPEC_POWER's value of that bin
+ *                     tg  = (P > thr[t][k]) ? 1.0f : floor[t]      strict; a NaN P compares false
+ *                     c   = (tg > m[t][k]) ? att[t] : rel[t]
+ *                     m[t][k] = fmaf(c, m[t][k] - tg, tg)          the gate plan's glide
+ *                     re' = m[t][k] * re;  im' = m[t][k] * im
+ *                   m is carried in d_mask [T][513] and is 1.0f after create and reset.  With 0 <= c < 1 every rounded
+ *                   step stays between the old m and tg, so with floor <= 1 m stays within [the smallest floor seen, 1];
+ *                   and tg is one of two finite values, so m never holds a NaN or an infinity, whatever the input.
+ *                   With floor 0 and rel 0.5 a shut bin's m halves exactly, through the subnormals, to +0.
+ *   synthesis       exactly the resynthesis plan's: the pair is packed, the imaginary parts of bins 0 and 512 are read as
+ *                   zero, the inverse is scaled by 2^-10, multiplied once by the synthesis window g[n], and added with one
+ *                   rounded addition per frame in ascending j into d_acc [T][1024]; emitted slots are stored as zero.
+ *                   Output sample o is the gated stream's sample o - 1024 (gab_dn_latency).  A new plan holds the
+ *                   least-squares dual of Hann at H, the values gab_resyn_create makes.
+ *   tables          thr [T][513]: every value >= 0, or +inf (that bin is always shut); a NaN and a negative value are
+ *                   refused.  A new plan holds zeros.  params [T][GAB_DN_FIELDS] = {floor, att, rel} per track with
+ *                   0 <= floor <= 1, 0 <= att < 1, 0 <= rel < 1; a new plan holds {1, 0, 0}.  So a new plan is
+ *                   transparent: its output is the bits of spectrum plan -> resynthesis plan.  att and rel are per FRAME:
+ *                   exp(-H / (fs t)) for a time constant t.  Both sets take a device table for tracks [first_track,
+ *                   first_track + n_tracks), checked on the device first: the first value that breaks its rule is named
+ *                   (track, bin or field) with GAB_ERR_INVALID_ARG and the plan keeps its table.  An accepted set acts
+ *                   from the next frame processed, unramped (the gain law itself is the glide); the state is kept.
+ *                   gab_dn_tables exposes both tables, the plan's own memory.  Synchronous with respect to `stream`.
+ *   windows         set_windows takes both, each device [1024]: every value finite, and the analysis sum S not zero (it
+ *                   scales P).  Both are checked before either is written; a refused set keeps both.
+ *   rows form       d_rows_in, d_rows_out [n_frames][T][513][2], any n_frames >= 0, on 8-byte boundaries; d_rows_out is
+ *                   d_rows_in itself or apart from it (a partial overlap is refused).  It advances the mask ONLY: the
+ *                   history, the accumulator and the position belong to the analyser and the resynthesiser beside it.
+ *                   One launch, a thread per (track, bin) that walks the frames in order.
+ *   fused form      d_in, d_out [n][T][B] float32, any 4-byte alignment.  d_in may NOT overlap d_out: the output is
+ *                   delayed, and a later frame still reads input that the delayed output would already have overwritten.
+ *   reset           d_hist and d_acc become zero, d_mask 1.0f, the position 0; the tables and the windows stay.
+ *   state           gab_dn_state: d_hist [T][1023], d_acc [T][1024], d_mask [T][513], p mod H; the plan's own memory.
+ *   channel pairs   as in both plans: a pair depends on nothing outside itself, bit for bit; a silent pair gives zeros.
+ *                   A NaN or an infinity in the input stays in its pair and in the 1024-sample spans of the frames that
+ *                   hold it, and leaves the mask finite.
+ *   determinism     Output bits depend on the pair's samples, the tables and the order of frames.  Not on B, on the cut
+ *                   into calls or batches, on the alignment of d_in and d_out, or on which frames share a launch.  A
+ *                   pair-aligned shard of tracks as its own plan gives those tracks' bits.
+ * A fused call is one launch on `stream` (a wave per pair walks the call's frames in ascending j and owns the pair's
+ * state: no atomics, no scratch, no second launch); it allocates nothing and waits for nothing, and all changing state but
+ * p mod H is on the device.  The frame phase p mod H and the count are launch arguments: a captured process replays one
+ * phase ("Captured calls", above) and is the stream's next buffer only where H divides B.  Arguments are checked before
+ * any device call: tracks >= 1, bufsize >= 1, 32 <= hop <= 1024, tracks <= 2^26, n_buffers B < 2^31 - 1024, null
+ * pointers, the track range of a set, the overlaps and alignments above.  Out of scope: smoothing across bins, a hold
+ * counter, subtractive or Wiener gain laws, one threshold table for all tracks, other transform sizes, the N - H
+ * latency, ramped table sets.  One thread at a time per plan.                                                       */
+typedef struct gab_dn_plan gab_dn_plan;
+#define GAB_DN_FIELDS 3
+int gab_dn_create(gab_dn_plan** plan, int tracks, int bufsize, int hop);
+int gab_dn_destroy(gab_dn_plan* plan);
+int gab_dn_set_thresholds(gab_dn_plan* plan, const float* d_thr, int first_track, int n_tracks, gab_stream_t stream);
+int gab_dn_set_params(gab_dn_plan* plan, const float* d_params, int first_track, int n_tracks, gab_stream_t stream);
+int gab_dn_set_windows(gab_dn_plan* plan, const float* d_analysis, const float* d_synthesis, gab_stream_t stream);
+int gab_dn_reset(gab_dn_plan* plan, gab_stream_t stream);
+int gab_dn_process(gab_dn_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_dn_process_batch(gab_dn_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_dn_process_rows(gab_dn_plan* plan, const float* d_rows_in, float* d_rows_out, int n_frames,
+                        gab_stream_t stream);
+int gab_dn_state(gab_dn_plan* plan, float** d_hist, float** d_acc, float** d_mask, int* position_mod_hop);
+int gab_dn_tables(gab_dn_plan* plan, float** d_thr, float** d_params);
+int gab_dn_latency(gab_dn_plan* plan, int* samples);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
