@@ -6,18 +6,22 @@
 //
 //   denoise_kernel        one launch a call: one wave per pair of tracks, four waves a workgroup, no workgroup barrier.
 //                         The wave owns its pair's state and walks the call's frames in ascending j (the order of the mask
-//                         recursion and of the overlap-add).  Per frame: spectrum_kernel's gather, window product, wave-held
+//                         recursion and of the overlap-add).  Per frame: stft::analyse's gather, window product, wave-held
 //                         forward transform and unpack; the gate on the lane's bins k = lane + 64 r (r < 9), mask and
 //                         thresholds in registers for the whole call; the gated bins through the wave's image, from where
 //                         every lane takes the bins above 512 as bin N - k (moved, not recomputed: the rows form's bits);
-//                         resynthesis_kernel's packing, wave-held inverse, scale, window and one rounded addition per slot
-//                         into a wave-private LDS ring, whose finished samples go out in front of every frame.  Behind the
+//                         stft::pack's packing, wave-held inverse, stft::Ring's scale, window and one rounded addition
+//                         per slot into a wave-private LDS ring, whose finished samples go out in front of every frame.
+//                         These stages are written out here, statement for statement what gab_stft.hpp holds for the
+//                         other two plans: through the helpers the compiler schedules this kernel 0.4 to 2.3 % slower
+//                         (DESIGN.md §4o), so a change to a helper is made here too.  Behind the
 //                         last frame the same wave emits the rest, writes the accumulator and the mask back and forms the
 //                         new history from the old one and the call's samples, every value in a register before any is
 //                         written.  No input ring in LDS: a frame's samples come from the caches.
 //   denoise_rows_kernel   one thread per (track, bin), contiguous along k; it walks the frames in order, the mask in a
 //                         register, and reads a bin and writes a bin per frame (in place or apart).
-//   DenoiseThrRule, DenoiseParamRule, DenoiseWindowRule    what gab_plan.hpp's check kernel refuses of a table.
+//   DenoiseThrRule, DenoiseParamRule    what gab_plan.hpp's check kernel refuses of a table (the windows:
+//                         gab_stft.hpp's rule).
 //
 // Output bits depend on the pair's samples, the tables and the order of frames; not on bufsize, on the cut into calls or
 // batches, on the alignment of d_in or d_out or on which frames share a launch.  No atomics, no scratch.
@@ -38,35 +42,13 @@ namespace {
 
 using fft::cf;
 
-constexpr int kDnN = 1024;                                // the transform, and the floats of a track's accumulator
-constexpr int kDnBins = kDnN / 2 + 1;                     // 513
-constexpr int kDnHist = kDnN - 1;                         // samples carried per track
-constexpr int kDnMinHop = 32;
-constexpr int kDnImg = fft::Pad<16>::size(kDnN);          // cf entries of a wave's LDS image (1088)
-constexpr int kDnImgB = 544;                              // track b's gated bins in the image: [544, 544 + 513) <= 1088
 constexpr int kDnMaxTracks = 1 << 26;                     // 2^23 workgroups of eight tracks: 2^31 threads
 constexpr int kDnFields = GAB_DN_FIELDS;                  // {floor, att, rel}
-
-// The lanes of a wave hand LDS words to one another (ring slots, gated bins): LDS instructions of a wave execute in
-// order, and this keeps the compiler from moving them across the hand-over (k_resynthesis.hip's).
-__device__ __forceinline__ void dn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// Sample i (relative to the call's first sample; -1023 <= i < n_buffers B) of track t (k_spectrum.hip's).
-__device__ __forceinline__ float dn_sample(const float* __restrict__ in, const float* hist, int T, int B,
-                                           bool one_buffer, int t, int i) {
-    if (i < 0) return hist[(size_t)t * kDnHist + (kDnHist + i)];
-    if (one_buffer) return in[(size_t)t * B + i];
-    const unsigned nb = (unsigned)i / (unsigned)B, s = (unsigned)i - nb * (unsigned)B;
-    return in[((size_t)nb * T + t) * B + s];
-}
 
 // The gate of one bin, the header's five lines: every operation rounded once, one fused multiply-add where it is written.
 __device__ __forceinline__ cf dn_gate(float re, float im, float& m, float thr, float inv, float floor, float att,
                                       float rel) {
-    const float P = __fmul_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)), inv);
+    const float P = stft::power(re, im, inv);
     const float tg = P > thr ? 1.0f : floor;              // strict; a NaN P compares false
     const float c = tg > m ? att : rel;
     m = __fmaf_rn(c, __fsub_rn(m, tg), tg);
@@ -83,13 +65,13 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
                                                      const float* __restrict__ wa, const float* __restrict__ ws,
                                                      const cf* __restrict__ tw, int T, int B, int n_buffers, int H,
                                                      int first_end, int frames, float inv_edge, float inv_mid) {
-    __shared__ cf lds[4 * kDnImg];
-    __shared__ float rings[4 * 2 * kDnN];
+    __shared__ cf lds[4 * stft::kImg];
+    __shared__ float rings[4 * 2 * stft::kN];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    cf* const img = lds + w * kDnImg;
-    float* const ra = rings + w * 2 * kDnN;
-    float* const rb = ra + kDnN;
+    cf* const img = lds + w * stft::kImg;
+    float* const ra = rings + w * 2 * stft::kN;
+    float* const rb = ra + stft::kN;
     const int q = (int)blockIdx.x * 4 + w;
     const int ta = 2 * q, tb = 2 * q + 1;
     if (ta >= T) return;                                   // whole wave; no barriers below
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
     auto emit = [&](int e) {
         const int m = e - c;
         for (int idx = lane; idx < m; idx += 64) {
-            const int s = (base + idx) & (kDnN - 1);
+            const int s = (base + idx) & (stft::kN - 1);
             const int i = c + idx;
             size_t o;
             if (one_buffer) {
@@ -126,26 +108,26 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
             if (hasb) out[o + B] = rb[s];
             rb[s] = 0.0f;
         }
-        base = (base + m) & (kDnN - 1);
+        base = (base + m) & (stft::kN - 1);
         c = e;
-        dn_wave_sync();
+        stft::wave_sync();
     };
 
     // the pair's state and tables of the lane's bins k = lane + 64 r: r < 8, and bin 512 in lane 0
     float ma[9], mb[9], tha[9], thb[9];
-    float* const maska = mask + (size_t)ta * kDnBins;
-    const float* const thra = thr + (size_t)ta * kDnBins;
+    float* const maska = mask + (size_t)ta * stft::kBins;
+    const float* const thra = thr + (size_t)ta * stft::kBins;
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
         const int k = lane + 64 * r;
         ma[r] = mb[r] = 1.0f;
         tha[r] = thb[r] = 0.0f;
-        if (k <= kDnN / 2) {
+        if (k <= stft::kN / 2) {
             ma[r] = maska[k];
             tha[r] = thra[k];
             if (hasb) {
-                mb[r] = maska[kDnBins + k];
-                thb[r] = thra[kDnBins + k];
+                mb[r] = maska[stft::kBins + k];
+                thb[r] = thra[stft::kBins + k];
             }
         }
     }
@@ -153,27 +135,27 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
     const float floora = pa[0], atta = pa[1], rela = pa[2];
     const float floorb = hasb ? pa[3] : 1.0f, attb = hasb ? pa[4] : 0.0f, relb = hasb ? pa[5] : 0.0f;
     float wn[16], g[16];
-    float* const acca = acc + (size_t)ta * kDnN;
+    float* const acca = acc + (size_t)ta * stft::kN;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int n = lane + 64 * r;
         wn[r] = wa[n];
         g[r] = ws[n];
         ra[n] = acca[n];
-        rb[n] = hasb ? acca[kDnN + n] : 0.0f;
+        rb[n] = hasb ? acca[stft::kN + n] : 0.0f;
     }
-    dn_wave_sync();
+    stft::wave_sync();
     for (int f = 0; f < frames; ++f) {
         const int end = first_end + f * H;
         emit(end);                                         // the ring's front is now the frame's first output sample
         // ---- analysis (spectrum_kernel): gather, window, transform, unpack ----
-        const int start = end - kDnN;
+        const int start = end - stft::kN;
         cf z[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int n = lane + 64 * r;
-            const float sa = dn_sample(in, hist, T, B, one_buffer, ta, start + n);
-            const float sb = hasb ? dn_sample(in, hist, T, B, one_buffer, tb, start + n) : 0.0f;
+            const float sa = stft::sample(in, hist, T, B, one_buffer, ta, start + n);
+            const float sb = hasb ? stft::sample(in, hist, T, B, one_buffer, tb, start + n) : 0.0f;
             z[r] = fft::mk(__fmul_rn(wn[r], sa), __fmul_rn(wn[r], sb));
         }
         FWD::run(z, img, t, lane);                         // EXEC is all ones here: every loop above has reconverged
@@ -188,8 +170,8 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
             const int k = lane + 64 * r;
             xa[r] = fft::mk(0.0f, 0.0f);
             xb[r] = fft::mk(0.0f, 0.0f);
-            if (k <= kDnN / 2) {
-                const cf zp = fft::conj(img[fft::Pad<16>::at((kDnN - k) & (kDnN - 1))]);
+            if (k <= stft::kN / 2) {
+                const cf zp = fft::conj(img[fft::Pad<16>::at((stft::kN - k) & (stft::kN - 1))]);
                 const cf s = fft::cadd(z[r], zp), d = fft::csub(z[r], zp);
                 xa[r] = fft::mk(0.5f * s.x, 0.5f * s.y);
                 xb[r] = fft::mk(0.5f * d.y, -0.5f * d.x);
@@ -199,69 +181,69 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
 #pragma unroll
         for (int r = 0; r < 9; ++r) {
             const int k = lane + 64 * r;
-            const float inv = (k == 0 || k == kDnN / 2) ? inv_edge : inv_mid;
-            if (k <= kDnN / 2) {
+            const float inv = (k == 0 || k == stft::kN / 2) ? inv_edge : inv_mid;
+            if (k <= stft::kN / 2) {
                 xa[r] = dn_gate(xa[r].x, xa[r].y, ma[r], tha[r], inv, floora, atta, rela);
                 if (hasb) xb[r] = dn_gate(xb[r].x, xb[r].y, mb[r], thb[r], inv, floorb, attb, relb);
                 else xb[r] = fft::mk(0.0f, 0.0f);
             }
         }
-        dn_wave_sync();                                    // every lane has read its partners: the image is free
+        stft::wave_sync();                                    // every lane has read its partners: the image is free
 #pragma unroll
         for (int r = 0; r < 9; ++r) {
             const int k = lane + 64 * r;
-            if (k <= kDnN / 2) {
+            if (k <= stft::kN / 2) {
                 img[k] = xa[r];
-                img[kDnImgB + k] = xb[r];
+                img[stft::kImgB + k] = xb[r];
             }
         }
-        dn_wave_sync();
+        stft::wave_sync();
         // ---- synthesis (resynthesis_kernel): Z[k] = Xa[k] + i Xb[k] (k <= 512), conj(Xa[N - k]) + i conj(Xb[N - k])
         // (k > 512); the imaginary parts of bins 0 and 512 are read as zero ----
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int k = lane + 64 * r;
-            const bool mirror = k > kDnN / 2;
+            const bool mirror = k > stft::kN / 2;
             cf a, b;
             if (r < 8) {
                 a = xa[r];
                 b = xb[r];
             } else {
-                const int kk = mirror ? kDnN - k : k;      // (r = 8, lane 0: bin 512, the lane's own)
+                const int kk = mirror ? stft::kN - k : k;      // (r = 8, lane 0: bin 512, the lane's own)
                 a = img[kk];
-                b = img[kDnImgB + kk];
+                b = img[stft::kImgB + kk];
             }
-            if (k == 0 || k == kDnN / 2) {
+            if (k == 0 || k == stft::kN / 2) {
                 a.y = 0.0f;
                 b.y = 0.0f;
             }
             z[r] = mirror ? fft::mk(__fadd_rn(a.x, b.y), __fsub_rn(b.x, a.y))
                           : fft::mk(__fsub_rn(a.x, b.y), __fadd_rn(a.y, b.x));
         }
-        dn_wave_sync();                                    // every lane has its mirrored bins: the image is free again
+        stft::wave_sync();                                    // every lane has its mirrored bins: the image is free again
         INV::run(z, img, t, lane);                         // EXEC is all ones here too
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int s = (base + lane + 64 * r) & (kDnN - 1);
+            const int s = (base + lane + 64 * r) & (stft::kN - 1);
             ra[s] = __fadd_rn(ra[s], __fmul_rn(g[r], __fmul_rn(z[r].x, 0x1p-10f)));
             rb[s] = __fadd_rn(rb[s], __fmul_rn(g[r], __fmul_rn(z[r].y, 0x1p-10f)));
         }
-        dn_wave_sync();
+        stft::wave_sync();
     }
     emit(L);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int n = lane + 64 * r;
-        const int s = (base + n) & (kDnN - 1);
+        const int s = (base + n) & (stft::kN - 1);
         acca[n] = ra[s];
-        if (hasb) acca[kDnN + n] = rb[s];
+        if (hasb) acca[stft::kN + n] = rb[s];
     }
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
         const int k = lane + 64 * r;
-        if (k <= kDnN / 2) {
+        if (k <= stft::kN / 2) {
             maska[k] = ma[r];
-            if (hasb) maska[kDnBins + k] = mb[r];
+            if (hasb) maska[stft::kBins + k] = mb[r];
         }
     }
     // hist becomes the last 1023 samples of hist ++ the call's n B samples.  Only this wave reads or writes its pair's
@@ -271,19 +253,19 @@ __global__ __launch_bounds__(256, 2) void denoise_kernel(const float* __restrict
     for (int r = 0; r < 16; ++r) {
         const int col = lane + 64 * r;                     // the new row's column: sample L - 1023 + col of the call
         va[r] = vb[r] = 0.0f;
-        if (col < kDnHist) {
-            va[r] = dn_sample(in, hist, T, B, one_buffer, ta, L - kDnHist + col);
-            if (hasb) vb[r] = dn_sample(in, hist, T, B, one_buffer, tb, L - kDnHist + col);
+        if (col < stft::kHist) {
+            va[r] = stft::sample(in, hist, T, B, one_buffer, ta, L - stft::kHist + col);
+            if (hasb) vb[r] = stft::sample(in, hist, T, B, one_buffer, tb, L - stft::kHist + col);
         }
     }
     __builtin_amdgcn_s_waitcnt(0);                         // vmcnt(0): every load above has returned
-    dn_wave_sync();
+    stft::wave_sync();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int col = lane + 64 * r;
-        if (col < kDnHist) {
-            hist[(size_t)ta * kDnHist + col] = va[r];
-            if (hasb) hist[(size_t)tb * kDnHist + col] = vb[r];
+        if (col < stft::kHist) {
+            hist[(size_t)ta * stft::kHist + col] = va[r];
+            if (hasb) hist[(size_t)tb * stft::kHist + col] = vb[r];
         }
     }
 }
@@ -293,12 +275,12 @@ __global__ __launch_bounds__(256) void denoise_rows_kernel(const float2* rin, fl
                                                           const float* __restrict__ thr,
                                                           const float* __restrict__ params, int T, int frames,
                                                           float inv_edge, float inv_mid) {
-    const size_t per_frame = (size_t)T * kDnBins;
+    const size_t per_frame = (size_t)T * stft::kBins;
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= per_frame) return;
-    const size_t t = i / kDnBins;
-    const int k = (int)(i - t * kDnBins);
-    const float inv = (k == 0 || k == kDnN / 2) ? inv_edge : inv_mid;
+    const size_t t = i / stft::kBins;
+    const int k = (int)(i - t * stft::kBins);
+    const float inv = stft::inv_of(k, inv_edge, inv_mid);
     const float floor = params[t * kDnFields], att = params[t * kDnFields + 1], rel = params[t * kDnFields + 2];
     const float th = thr[i];
     float m = mask[i];
@@ -314,8 +296,8 @@ __global__ __launch_bounds__(256) void denoise_rows_kernel(const float2* rin, fl
 struct DenoiseThrRule {
     __device__ bool refuses(const float* src, size_t i) const { return !(src[i] >= 0.0f); }
     std::string refusal(unsigned i, int first_track) const {
-        return "track " + std::to_string(first_track + (int)(i / kDnBins)) + " bin " + std::to_string((int)(i % kDnBins)) +
-               " (threshold) must be >= 0 or +inf, not a NaN; the plan keeps its thresholds";
+        return "track " + std::to_string(first_track + (int)(i / stft::kBins)) + " bin " +
+               std::to_string((int)(i % stft::kBins)) + " (threshold) must be >= 0 or +inf, not a NaN; the plan keeps its thresholds";
     }
 };
 
@@ -335,16 +317,6 @@ struct DenoiseParamRule {
     }
 };
 
-// src: [1024]; synthesis says which of the two windows it is
-struct DenoiseWindowRule {
-    int synthesis;
-    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
-    std::string refusal(unsigned i, int) const {
-        return std::string(synthesis ? "synthesis" : "analysis") + " window value " + std::to_string(i) +
-               " is not finite; the plan keeps its windows";
-    }
-};
-
 }  // namespace
 }  // namespace gab
 
@@ -361,14 +333,6 @@ struct gab_dn_plan {
     gab::DeviceBuf<float> thr;         // [T][513]
     gab::DeviceBuf<float> params;      // [T][3]
     gab::DeviceBuf<unsigned> flag;
-
-    // frames of a call of n buffers from the plan's position
-    long long count(int n_buffers) const { return ((long long)phase + (long long)n_buffers * bufsize) / hop; }
-    // S = sum of the analysis window in float64, ascending n; the two factors of a power (the spectrum plan's)
-    void scale(double S) {
-        inv_edge = (float)(1.0 / (S * S));
-        inv_mid = (float)(4.0 / (S * S));
-    }
 };
 
 namespace gab {
@@ -381,24 +345,23 @@ void dn_open_mask(gab_dn_plan* p, hipStream_t s) {
 
 // n buffers in one launch on s, from the plan's position; nothing is allocated, nothing waits.
 int dn_launch(gab_dn_plan* p, const float* d_in, float* d_out, int n_buffers, hipStream_t s, const char* who) {
-    const long long L = (long long)n_buffers * p->bufsize;
-    if (L > 0x7fffffffLL - kDnN) return refuse(who, "n_buffers * bufsize must be below 2^31 - 1024");
-    if (overlaps(d_in, d_out, (size_t)L * (size_t)p->tracks)) return refuse(who, "d_in and d_out overlap");
-    const long long frames = p->count(n_buffers);
+    if (int rc = stft::check_length(who, *p, n_buffers)) return rc;
+    if (overlaps(d_in, d_out, (size_t)n_buffers * p->bufsize * p->tracks)) return refuse(who, "d_in and d_out overlap");
+    const long long frames = stft::count(*p, n_buffers);
     const unsigned groups = (unsigned)(((p->tracks + 1) / 2 + 3) / 4);
     denoise_kernel<<<dim3(groups), 256, 0, s>>>(d_in, d_out, p->hist.get(), p->acc.get(), p->mask.get(), p->thr.get(),
                                                 p->params.get(), p->analysis.get(), p->synthesis.get(), p->tw, p->tracks,
-                                                p->bufsize, n_buffers, p->hop, p->hop - p->phase, (int)frames,
+                                                p->bufsize, n_buffers, p->hop, stft::first_end(*p), (int)frames,
                                                 p->inv_edge, p->inv_mid);
     if (int rc = launch_status("denoise_kernel")) return rc;
-    p->phase = (int)(((long long)p->phase + L) % p->hop);
+    stft::advance(*p, n_buffers);
     return GAB_OK;
 }
 
 int dn_set_thresholds(gab_dn_plan* p, const float* d_thr, int first_track, int n_tracks, const char* who, hipStream_t s) {
-    const size_t n = (size_t)n_tracks * kDnBins;
+    const size_t n = (size_t)n_tracks * stft::kBins;
     return check_then(p->flag, s, who, d_thr, n, DenoiseThrRule{}, first_track, [&] {
-        GAB_HIP_CHECK(hipMemcpyAsync(p->thr.get() + (size_t)first_track * kDnBins, d_thr, n * sizeof(float),
+        GAB_HIP_CHECK(hipMemcpyAsync(p->thr.get() + (size_t)first_track * stft::kBins, d_thr, n * sizeof(float),
                                      hipMemcpyDeviceToDevice, s));
         GAB_HIP_CHECK(hipStreamSynchronize(s));
     });
@@ -420,25 +383,25 @@ extern "C" {
 
 int gab_dn_create(gab_dn_plan** out, int tracks, int bufsize, int hop) {
     return gab::create_entry("gab_dn_create", out, tracks, bufsize, [&] {
-        if (hop < gab::kDnMinHop || hop > gab::kDnN) return gab::bad_arg("gab_dn_create: hop must be 32..1024");
+        if (int rc = gab::stft::check_hop("gab_dn_create", hop)) return rc;
         if (tracks > gab::kDnMaxTracks)
             return gab::bad_arg("gab_dn_create: more than 2^23 workgroups (tracks / 8) in one launch");
         return GAB_OK;
     }, [&](gab_dn_plan& p) {
         p.hop = hop;
         p.tw = gab::fft::device_twiddles();
-        p.analysis.alloc(gab::kDnN);
-        p.synthesis.alloc(gab::kDnN);
-        p.hist.alloc((size_t)tracks * gab::kDnHist);
-        p.acc.alloc((size_t)tracks * gab::kDnN);
-        p.mask.alloc((size_t)tracks * gab::kDnBins);
-        p.thr.alloc((size_t)tracks * gab::kDnBins);
+        p.analysis.alloc(gab::stft::kN);
+        p.synthesis.alloc(gab::stft::kN);
+        p.hist.alloc((size_t)tracks * gab::stft::kHist);
+        p.acc.alloc((size_t)tracks * gab::stft::kN);
+        p.mask.alloc((size_t)tracks * gab::stft::kBins);
+        p.thr.alloc((size_t)tracks * gab::stft::kBins);
         p.params.alloc((size_t)tracks * gab::kDnFields);
         p.flag.alloc(1);
         // the spectrum plan's periodic Hann window and the resynthesis plan's dual of it at this hop; thresholds of
         // zero under {floor, att, rel} = {1, 0, 0}: transparent
         const std::vector<float> w = gab::stft_hann(), g = gab::stft_hann_dual(hop);
-        p.scale(gab::stft_window_sum(w));
+        gab::stft::scale(p, gab::stft_window_sum(w));
         std::vector<float> rows((size_t)tracks * gab::kDnFields, 0.0f);
         for (int t = 0; t < tracks; ++t) rows[(size_t)t * gab::kDnFields] = 1.0f;
         GAB_HIP_CHECK(hipMemcpy(p.analysis.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -471,13 +434,13 @@ int gab_dn_set_windows(gab_dn_plan* plan, const float* d_analysis, const float* 
     const char* const who = "gab_dn_set_windows";
     return gab::entry(who, {plan, d_analysis, d_synthesis}, [&]() -> int {
         hipStream_t s = gab::as_stream(stream);
-        const size_t bytes = gab::kDnN * sizeof(float);
+        const size_t bytes = gab::stft::kN * sizeof(float);
         int rc_synthesis = GAB_OK;
         bool zero_sum = false;
-        const int rc = gab::check_then(plan->flag, s, who, d_analysis, (size_t)gab::kDnN, gab::DenoiseWindowRule{0}, 0, [&] {
-            rc_synthesis = gab::check_then(plan->flag, s, who, d_synthesis, (size_t)gab::kDnN,
-                                           gab::DenoiseWindowRule{1}, 0, [&] {
-                std::vector<float> w(gab::kDnN);
+        const int rc = gab::check_then(plan->flag, s, who, d_analysis, (size_t)gab::stft::kN, gab::stft::WindowRule{1}, 0, [&] {
+            rc_synthesis = gab::check_then(plan->flag, s, who, d_synthesis, (size_t)gab::stft::kN,
+                                           gab::stft::WindowRule{2}, 0, [&] {
+                std::vector<float> w(gab::stft::kN);
                 GAB_HIP_CHECK(hipMemcpyAsync(w.data(), d_analysis, bytes, hipMemcpyDeviceToHost, s));
                 GAB_HIP_CHECK(hipStreamSynchronize(s));
                 const double S = gab::stft_window_sum(w);
@@ -485,7 +448,7 @@ int gab_dn_set_windows(gab_dn_plan* plan, const float* d_analysis, const float* 
                 GAB_HIP_CHECK(hipMemcpyAsync(plan->analysis.get(), d_analysis, bytes, hipMemcpyDeviceToDevice, s));
                 GAB_HIP_CHECK(hipMemcpyAsync(plan->synthesis.get(), d_synthesis, bytes, hipMemcpyDeviceToDevice, s));
                 GAB_HIP_CHECK(hipStreamSynchronize(s));
-                plan->scale(S);
+                gab::stft::scale(*plan, S);
             });
         });
         if (rc) return rc;
@@ -525,7 +488,7 @@ int gab_dn_process_rows(gab_dn_plan* plan, const float* d_rows_in, float* d_rows
         const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_rows_in), o0 = reinterpret_cast<uintptr_t>(d_rows_out);
         if (i0 & 7u) return gab::refuse(who, "d_rows_in must lie on an 8-byte boundary");
         if (o0 & 7u) return gab::refuse(who, "d_rows_out must lie on an 8-byte boundary");
-        const size_t per_frame = (size_t)plan->tracks * gab::kDnBins;
+        const size_t per_frame = (size_t)plan->tracks * gab::stft::kBins;
         const uintptr_t bytes = (uintptr_t)n_frames * per_frame * 2 * sizeof(float);
         if (i0 != o0 && i0 < o0 + bytes && o0 < i0 + bytes)
             return gab::refuse(who, "d_rows_in and d_rows_out overlap in part; they are the same rows or apart");
@@ -557,7 +520,7 @@ int gab_dn_tables(gab_dn_plan* plan, float** d_thr, float** d_params) {
 
 int gab_dn_latency(gab_dn_plan* plan, int* samples) {
     return gab::entry("gab_dn_latency", {plan, samples}, [&] {
-        *samples = gab::kDnN;
+        *samples = gab::stft::kN;
         return GAB_OK;
     });
 }

@@ -13,7 +13,7 @@
 //                        Z = Xa + i Xb; gab_fft.hpp's wave-held inverse runs through the wave's image; real and
 //                        imaginary part are scaled, windowed and added into the ring, one __fadd_rn per slot.  Behind
 //                        the last frame the rest of the call's samples go out and the ring is written back from its base.
-//   ResynRule            refuses a window value that is not finite (gab_plan.hpp's check kernel).
+// The packing, the ring and the window rule are gab_stft.hpp's, which the denoise plan shares.
 //
 // A slot's bits are the ordered float32 sum of the header: they depend on the frames' u, on g and on that order, not on
 // bufsize, on the cut into calls or batches, on the alignment of d_out or on which frames share a launch.  No atomics, no
@@ -35,18 +35,7 @@ namespace {
 
 using fft::cf;
 
-constexpr int kResynN = 1024;                             // the transform, and the floats of a track's accumulator
-constexpr int kResynBins = kResynN / 2 + 1;               // 513
-constexpr int kResynMinHop = 32;
-constexpr int kResynImg = fft::Pad<16>::size(kResynN);    // cf entries of a wave's LDS image
 constexpr int kResynMaxTracks = 1 << 26;                  // 2^23 workgroups of eight tracks: 2^31 threads
-
-// The lanes of a wave hand ring slots to one another (a slot's lane moves with the base): LDS instructions of a wave
-// execute in order, and this keeps the compiler from moving them across the hand-over.
-__device__ __forceinline__ void resyn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // Grid: x = group of four pairs.  rows: [frames][T][513] complex, only read.  acc: [T][1024]: acc[i] is the partial
 // sum of the output sample i places behind the plan's position: on entry the call's first sample, on return the one
@@ -56,119 +45,58 @@ __global__ __launch_bounds__(256) void resynthesis_kernel(const float2* __restri
                                                          const float* __restrict__ window, float* __restrict__ out,
                                                          const cf* __restrict__ tw, int T, int B, int n_buffers, int H,
                                                          int first_end, int frames) {
-    __shared__ cf lds[4 * kResynImg];
-    __shared__ float rings[4 * 2 * kResynN];
+    __shared__ cf lds[4 * stft::kImg];
+    __shared__ float rings[4 * 2 * stft::kN];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    cf* const img = lds + w * kResynImg;
-    float* const ra = rings + w * 2 * kResynN;
-    float* const rb = ra + kResynN;
+    cf* const img = lds + w * stft::kImg;
+    float* const ra = rings + w * 2 * stft::kN;
     const int q = (int)blockIdx.x * 4 + w;
     const int ta = 2 * q;
     if (ta >= T) return;                                   // whole wave; no barriers below
     const bool hasb = ta + 1 < T;
-    const bool one_buffer = n_buffers == 1;
-    const int L = n_buffers * B;                           // (the host holds it below 2^31 - 1024)
 
     using WF = fft::WaveFFT1024<true>;
     WF::Twiddles t;
     WF::load_twiddles(t, tw, lane);
-    int base = 0;                                          // the ring slot of the oldest sample that is not out yet
-    int c = 0;                                             // samples of the call that are out
-
-    // Samples [c, e) of the call (e - c <= 1024, wave-uniform) from the ring's front to d_out; their slots become zero
-    // by a store, so whatever they held (a NaN too) is gone.
-    auto emit = [&](int e) {
-        const int m = e - c;
-        for (int idx = lane; idx < m; idx += 64) {
-            const int s = (base + idx) & (kResynN - 1);
-            const int i = c + idx;
-            size_t o;
-            if (one_buffer) {
-                o = (size_t)ta * B + i;
-            } else {
-                const unsigned nb = (unsigned)i / (unsigned)B, sb = (unsigned)i - nb * (unsigned)B;
-                o = ((size_t)nb * T + ta) * B + sb;
-            }
-            out[o] = ra[s];
-            ra[s] = 0.0f;
-            if (hasb) out[o + B] = rb[s];
-            rb[s] = 0.0f;
-        }
-        base = (base + m) & (kResynN - 1);
-        c = e;
-        resyn_wave_sync();
-    };
+    stft::Ring ring{ra, ra + stft::kN, out, T, B, ta, lane, n_buffers == 1, hasb};
 
     // The pair's two rows of a frame are requested a frame ahead (frame 0's here, in front of the ring's fill) and wanted
     // last: the loads fly while the transform before them runs and the finished samples go out.  Lane l, register r: bin
-    // k = l + 64 r, for k > 512 bin N - k (conjugated below).
+    // k = l + 64 r, for k > 512 bin N - k (stft::pack conjugates it).
     float2 xa[16], xb[16];
     auto request = [&](int f) {
-        const float2* const rowa = rows + ((size_t)f * T + ta) * kResynBins;
-        const float2* const rowb = rowa + kResynBins;
+        const float2* const rowa = rows + ((size_t)f * T + ta) * stft::kBins;
+        const float2* const rowb = rowa + stft::kBins;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int k = lane + 64 * r;
-            const int kk = k > kResynN / 2 ? kResynN - k : k;
+            const int kk = k > stft::kN / 2 ? stft::kN - k : k;
             xa[r] = rowa[kk];
             xb[r] = hasb ? rowb[kk] : make_float2(0.0f, 0.0f);
         }
     };
     if (frames > 0) request(0);
     float g[16];
-    float* const acca = acc + (size_t)ta * kResynN;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int n = lane + 64 * r;
-        g[r] = window[n];
-        ra[n] = acca[n];
-        rb[n] = hasb ? acca[kResynN + n] : 0.0f;
-    }
-    resyn_wave_sync();
+    for (int r = 0; r < 16; ++r) g[r] = window[lane + 64 * r];
+    float* const acca = acc + (size_t)ta * stft::kN;
+    ring.fill(acca);
+    stft::wave_sync();
     for (int f = 0; f < frames; ++f) {
-        emit(first_end + f * H);                           // the ring's front is now the frame's first sample
-        // Z[k] = Xa[k] + i Xb[k] (k <= 512), conj(Xa[N - k]) + i conj(Xb[N - k]) (k > 512); the imaginary parts of bins
-        // 0 and 512 are read as zero
+        ring.emit(first_end + f * H);                      // the ring's front is now the frame's first sample
         cf z[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int k = lane + 64 * r;
-            const bool mirror = k > kResynN / 2;
-            if (k == 0 || k == kResynN / 2) {
-                xa[r].y = 0.0f;
-                xb[r].y = 0.0f;
-            }
-            z[r] = mirror ? fft::mk(__fadd_rn(xa[r].x, xb[r].y), __fsub_rn(xb[r].x, xa[r].y))
-                          : fft::mk(__fsub_rn(xa[r].x, xb[r].y), __fadd_rn(xa[r].y, xb[r].x));
-        }
+        for (int r = 0; r < 16; ++r)
+            z[r] = stft::pack(fft::mk(xa[r].x, xa[r].y), fft::mk(xb[r].x, xb[r].y), lane + 64 * r);
         if (f + 1 < frames) request(f + 1);
         WF::run(z, img, t, lane);                          // EXEC is all ones here: every loop above has reconverged
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int s = (base + lane + 64 * r) & (kResynN - 1);
-            ra[s] = __fadd_rn(ra[s], __fmul_rn(g[r], __fmul_rn(z[r].x, 0x1p-10f)));
-            rb[s] = __fadd_rn(rb[s], __fmul_rn(g[r], __fmul_rn(z[r].y, 0x1p-10f)));
-        }
-        resyn_wave_sync();
+        ring.add(z, g);
+        stft::wave_sync();
     }
-    emit(L);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int n = lane + 64 * r;
-        const int s = (base + n) & (kResynN - 1);
-        acca[n] = ra[s];
-        if (hasb) acca[kResynN + n] = rb[s];
-    }
+    ring.emit(n_buffers * B);                              // (the host holds it below 2^31 - 1024)
+    ring.store(acca);
 }
-
-// src: [1024]
-struct ResynRule {
-    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
-    std::string refusal(unsigned i, int) const {
-        return "window value " + std::to_string(i) + " is not finite; the plan keeps its window";
-    }
-};
 
 }  // namespace
 }  // namespace gab
@@ -180,9 +108,6 @@ struct gab_resyn_plan {
     gab::DeviceBuf<float> window;      // [1024]
     gab::DeviceBuf<float> acc;         // [T][1024]
     gab::DeviceBuf<unsigned> flag;
-
-    // frames of a call of n buffers from the plan's position
-    long long count(int n_buffers) const { return ((long long)phase + (long long)n_buffers * bufsize) / hop; }
 };
 
 namespace gab {
@@ -191,22 +116,21 @@ namespace {
 // n buffers in one launch on s, from the plan's position; nothing is allocated, nothing waits.  *n_frames: host.
 int resyn_launch(gab_resyn_plan* p, const float* d_rows, float* d_out, int n_buffers, int* n_frames, hipStream_t s,
                  const char* who) {
-    const long long L = (long long)n_buffers * p->bufsize;
-    if (L > 0x7fffffffLL - kResynN) return refuse(who, "n_buffers * bufsize must be below 2^31 - 1024");
+    if (int rc = stft::check_length(who, *p, n_buffers)) return rc;
     if (reinterpret_cast<uintptr_t>(d_rows) & 7u) return refuse(who, "d_rows must lie on an 8-byte boundary");
-    const long long frames = p->count(n_buffers);
+    const long long frames = stft::count(*p, n_buffers);
     if (frames > 0) {
         const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rows), o0 = reinterpret_cast<uintptr_t>(d_out);
-        const uintptr_t rbytes = (uintptr_t)frames * (uintptr_t)p->tracks * kResynBins * 2 * sizeof(float);
-        const uintptr_t obytes = (uintptr_t)L * (uintptr_t)p->tracks * sizeof(float);
+        const uintptr_t rbytes = (uintptr_t)frames * (uintptr_t)p->tracks * stft::kBins * 2 * sizeof(float);
+        const uintptr_t obytes = (uintptr_t)n_buffers * p->bufsize * p->tracks * sizeof(float);
         if (r0 < o0 + obytes && o0 < r0 + rbytes) return refuse(who, "d_rows and d_out overlap");
     }
     const unsigned groups = (unsigned)(((p->tracks + 1) / 2 + 3) / 4);
     resynthesis_kernel<<<dim3(groups), 256, 0, s>>>(reinterpret_cast<const float2*>(d_rows), p->acc.get(),
                                                     p->window.get(), d_out, p->tw, p->tracks, p->bufsize, n_buffers,
-                                                    p->hop, p->hop - p->phase, (int)frames);
+                                                    p->hop, stft::first_end(*p), (int)frames);
     if (int rc = launch_status("resynthesis_kernel")) return rc;
-    p->phase = (int)(((long long)p->phase + L) % p->hop);
+    stft::advance(*p, n_buffers);
     *n_frames = (int)frames;
     return GAB_OK;
 }
@@ -218,15 +142,15 @@ extern "C" {
 
 int gab_resyn_create(gab_resyn_plan** out, int tracks, int bufsize, int hop) {
     return gab::create_entry("gab_resyn_create", out, tracks, bufsize, [&] {
-        if (hop < gab::kResynMinHop || hop > gab::kResynN) return gab::bad_arg("gab_resyn_create: hop must be 32..1024");
+        if (int rc = gab::stft::check_hop("gab_resyn_create", hop)) return rc;
         if (tracks > gab::kResynMaxTracks)
             return gab::bad_arg("gab_resyn_create: more than 2^23 workgroups (tracks / 8) in one launch");
         return GAB_OK;
     }, [&](gab_resyn_plan& p) {
         p.hop = hop;
         p.tw = gab::fft::device_twiddles();
-        p.window.alloc(gab::kResynN);
-        p.acc.alloc((size_t)tracks * gab::kResynN);
+        p.window.alloc(gab::stft::kN);
+        p.acc.alloc((size_t)tracks * gab::stft::kN);
         p.flag.alloc(1);
         const std::vector<float> g = gab::stft_hann_dual(hop);  // of the spectrum plan's periodic Hann window
         GAB_HIP_CHECK(hipMemcpy(p.window.get(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -243,8 +167,8 @@ int gab_resyn_set_window(gab_resyn_plan* plan, const float* d_window, gab_stream
     return gab::set_entry("gab_resyn_set_window",
                           [&](gab_resyn_plan* p, const float* d_src, int, int, const char* who) -> int {
         hipStream_t s = gab::as_stream(stream);
-        return gab::check_then(p->flag, s, who, d_src, (size_t)gab::kResynN, gab::ResynRule{}, 0, [&] {
-            GAB_HIP_CHECK(hipMemcpyAsync(p->window.get(), d_src, gab::kResynN * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return gab::check_then(p->flag, s, who, d_src, (size_t)gab::stft::kN, gab::stft::WindowRule{0}, 0, [&] {
+            GAB_HIP_CHECK(hipMemcpyAsync(p->window.get(), d_src, gab::stft::kN * sizeof(float), hipMemcpyDeviceToDevice, s));
             GAB_HIP_CHECK(hipStreamSynchronize(s));
         });
     }, plan, d_window, true, 0, 0);
@@ -273,18 +197,14 @@ int gab_resyn_process_batch(gab_resyn_plan* plan, const float* d_rows, float* d_
 }
 
 int gab_resyn_frames(gab_resyn_plan* plan, int n_buffers, int* capacity) {
-    return gab::batch_entry("gab_resyn_frames", {plan, capacity}, n_buffers, [&]() -> int {
-        const long long L = (long long)n_buffers * plan->bufsize;
-        const long long cap = (L + plan->hop - 1) / plan->hop;
-        if (cap > 0x7fffffffLL) return gab::refuse("gab_resyn_frames", "n_buffers * bufsize is too large");
-        *capacity = (int)cap;
-        return GAB_OK;
+    return gab::batch_entry("gab_resyn_frames", {plan, capacity}, n_buffers, [&] {
+        return gab::stft::capacity("gab_resyn_frames", *plan, n_buffers, capacity);
     });
 }
 
 int gab_resyn_count(gab_resyn_plan* plan, int n_buffers, int* frames) {
     return gab::batch_entry("gab_resyn_count", {plan, frames}, n_buffers, [&]() -> int {
-        const long long n = plan->count(n_buffers);
+        const long long n = gab::stft::count(*plan, n_buffers);
         if (n > 0x7fffffffLL) return gab::refuse("gab_resyn_count", "n_buffers * bufsize is too large");
         *frames = (int)n;
         return GAB_OK;
@@ -302,7 +222,7 @@ int gab_resyn_state(gab_resyn_plan* plan, float** d_acc, float** d_window, int* 
 
 int gab_resyn_latency(gab_resyn_plan* plan, int* samples) {
     return gab::entry("gab_resyn_latency", {plan, samples}, [&] {
-        *samples = gab::kResynN;
+        *samples = gab::stft::kN;
         return GAB_OK;
     });
 }

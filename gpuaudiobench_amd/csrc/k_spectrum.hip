@@ -12,7 +12,8 @@
 //                           wave's LDS image, lane b adding band b in order) the bands.
 //   spectrum_hist_kernel    behind it on the same stream: a wave per track forms the last 1023 samples of
 //                           history ++ call in registers and writes them only after every lane has read.
-//   SpectrumRule            refuses a window value that is not finite (gab_plan.hpp's check kernel).
+// The gather, the transform and the unpack, the power of a bin, the history update and the window rule are gab_stft.hpp's,
+// which the denoise plan shares.
 //
 // A frame's bits depend on its pair's 1024 windowed samples (and, for powers, on the window's sum) and on nothing else:
 // not on bufsize, the hop, the cut into calls, the alignment of d_in or the other frames of the launch.  Every frame
@@ -35,23 +36,9 @@ namespace {
 
 using fft::cf;
 
-constexpr int kSpecN = 1024;                              // the transform
-constexpr int kSpecBins = kSpecN / 2 + 1;                 // 513
-constexpr int kSpecHist = kSpecN - 1;                     // samples carried per track
 constexpr int kSpecMaxBands = 64;                         // a lane per band
-constexpr int kSpecMinHop = 32;
-constexpr int kSpecImg = fft::Pad<16>::size(kSpecN);      // cf entries of a wave's LDS image
 constexpr unsigned kSpecMaxBlocks = 1u << 23;             // workgroups of one launch: 2^31 threads
 enum { kSpecComplex = 0, kSpecBinsMode = 1, kSpecBandsMode = 2 };
-
-// Sample i (relative to the call's first sample; -1023 <= i < n_buffers B) of track t.
-__device__ __forceinline__ float spec_sample(const float* __restrict__ in, const float* __restrict__ hist, int T, int B,
-                                             bool one_buffer, int t, int i) {
-    if (i < 0) return hist[(size_t)t * kSpecHist + (kSpecHist + i)];
-    if (one_buffer) return in[(size_t)t * B + i];
-    const unsigned nb = (unsigned)i / (unsigned)B, s = (unsigned)i - nb * (unsigned)B;
-    return in[((size_t)nb * T + t) * B + s];
-}
 
 // Grid: x = (group of four pairs) * frames + frame.  in: [n][T][B], only read.  hist: [T][1023], only read.  window:
 // [1024].  Frame f ends `first_end + f H` samples behind the call's first (1 <= first_end; the last end <= n B).
@@ -62,77 +49,51 @@ __global__ __launch_bounds__(256) void spectrum_kernel(const float* __restrict__
                                                       float* __restrict__ rows, const cf* __restrict__ tw, int T, int B,
                                                       int n_buffers, int H, int first_end, int frames, int bands,
                                                       float inv_edge, float inv_mid) {
-    __shared__ cf lds[4 * kSpecImg];
+    __shared__ cf lds[4 * stft::kImg];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    cf* const img = lds + w * kSpecImg;
+    cf* const img = lds + w * stft::kImg;
     const int f = (int)(blockIdx.x % (unsigned)frames);
     const int q = (int)(blockIdx.x / (unsigned)frames) * 4 + w;
-    const int ta = 2 * q, tb = 2 * q + 1;
+    const int ta = 2 * q;
     if (ta >= T) return;                                   // whole wave; no barriers below
-    const bool hasb = tb < T;
-    const bool one_buffer = n_buffers == 1;
-    const int start = first_end + f * H - kSpecN;          // of the frame, relative to the call's first sample
+    const bool hasb = ta + 1 < T;
+    const int start = first_end + f * H - stft::kN;        // of the frame, relative to the call's first sample
 
     using WF = fft::WaveFFT1024<false>;
     WF::Twiddles t;
     WF::load_twiddles(t, tw, lane);
-    cf z[16];
+    float wn[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int n = lane + 64 * r;
-        const float wn = window[n];
-        const float xa = spec_sample(in, hist, T, B, one_buffer, ta, start + n);
-        const float xb = hasb ? spec_sample(in, hist, T, B, one_buffer, tb, start + n) : 0.0f;
-        z[r] = fft::mk(__fmul_rn(wn, xa), __fmul_rn(wn, xb));
-    }
-    WF::run(z, img, t, lane);
-    // partner Z[(N - k) mod N], k = lane + 64 r: bins 0..512 are r < 8 plus (r = 8, lane 0)
-    const unsigned rb = (unsigned)lane + ((unsigned)lane >> 4);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) img[rb + 68 * r] = z[r];
-    __builtin_amdgcn_wave_barrier();
+    for (int r = 0; r < 16; ++r) wn[r] = window[lane + 64 * r];
     cf xa[9], xb[9];
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        const int k = lane + 64 * r;
-        xa[r] = fft::mk(0.0f, 0.0f);
-        xb[r] = fft::mk(0.0f, 0.0f);
-        if (k <= kSpecN / 2) {
-            const cf zp = fft::conj(img[fft::Pad<16>::at((kSpecN - k) & (kSpecN - 1))]);
-            const cf s = fft::cadd(z[r], zp), d = fft::csub(z[r], zp);
-            xa[r] = fft::mk(0.5f * s.x, 0.5f * s.y);
-            xb[r] = fft::mk(0.5f * d.y, -0.5f * d.x);
-        }
-    }
+    stft::analyse(in, hist, T, B, n_buffers == 1, ta, hasb, start, wn, img, t, lane, xa, xb);
     if constexpr (MODE == kSpecComplex) {
-        float2* const oa = reinterpret_cast<float2*>(rows) + ((size_t)f * T + ta) * kSpecBins;
-        float2* const ob = oa + kSpecBins;
+        float2* const oa = reinterpret_cast<float2*>(rows) + ((size_t)f * T + ta) * stft::kBins;
+        float2* const ob = oa + stft::kBins;
 #pragma unroll
         for (int r = 0; r < 9; ++r) {
             const int k = lane + 64 * r;
-            if (k <= kSpecN / 2) {
+            if (k <= stft::kN / 2) {
                 oa[k] = make_float2(xa[r].x, xa[r].y);
                 if (hasb) ob[k] = make_float2(xb[r].x, xb[r].y);
             }
         }
     } else {
-        // P[k] = (re re + im im) inv_k, every operation rounded once
         float pa[9], pb[9];
 #pragma unroll
         for (int r = 0; r < 9; ++r) {
-            const int k = lane + 64 * r;
-            const float inv = (k == 0 || k == kSpecN / 2) ? inv_edge : inv_mid;
-            pa[r] = __fmul_rn(__fadd_rn(__fmul_rn(xa[r].x, xa[r].x), __fmul_rn(xa[r].y, xa[r].y)), inv);
-            pb[r] = __fmul_rn(__fadd_rn(__fmul_rn(xb[r].x, xb[r].x), __fmul_rn(xb[r].y, xb[r].y)), inv);
+            const float inv = stft::inv_of(lane + 64 * r, inv_edge, inv_mid);
+            pa[r] = stft::power(xa[r].x, xa[r].y, inv);
+            pb[r] = stft::power(xb[r].x, xb[r].y, inv);
         }
         if constexpr (MODE == kSpecBinsMode) {
-            float* const oa = rows + ((size_t)f * T + ta) * kSpecBins;
-            float* const ob = oa + kSpecBins;
+            float* const oa = rows + ((size_t)f * T + ta) * stft::kBins;
+            float* const ob = oa + stft::kBins;
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
                 const int k = lane + 64 * r;
-                if (k <= kSpecN / 2) {
+                if (k <= stft::kN / 2) {
                     oa[k] = pa[r];
                     if (hasb) ob[k] = pb[r];
                 }
@@ -140,16 +101,14 @@ __global__ __launch_bounds__(256) void spectrum_kernel(const float* __restrict__
         } else {
             // the powers through the wave's image (every lane has read its partners), then lane b adds band b in order
             float* const pw = reinterpret_cast<float*>(img);          // [2][576]
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            stft::wave_sync();
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
                 const int k = lane + 64 * r;
                 pw[k] = pa[r];
                 pw[576 + k] = pb[r];
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            stft::wave_sync();
             if (lane < bands) {
                 const int e0 = edges[lane], e1 = edges[lane + 1];
                 float sa = 0.0f, sb = 0.0f;
@@ -171,35 +130,11 @@ __global__ __launch_bounds__(256) void spectrum_hist_kernel(const float* __restr
                                                            int n_buffers) {
     const int lane = threadIdx.x & 63;
     const int t = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    const long long L = (long long)n_buffers * B;
-    const bool one_buffer = n_buffers == 1;
     float v[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int c = lane + 64 * r;                       // the new row's column: sample L - 1023 + c of the call
-        v[r] = 0.0f;
-        if (t < T && c < kSpecHist) {
-            const long long i = L - kSpecHist + c;
-            v[r] = spec_sample(in, hist, T, B, one_buffer, t, (int)i);
-        }
-    }
+    stft::hist_read(v, in, hist, T, B, n_buffers == 1, t, t < T, n_buffers * B, lane);   // (n B < 2^31 - 1024: the host)
     __syncthreads();
-    if (t < T) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = lane + 64 * r;
-            if (c < kSpecHist) hist[(size_t)t * kSpecHist + c] = v[r];
-        }
-    }
+    if (t < T) stft::hist_write(v, hist, t, lane);
 }
-
-// src: [1024]
-struct SpectrumRule {
-    __device__ bool refuses(const float* src, size_t i) const { return not_finite(__float_as_uint(src[i])); }
-    std::string refusal(unsigned i, int) const {
-        return "window value " + std::to_string(i) + " is not finite; the plan keeps its window";
-    }
-};
 
 }  // namespace
 }  // namespace gab
@@ -215,25 +150,17 @@ struct gab_spec_plan {
     gab::DeviceBuf<unsigned> flag;
 
     int width() const {
-        return mode == GAB_SPEC_COMPLEX ? 2 * gab::kSpecBins : bands ? bands : gab::kSpecBins;
+        return mode == GAB_SPEC_COMPLEX ? 2 * gab::stft::kBins : bands ? bands : gab::stft::kBins;
     }
-    // frames of a call of n buffers from the plan's position
-    long long count(int n_buffers) const { return ((long long)phase + (long long)n_buffers * bufsize) / hop; }
 };
 
 namespace gab {
 namespace {
 
-// S = sum of w in float64, ascending n; the two factors of a power
-void spectrum_scale(gab_spec_plan* p, double S) {
-    p->inv_edge = (float)(1.0 / (S * S));
-    p->inv_mid = (float)(4.0 / (S * S));
-}
-
 // The edge rule: 0 <= e_0 < e_1 < ... < e_bands <= 513.  The first value that breaks it, or -1.
 int spectrum_bad_edge(const int* e, int bands) {
     for (int b = 0; b <= bands; ++b) {
-        if (e[b] < 0 || e[b] > kSpecBins) return b;
+        if (e[b] < 0 || e[b] > stft::kBins) return b;
         if (b > 0 && e[b] <= e[b - 1]) return b;
     }
     return -1;
@@ -243,15 +170,14 @@ int spectrum_bad_edge(const int* e, int bands) {
 // nothing waits.  *n_frames: host.
 int spectrum_launch(gab_spec_plan* p, const float* d_in, float* d_rows, int n_buffers, int* n_frames, hipStream_t s,
                     const char* who) {
-    const long long L = (long long)n_buffers * p->bufsize;
-    if (L > 0x7fffffffLL - kSpecN) return refuse(who, "n_buffers * bufsize must be below 2^31 - 1024");
-    const long long frames = p->count(n_buffers);
+    if (int rc = stft::check_length(who, *p, n_buffers)) return rc;
+    const long long frames = stft::count(*p, n_buffers);
     const long long groups = ((p->tracks + 1) / 2 + 3) / 4;
     if (frames * groups > (long long)kSpecMaxBlocks)
         return refuse(who, "more than 2^23 workgroups (frames x tracks / 8) in one call");
     if (frames > 0) {
         const dim3 grid((unsigned)(frames * groups));
-        const int first_end = p->hop - p->phase;
+        const int first_end = stft::first_end(*p);
 #define GAB_SPEC(MM)                                                                                                   \
     spectrum_kernel<MM><<<grid, 256, 0, s>>>(d_in, p->hist.get(), p->window.get(), p->edges.get(), d_rows, p->tw,        \
                                              p->tracks, p->bufsize, n_buffers, p->hop, first_end, (int)frames,           \
@@ -265,7 +191,7 @@ int spectrum_launch(gab_spec_plan* p, const float* d_in, float* d_rows, int n_bu
     spectrum_hist_kernel<<<dim3((unsigned)((p->tracks + 3) / 4)), 256, 0, s>>>(d_in, p->hist.get(), p->tracks,
                                                                               p->bufsize, n_buffers);
     if (int rc = launch_status("spectrum_hist_kernel")) return rc;
-    p->phase = (int)(((long long)p->phase + L) % p->hop);
+    stft::advance(*p, n_buffers);
     *n_frames = (int)frames;
     return GAB_OK;
 }
@@ -277,7 +203,7 @@ extern "C" {
 
 int gab_spec_create(gab_spec_plan** out, int tracks, int bufsize, int hop, int mode, int bands) {
     return gab::create_entry("gab_spec_create", out, tracks, bufsize, [&] {
-        if (hop < gab::kSpecMinHop || hop > gab::kSpecN) return gab::bad_arg("gab_spec_create: hop must be 32..1024");
+        if (int rc = gab::stft::check_hop("gab_spec_create", hop)) return rc;
         if (mode != GAB_SPEC_COMPLEX && mode != GAB_SPEC_POWER)
             return gab::bad_arg("gab_spec_create: mode must be GAB_SPEC_COMPLEX or GAB_SPEC_POWER");
         if (bands < 0 || bands > gab::kSpecMaxBands) return gab::bad_arg("gab_spec_create: bands must be 0..64");
@@ -287,15 +213,15 @@ int gab_spec_create(gab_spec_plan** out, int tracks, int bufsize, int hop, int m
     }, [&](gab_spec_plan& p) {
         p.hop = hop; p.mode = mode; p.bands = bands;
         p.tw = gab::fft::device_twiddles();
-        p.window.alloc(gab::kSpecN);
-        p.hist.alloc((size_t)tracks * gab::kSpecHist);
+        p.window.alloc(gab::stft::kN);
+        p.hist.alloc((size_t)tracks * gab::stft::kHist);
         p.edges.alloc(gab::kSpecMaxBands + 1);
         p.flag.alloc(1);
         // the periodic Hann window, float64, rounded once; S added in ascending n over the rounded values
         const std::vector<float> w = gab::stft_hann();
-        gab::spectrum_scale(&p, gab::stft_window_sum(w));
+        gab::stft::scale(p, gab::stft_window_sum(w));
         int e[gab::kSpecMaxBands + 1] = {0};
-        for (int b = 0; b <= bands; ++b) e[b] = bands ? (int)((long long)gab::kSpecBins * b / bands) : 0;
+        for (int b = 0; b <= bands; ++b) e[b] = bands ? (int)((long long)gab::stft::kBins * b / bands) : 0;
         GAB_HIP_CHECK(hipMemcpy(p.window.get(), w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
         GAB_HIP_CHECK(hipMemcpy(p.edges.get(), e, sizeof(e), hipMemcpyHostToDevice));
         GAB_HIP_CHECK(hipMemset(p.hist.get(), 0, p.hist.size() * sizeof(float)));
@@ -313,16 +239,15 @@ int gab_spec_set_window(gab_spec_plan* plan, const float* d_window, gab_stream_t
                           [&](gab_spec_plan* p, const float* d_src, int, int, const char* who) -> int {
         hipStream_t s = gab::as_stream(stream);
         bool zero_sum = false;
-        const int rc = gab::check_then(p->flag, s, who, d_src, (size_t)gab::kSpecN, gab::SpectrumRule{}, 0, [&] {
-            std::vector<float> w(gab::kSpecN);
+        const int rc = gab::check_then(p->flag, s, who, d_src, (size_t)gab::stft::kN, gab::stft::WindowRule{0}, 0, [&] {
+            std::vector<float> w(gab::stft::kN);
             GAB_HIP_CHECK(hipMemcpyAsync(w.data(), d_src, w.size() * sizeof(float), hipMemcpyDeviceToHost, s));
             GAB_HIP_CHECK(hipStreamSynchronize(s));
-            double S = 0.0;
-            for (int n = 0; n < gab::kSpecN; ++n) S += (double)w[(size_t)n];
+            const double S = gab::stft_window_sum(w);
             if (S == 0.0) { zero_sum = true; return; }
             GAB_HIP_CHECK(hipMemcpyAsync(p->window.get(), d_src, w.size() * sizeof(float), hipMemcpyDeviceToDevice, s));
             GAB_HIP_CHECK(hipStreamSynchronize(s));
-            gab::spectrum_scale(p, S);
+            gab::stft::scale(*p, S);
         });
         if (rc) return rc;
         if (zero_sum) return gab::refuse(who, "the window's sum is zero; the plan keeps its window");
@@ -368,12 +293,8 @@ int gab_spec_process_batch(gab_spec_plan* plan, const float* d_in, float* d_rows
 }
 
 int gab_spec_frames(gab_spec_plan* plan, int n_buffers, int* capacity) {
-    return gab::batch_entry("gab_spec_frames", {plan, capacity}, n_buffers, [&]() -> int {
-        const long long L = (long long)n_buffers * plan->bufsize;
-        const long long cap = (L + plan->hop - 1) / plan->hop;
-        if (cap > 0x7fffffffLL) return gab::refuse("gab_spec_frames", "n_buffers * bufsize is too large");
-        *capacity = (int)cap;
-        return GAB_OK;
+    return gab::batch_entry("gab_spec_frames", {plan, capacity}, n_buffers, [&] {
+        return gab::stft::capacity("gab_spec_frames", *plan, n_buffers, capacity);
     });
 }
 

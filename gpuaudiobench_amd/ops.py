@@ -1293,7 +1293,40 @@ def spectrum_band_edges(bands, fs=48000.0, fmin=20.0, fmax=None):
     return e
 
 
-class SpectrumPlan(_TrackPlan):
+class _StftPlan(_TrackPlan):
+    """What the short-time Fourier plans (spectrum, resynthesis, denoise) share: frames of N samples, rows of BINS
+    complex bins, on the grid of `hop` samples since the reset."""
+
+    N = 1024
+    BINS = 513
+
+    def _create(self, tracks, bufsize, hop, *rest):
+        self.hop = hop
+        super()._create(tracks, bufsize, hop, *rest)
+
+    @staticmethod
+    def counts(bufsize, hop, first_buffer, n):
+        """The frame counts of buffers first_buffer .. first_buffer + n - 1 since a reset: host integers, no GPU."""
+        lo = [(k * bufsize) // hop for k in range(first_buffer, first_buffer + n + 1)]
+        return [b - a for a, b in zip(lo, lo[1:])]
+
+    def _streams_out(self):
+        """Of the plans that write a stream: its `latency`, and what a call that takes no frame points at."""
+        c = C.c_int(0)
+        check(self._fn("latency")(self._h, C.byref(c)))
+        self.latency = c.value                              # samples
+        self._none = torch.zeros(2, dtype=torch.float32, device="cuda")
+
+    def _refuse_moving_grid(self):
+        """prepare() only where hop divides bufsize: the frame phase and the count are launch arguments, constant there
+        (phase 0, bufsize / hop frames a call) and nowhere else."""
+        if self.bufsize % self.hop:
+            raise ValueError("%s.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
+                             "frame count change from call to call and a prepared or captured call would repeat one "
+                             "of them" % (type(self).__name__, self.hop, self.bufsize))
+
+
+class SpectrumPlan(_StftPlan):
     """gab_spec_plan: a short-time Fourier analyser per track.  Frames of 1024 samples every `hop` samples of the
     stream (the last 1023 samples are carried), under a window (a new plan: periodic Hann), as complex bins
     (mode="complex": rows [frames][tracks][513][2]), as powers per bin (mode="power": [frames][tracks][513]; a sine of
@@ -1301,22 +1334,14 @@ class SpectrumPlan(_TrackPlan):
     frames that end inside it, possibly none; `counts` says how many without a GPU."""
 
     _destroy = "gab_spec_destroy"
-    N = 1024
-    BINS = 513
     MODES = {"complex": 0, "power": 1}
 
     def __init__(self, tracks, bufsize, hop=512, mode="power", bands=0):
         if mode not in self.MODES:
             raise ValueError("mode must be 'complex' or 'power'")
-        self.hop, self.mode, self.bands = hop, mode, bands
+        self.mode, self.bands = mode, bands
         self._create(tracks, bufsize, hop, self.MODES[mode], bands)
         self.row_shape = (self.BINS, 2) if mode == "complex" else (bands or self.BINS,)
-
-    @staticmethod
-    def counts(bufsize, hop, first_buffer, n):
-        """The frame counts of buffers first_buffer .. first_buffer + n - 1 since a reset: host integers, no GPU."""
-        lo = [(k * bufsize) // hop for k in range(first_buffer, first_buffer + n + 1)]
-        return [b - a for a, b in zip(lo, lo[1:])]
 
     def frames(self, n_buffers=1):
         """The largest frame count a call of n_buffers buffers can return: the rows an `out` must hold."""
@@ -1378,10 +1403,7 @@ class SpectrumPlan(_TrackPlan):
         """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
         `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
         there (phase 0, bufsize / hop frames a call) and nowhere else."""
-        if self.bufsize % self.hop:
-            raise ValueError("SpectrumPlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
-                             "frame count change from call to call and a prepared or captured call would repeat one "
-                             "of them" % (self.hop, self.bufsize))
+        self._refuse_moving_grid()
         assert out.numel() >= self.frames(1) * self.tracks * torch.Size(self.row_shape).numel()
         self._n = C.c_int(0)
         return (self._h, _dev(x), _dev(out), C.byref(self._n), _stream(stream))
@@ -1412,7 +1434,7 @@ def synthesis_window(w, hop):
     return g.to(torch.float32).to(device)
 
 
-class ResynthesisPlan(_TrackPlan):
+class ResynthesisPlan(_StftPlan):
     """gab_resyn_plan: the overlap-add inverse of SpectrumPlan(mode="complex").  Rows [frames][tracks][513][2] become
     the stream again: every frame is inverse-transformed, multiplied by the synthesis window (a new plan: the dual of
     the periodic Hann window at `hop`, see synthesis_window) and added on the hop grid in a fixed order; the 1024 samples
@@ -1421,17 +1443,10 @@ class ResynthesisPlan(_TrackPlan):
     same bufsize and hop emits for the same call, possibly none; `counts` says how many without a GPU."""
 
     _destroy = "gab_resyn_destroy"
-    N = 1024
-    BINS = 513
-    counts = staticmethod(SpectrumPlan.counts)
 
     def __init__(self, tracks, bufsize, hop=512):
-        self.hop = hop
         self._create(tracks, bufsize, hop)
-        c = C.c_int(0)
-        check(lib.gab_resyn_latency(self._h, C.byref(c)))
-        self.latency = c.value                              # samples
-        self._none = torch.zeros(2, dtype=torch.float32, device="cuda")     # what a call that takes no frame points at
+        self._streams_out()
 
     def frames(self, n_buffers=1):
         """The largest frame count a call of n_buffers buffers can take."""
@@ -1493,10 +1508,7 @@ class ResynthesisPlan(_TrackPlan):
         """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
         `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
         there (phase 0, bufsize / hop frames a call) and nowhere else."""
-        if self.bufsize % self.hop:
-            raise ValueError("ResynthesisPlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
-                             "frame count change from call to call and a prepared or captured call would repeat one "
-                             "of them" % (self.hop, self.bufsize))
+        self._refuse_moving_grid()
         assert rows.numel() == (self.bufsize // self.hop) * self.tracks * self.BINS * 2
         assert out.numel() == self.tracks * self.bufsize
         self._n = C.c_int(0)
@@ -1536,7 +1548,7 @@ def denoise_thresholds(power_rows, sensitivity_db=6.0):
     return torch.from_numpy(thr).to(power_rows.device) if is_tensor else thr
 
 
-class DenoisePlan(_TrackPlan):
+class DenoisePlan(_StftPlan):
     """gab_dn_plan: a spectral noise gate per (track, bin) with a smoothed gain.  process / process_batch take the stream
     and return it gated and delayed by `latency` = 1024 samples in ONE launch: SpectrumPlan(mode="complex")'s analysis,
     the gate, ResynthesisPlan's overlap-add, bit for bit that composition.  process_rows is the gate alone, complex rows
@@ -1545,18 +1557,11 @@ class DenoisePlan(_TrackPlan):
     (denoise_params).  A new plan is transparent."""
 
     _destroy = "gab_dn_destroy"
-    N = 1024
-    BINS = 513
     FIELDS = ("floor", "att", "rel")
-    counts = staticmethod(SpectrumPlan.counts)
 
     def __init__(self, tracks, bufsize, hop=256):
-        self.hop = hop
         self._create(tracks, bufsize, hop)
-        c = C.c_int(0)
-        check(lib.gab_dn_latency(self._h, C.byref(c)))
-        self.latency = c.value                              # samples
-        self._none = torch.zeros(2, dtype=torch.float32, device="cuda")     # what a call of no frame points at
+        self._streams_out()
 
     def reset(self):
         """Zero history and accumulator, a mask of ones, position 0; the tables and the windows stay."""
@@ -1620,10 +1625,7 @@ class DenoisePlan(_TrackPlan):
         """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
         `launch(args)`.  Only where hop divides bufsize: the frame phase and the count are launch arguments, constant
         there (phase 0, bufsize / hop frames a call) and nowhere else."""
-        if self.bufsize % self.hop:
-            raise ValueError("DenoisePlan.prepare: hop %d does not divide bufsize %d, so the frame phase and the "
-                             "frame count change from call to call and a prepared or captured call would repeat one "
-                             "of them" % (self.hop, self.bufsize))
+        self._refuse_moving_grid()
         assert x.numel() == out.numel() == self.tracks * self.bufsize
         return (self._h, _dev(x), _dev(out), _stream(stream))
 

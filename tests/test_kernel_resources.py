@@ -64,3 +64,10 @@ def test_headline_kernels_keep_their_occupancy(resources):
         assert r["occupancy"] >= 3 and r["vgprs"] <= 168 and r["lds"] <= 160 * 1024, (name, r)
     assert one("17conv_batch_kernel")["vgprs"] <= 208                        # the looped body is the single-buffer launch's
     assert one("keep_warm_kernel")["vgprs"] <= 16                            # eight idle waves must fit beside anything but the engine
+    for name in ("denoise_kernel", "resynthesis_kernel"):                  # an image and a ring a wave: two workgroups a compute unit
+        r = one(name)
+        assert r["occupancy"] >= 2 and r["lds"] <= 67584, (name, r)
+    spectrum = {k: v for k, v in resources.items() if "spectrum_kernel" in k}
+    assert len(spectrum) == 3, sorted(spectrum)                              # complex, bins, bands: an image a wave, four workgroups a unit
+    for name, r in spectrum.items():
+        assert r["occupancy"] >= 4 and r["lds"] == 34816, (name, r)
