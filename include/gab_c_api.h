@@ -698,8 +698,8 @@ int gab_eq_form(const gab_eq_plan* plan, int* samples_per_lane, int* segments);
  * from (bufsize, buses) alone — never from tracks, the layout, the device or the batch length — and gab_mix_form
  * reports them: a plan's bits are the same on every box, and one restatement of the three steps above, given those two
  * integers, is the kernel's bits for every shape.
- * tracks >= 1, bufsize >= 1, 1 <= buses <= 64; arguments are checked before any device call.  One thread at a time
- * per plan.                                                                                                          */
+ * tracks >= 1, bufsize >= 1, 1 <= buses <= 64, and ceil(tracks / 256) * ceil(bufsize / 64), the workgroups one buffer
+ * takes, below 2^31; arguments are checked before any device call.  One thread at a time per plan.                  */
 typedef struct gab_mix_plan gab_mix_plan;
 #define GAB_MIX_TRACK_MAJOR  0   /* d_in [t*B + s]: what gab_eq_process, gab_gain, gab_iir write */
 #define GAB_MIX_SAMPLE_MAJOR 1   /* d_in [T*s + t]: what gab_conv_process writes                 */

@@ -16,6 +16,8 @@ float32 against float64 on the four sets of splits.
 
 The kernels' own times, in a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/crossover_bench.py --launches 50 --out /dev/null
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

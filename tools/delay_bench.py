@@ -11,6 +11,8 @@ as a fraction of 8 TB/s, and the aim for a and b: twice gain's time plus a quart
     python tools/delay_bench.py [--launches 200] [--tracks 8192,65536]
 
 The kernels' own times, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/delay_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

@@ -15,6 +15,8 @@ In front of the timings: the accuracy ratios of tests/test_denoise_gpu.py (the f
 chain over the float32 twin chain's own, per pair, where no decision can flip).
 
     python tools/denoise_bench.py [--launches 100] [--tracks 8192,65536] [--out profiles/r27_denoise.txt]
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

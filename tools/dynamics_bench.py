@@ -11,6 +11,8 @@ buffer.  The plan moves 8 T B bytes per buffer (x in, y out), 12 T B with a key;
 
 The kernels' own times, in a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/dynamics_bench.py --launches 50 --out /dev/null
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

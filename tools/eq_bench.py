@@ -7,6 +7,8 @@ of each after a warm-up, the two alternated in the same process.  Beside the tim
     python tools/eq_bench.py [--launches 200] [--tracks 128,1024,8192,65536] [--sections 1,2,4,8,16]
 
 The kernel's own time, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/eq_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import ctypes as C

@@ -16,6 +16,8 @@ rows of one track count, printed below each group.
 
 The kernels' own times, in a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/gate_bench.py --launches 50 --out /dev/null
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

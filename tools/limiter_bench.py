@@ -15,6 +15,8 @@ The margin of both is the spread of gab_gain's own median over the rows of one t
 
 The kernels' own times, in a run of its own:
     rocprofv3 --kernel-trace --stats -- python tools/limiter_bench.py --launches 50 --out /dev/null
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

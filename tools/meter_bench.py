@@ -10,6 +10,8 @@ are reported, the calls alternated.  process_batch(--batch, 32) is timed the sam
     python tools/meter_bench.py [--launches 200] [--tracks 8192,65536] [--windows 1,38]
 
 The kernels' own times, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/meter_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import ctypes as C

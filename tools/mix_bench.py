@@ -11,6 +11,8 @@ lies (out[B x M] = X^T G), so neither side pays for a transpose.
     python tools/mix_bench.py [--launches 200] [--tracks 1024,8192,65536] [--buses 2,16,64]
 
 The kernels' own times, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/mix_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

@@ -10,6 +10,8 @@ position moves from launch to launch as it does in a stream, so a median is over
     python tools/resample_bench.py [--launches 200] [--tracks 8192,65536]
 
 The kernels' own times, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/resample_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

@@ -17,6 +17,8 @@ In front of the timings: the accuracy ratio of tests/test_resynthesis_gpu.py, th
 max_n |u - u64| / (peak_t + peak_p) over the twin's (tests/resynthesis_twin.py) on the same rows.
 
     python tools/resynthesis_bench.py [--launches 200] [--tracks 8192,65536] [--out profiles/r26_resynthesis.txt]
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

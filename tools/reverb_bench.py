@@ -12,6 +12,8 @@ because the traffic is N line rows per track rather than one stream.  Met or mis
     python tools/reverb_bench.py [--launches 200] [--out profiles/r15_reverb.txt]
 
 The kernels' own times, in a run of its own:  rocprofv3 --kernel-trace --stats -- python tools/reverb_bench.py --launches 50
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os

@@ -18,6 +18,8 @@ In front of the timings: the accuracy ratio of tests/test_spectrum_gpu.py, the k
 max_k |X - X64| / (peak_t + peak_p) over the twin's (tests/spectrum_twin.py) on the same Hann frames.
 
     python tools/spectrum_bench.py [--launches 200] [--tracks 8192,65536] [--out profiles/r22_spectrum.txt]
+
+The outputs at these shapes: tests/test_scale_gpu.py::test_bench_shape (bits, against per-buffer calls and a shard).
 """
 import argparse
 import os
