@@ -282,6 +282,18 @@ PROTOTYPES = {
     "gab_dn_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
     "gab_dn_tables": (_I, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "gab_dn_latency": (_I, [_P, C.POINTER(_I)]),
+    "gab_sat_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I]),
+    "gab_sat_destroy": (_I, [_P]),
+    "gab_sat_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "gab_sat_set_params": (_I, [_P, _P, _I, _P]),
+    "gab_sat_set_params_tracks": (_I, [_P, _P, _I, _I, _I, _P]),
+    "gab_sat_set_taps": (_I, [_P, _P, _P, _P]),
+    "gab_sat_reset": (_I, [_P, _P]),
+    "gab_sat_process": (_I, [_P, _P, _P, _P]),
+    "gab_sat_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_sat_apply": (_I, [_P, _P, _P, _I, _P]),
+    "gab_sat_params": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)]),
+    "gab_sat_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

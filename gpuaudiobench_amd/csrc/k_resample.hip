@@ -26,11 +26,12 @@
 #include <vector>
 
 #include "gab_plan.hpp"
+#include "gab_resample_design.hpp"    // resample_design: the header's taps, shared with the saturator plan
 
 namespace gab {
 namespace {
 
-constexpr int kRsTracks = 64;             // tracks of a workgroup: the lanes of a wave
+constexpr int kRsTracks = 64;            // tracks of a workgroup: the lanes of a wave
 constexpr int kRsChunk = 64;              // input samples of a chunk
 constexpr int kRsBatch = 64;              // outputs turned through the output tile at once
 constexpr int kRsOutPitch = 65;           // floats: a lane per row writes, a lane per column reads, both over all banks
@@ -186,31 +187,6 @@ struct gab_resample_plan {
 
 namespace gab {
 namespace {
-
-// The header's taps: float64, each phase divided by its sum (added in ascending j), rounded once.
-std::vector<float> resample_design(int L, int M, int K) {
-    const double pi = 3.14159265358979323846;
-    const double ratio = (double)L / (double)M;
-    const double c = 0.94 * (ratio < 1.0 ? ratio : 1.0);
-    const double half = (double)(K / 2);
-    std::vector<float> taps((size_t)L * K);
-    std::vector<double> h((size_t)K);
-    for (int p = 0; p < L; ++p) {
-        double sum = 0.0;
-        for (int j = 0; j < K; ++j) {
-            const double d = (double)(j - K / 2) + (double)p / (double)L;
-            const double u = d / half;
-            const double x = c * d;
-            const double s = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
-            const double wnd = 0.35875 + 0.48829 * std::cos(pi * u) + 0.14128 * std::cos(2.0 * pi * u) +
-                               0.01168 * std::cos(3.0 * pi * u);
-            h[(size_t)j] = s * wnd;
-            sum += h[(size_t)j];
-        }
-        for (int j = 0; j < K; ++j) taps[(size_t)p * K + j] = (float)(h[(size_t)j] / sum);
-    }
-    return taps;
-}
 
 // n buffers in one launch, from the plan's position; nothing is allocated, nothing waits.  counts: [n], host.
 int resample_launch(gab_resample_plan* p, const float* d_in, float* d_out, int n_buffers, int* counts, hipStream_t s) {

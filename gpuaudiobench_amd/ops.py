@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1032,7 +1032,118 @@ class LimiterPlan(_TrackPlan):
     launch = _launcher("gab_lim_process")
 
 
-_REVERB_SPREAD = 4.65     # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)
+def saturator_params(drive_db=0.0, bias=0.0, level_db=0.0, compensate=False):
+    """A row (all arguments scalars) or a table [n][3] float32 of SaturatorPlan parameters {drive, bias, level} from the
+    knobs of a saturator; float64, rounded once.  Levels go from dB to linear; compensate=True divides level by drive,
+    so that a signal below the curve's knee keeps its level whatever the drive."""
+    import numpy as np
+    args = [np.asarray(a, np.float64) for a in (drive_db, bias, level_db)]
+    scalar = all(a.ndim == 0 for a in args)
+    drive_db, bias, level_db = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    drive = 10.0 ** (drive_db / 20.0)
+    level = 10.0 ** (level_db / 20.0)
+    if compensate:
+        level = level / drive
+    table = np.stack([drive, bias, level], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class SaturatorPlan(_TrackPlan):
+    """gab_sat_plan: a waveshaper per track at `oversample` (1, 2, 4 or 8) times the stream's rate, so that the harmonics
+    it makes do not fold back: up by R, the curve ("hard", "cubic" or "rational"), down by R in one launch, bit for bit
+    ResamplePlan(up=R) -> apply -> ResamplePlan(down=R) (gab_c_api.h).  Parameters per track {drive, bias, level}
+    (saturator_params makes them from dB); a new plan holds {1, 0, 1}, and new parameters are ramped in over the next
+    buffer unless ramp=False.  up_taps / down_taps None: ResamplePlan.default_taps, 32 and 32 R (0 and 0 at R = 1).
+    The plan delays by `.latency` = up_taps / 2 + down_taps / (2 R) samples."""
+
+    _destroy = "gab_sat_destroy"
+    FIELDS = ("drive", "bias", "level")
+    CURVES = ("hard", "cubic", "rational")
+
+    def __init__(self, tracks, bufsize, oversample=4, curve="cubic", up_taps=None, down_taps=None):
+        if curve not in self.CURVES:
+            raise ValueError("curve must be one of %s" % (self.CURVES,))
+        if oversample == 1:
+            up_taps, down_taps = up_taps or 0, down_taps or 0
+        elif oversample in (2, 4, 8):
+            up_taps = ResamplePlan.default_taps(oversample, 1) if up_taps is None else up_taps
+            down_taps = ResamplePlan.default_taps(1, oversample) if down_taps is None else down_taps
+        else:
+            up_taps, down_taps = up_taps or 0, down_taps or 0         # the library refuses it with its text
+        self._create(tracks, bufsize, oversample, self.CURVES.index(curve), up_taps, down_taps)
+        v = [C.c_int(0) for _ in range(5)]
+        check(lib.gab_sat_info(self._h, *[C.byref(c) for c in v]))
+        self.oversample, _, self.up_taps, self.down_taps, self.latency = (c.value for c in v)
+        self.curve = curve
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][3], or [n][3] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n = self._rows(table, len(self.FIELDS), first_track)
+        self._set("params", _dev(table), first_track, n, 1 if ramp else 0)
+
+    def set_taps(self, up, down):
+        """up: device tensor [oversample][up_taps], down: [down_taps]; in force from the next buffer, the histories are
+        kept."""
+        assert up.numel() == self.oversample * self.up_taps and down.numel() == self.down_taps
+        check(lib.gab_sat_set_taps(self._h, _dev(up), _dev(down), _stream()))
+
+    def reset(self):
+        """Both histories zero, current := target, a pending ramp dropped; the taps stay."""
+        super().reset()
+
+    def process(self, x, out=None):
+        """One buffer, track-major [tracks*bufsize]; out may not overlap x."""
+        return self._process("process", x, out, 1, None)
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch."""
+        n = _n_buffers(self, xs)
+        return self._process("process_batch", xs, out, n, None, n)
+
+    def apply(self, u, out=None):
+        """The curve alone on oversampled blocks [n][tracks][oversample*bufsize] (what ResamplePlan(up=oversample) gives);
+        out may be u itself.  Takes a pending ramp as process_batch would; touches no history."""
+        n, rest = divmod(u.numel(), self.tracks * self.bufsize * self.oversample)
+        assert rest == 0
+        out = torch.empty_like(u) if out is None else out
+        assert out.numel() == u.numel()
+        check(lib.gab_sat_apply(self._h, _dev(u), _dev(out), n, _stream()))
+        return out
+
+    def params(self):
+        """Copies of (current, target), each [tracks][3]."""
+        return self._tables("params", len(self.FIELDS))
+
+    def _state(self):
+        p = [C.c_void_p() for _ in range(4)]
+        check(lib.gab_sat_state(self._h, *[C.byref(c) for c in p]))
+        return [c.value for c in p]
+
+    def state(self):
+        """Copies of (hist_in [tracks][up_taps-1], hist_os [tracks][down_taps-1]), oldest first; (None, None) at
+        oversample 1."""
+        if self.oversample == 1:
+            return None, None
+        a, b, _, _ = self._state()
+        return _view(a, self.tracks, self.up_taps - 1).clone(), _view(b, self.tracks, self.down_taps - 1).clone()
+
+    def taps(self):
+        """Copies of the tables in force, (up [oversample][up_taps], down [down_taps]); (None, None) at oversample 1."""
+        if self.oversample == 1:
+            return None, None
+        _, _, u, d = self._state()
+        return _view(u, self.oversample, self.up_taps).clone(), _view(d, 1, self.down_taps).clone().view(-1)
+
+    def prepare(self, x, out, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  Capture only with no ramp pending: gab_c_api.h, "Captured calls"."""
+        return (self._h, _dev(x), _dev(out), _stream(stream))
+
+    launch = _launcher("gab_sat_process")
+
+
+_REVERB_SPREAD = 4.65    # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)
 
 
 def _primes_from(lengths):

@@ -567,6 +567,8 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       long as no table holds a -0.0; and a set with ramp = 1 between two replays is ramped in by the
  *                       next replay, as between two plain calls.  The call that was captured also cleared the host's
  *                       flag, as if the ramp had run.
+ *                       The saturator's process, process_batch and apply pick their form by the same flag and behave
+ *                       the same way; capture them with no ramp pending (tests/test_saturator_gpu.py).
  *   mix's ramp_first    the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
  *                       one that takes the ramp form.
  *   meter's decay       a launch argument: set_decay after the capture does not reach the replays.
@@ -1588,6 +1590,87 @@ int gab_dn_process_rows(gab_dn_plan* plan, const float* d_rows_in, float* d_rows
 int gab_dn_state(gab_dn_plan* plan, float** d_hist, float** d_acc, float** d_mask, int* position_mod_hop);
 int gab_dn_tables(gab_dn_plan* plan, float** d_thr, float** d_params);
 int gab_dn_latency(gab_dn_plan* plan, int* samples);
+
+/* ---- saturator: a waveshaper per track between an interpolator by R and a decimator by R, fused (additive; no
+ * counterpart in the reference) ---------------------------------------------------------------------------------------
+ * Drive into a curve colours a signal and, at the stream's own rate, folds the new harmonics back below Nyquist.  The
+ * plan shapes at R times the rate: up by R, the curve, down by R, in one launch.  T = tracks, B = bufsize, R =
+ * oversample in {1, 2, 4, 8}, Ku = up_taps, Kd = down_taps; `curve` is one curve for the plan.
+ *   the contract    On one device, the fused form (process, process_batch) equals
+ *                     gab_resample_* (T, B, up R, down 1, taps Ku) -> gab_sat_apply -> gab_resample_* (T, R B, up 1,
+ *                     down R, taps Kd)
+ *                   BIT FOR BIT: the outputs, d_hist_in against the first resampler's history and d_hist_os against the
+ *                   second's, after every call of any cut.  At R = 1 process is apply.
+ *   rows            [T][GAB_SAT_FIELDS] float32 = {drive, bias, level} per track; a new plan holds {1, 0, 1}.  One rule:
+ *                   every field finite.  set_params (all tracks) and set_params_tracks ([first_track, first_track +
+ *                   n_tracks)) take a device table, checked on the device first: the first refused value is named as
+ *                   (track, field) with GAB_ERR_INVALID_ARG and the plan keeps its parameters.  ramp = 0: in force at
+ *                   once.  ramp = 1: over the next buffer processed, base sample s of that buffer takes, per field,
+ *                     fmaf(target - current, r[s], current),  r[s] = (float)((s + 1) / B)    (float64, rounded once)
+ *                   and all R oversampled samples of base sample s take that row; behind that buffer current := target.
+ *                   In a batch only the first buffer ramps.  Synchronous with respect to `stream`.
+ *   stage 1, up     (R >= 2) w is the track's input stream, zero before the first sample after a reset:
+ *                     u[R i + p] = fmaf(h_p[Ku-1], w[i-Ku+1], ... fmaf(h_p[1], w[i-1], h_p[0] * w[i]))     p = 0..R-1
+ *                   the resample plan's chain with its table for L = R, M = 1 ("taps" above; the one design function).
+ *   stage 2, curve  per oversampled sample, every operation rounded once:
+ *                     a = fmaf(drive, u, bias);   v = level * (S(a) - S(bias))
+ *                   so silence stays silence under a bias.  S is written with comparisons, and a NaN passes through:
+ *                     GAB_SAT_HARD      S(x) = x > 1 ? 1 : (x < -1 ? -1 : x)
+ *                     GAB_SAT_CUBIC     c = HARD(x);  c2 = c * c;  S = c * fmaf(-0.5f, c2, 1.5f)   (+-1 at the rails,
+ *                                       slope 0 there)
+ *                     GAB_SAT_RATIONAL  S(x) = x / (1.0f + fabsf(x))                (the IEEE division, rounded once)
+ *                   No library transcendental anywhere.  At R = 1, u is the input itself.
+ *   stage 3, down   (R >= 2) base output m is the resample plan's chain with its one-row table g for L = 1, M = R:
+ *                     y[m] = fmaf(g[Kd-1], v[m R - Kd + 1], ... fmaf(g[1], v[m R - 1], g[0] * v[m R]))
+ *   latency         Ku / 2 + Kd / (2 R) base samples, the same for every track; 0 at R = 1 (gab_sat_info).
+ *   state           d_hist_in [T][Ku-1]: the last Ku-1 inputs; d_hist_os [T][Kd-1]: the last Kd-1 shaped oversampled
+ *                   samples; both oldest first, zero after create and reset, and right when B < Ku-1 or R B < Kd-1: they
+ *                   are shifted, not replaced.  gab_sat_state exposes both and the two tap tables d_up [R][Ku] and
+ *                   d_down [Kd], the plan's own memory (all four null at R = 1).  reset also makes current := target
+ *                   and drops a pending ramp; the taps stay.
+ *   set_taps        d_up [R][Ku], d_down [Kd], device.  Both are checked on the device before either is written: the first
+ *                   value that is not finite is named as (table, phase, tap) with GAB_ERR_INVALID_ARG and the plan keeps
+ *                   both tables.  The histories are kept; accepted taps are in force from the next buffer.  Refused at
+ *                   R = 1, which has no taps.  Synchronous with respect to `stream`.
+ *   fused form      d_in, d_out [n][T][B] float32, any 4-byte alignment (16-byte loads and stores where both pointers
+ *                   and B allow).  d_out may not overlap d_in (refused): the output is delayed.  One launch on `stream`: a
+ *                   workgroup owns 16 tracks for the whole call, every buffer of a batch included, walks them in chunks
+ *                   of 64 base samples through LDS and is the only reader and writer of their histories: no second
+ *                   launch.  process_batch gives the bits of n process calls.
+ *   curve form      gab_sat_apply: stage 2 alone on d_in, d_out [n_buffers][T][R B] oversampled blocks, base sample s of
+ *                   a row being its samples [R s, R s + R).  d_out may be d_in itself (any other overlap is refused).
+ *                   It consumes a pending ramp exactly as process_batch would and touches no history.
+ *   determinism     Output bits depend on the track's samples, its rows and the taps.  Not on B, on the cut into calls
+ *                   or batches, or on alignment.  A shard of tracks as its own plan gives those tracks' bits.  A NaN or
+ *                   an infinity stays in its track, and is gone from the output once the input that made it has left
+ *                   both windows: Ku - 1 + ceil((Kd - 1) / R) base samples behind it.
+ * Every call allocates nothing and waits for nothing but the sets, and all changing state but the pending flag is on the
+ * device: capture with no ramp pending ("Captured calls", above).  Arguments are checked before any device call, each
+ * refusal with its own text: tracks >= 1, 1 <= bufsize <= 2^20, oversample in {1, 2, 4, 8}, curve in 0..2; at R >= 2
+ * up_taps even and in 4..64, down_taps in 4..256 and a multiple of 2 R (so that the latency is a whole number of
+ * samples); at R = 1 both 0; null pointers, n_buffers >= 1, the track range of a set, the overlaps above.  Fewer than 16
+ * tracks x 256 use a part of the device.  Out of scope: a dry / wet mix (the dry path needs its own delay line: the
+ * delay and mix plans do it), a curve per track, tanh or any transcendental curve, minimum-phase filters, in-place
+ * process.  One thread at a time per plan.                                                                          */
+typedef struct gab_sat_plan gab_sat_plan;
+#define GAB_SAT_FIELDS 3
+#define GAB_SAT_HARD 0
+#define GAB_SAT_CUBIC 1
+#define GAB_SAT_RATIONAL 2
+int gab_sat_create(gab_sat_plan** plan, int tracks, int bufsize, int oversample, int curve, int up_taps,
+                   int down_taps);
+int gab_sat_destroy(gab_sat_plan* plan);
+int gab_sat_info(gab_sat_plan* plan, int* oversample, int* curve, int* up_taps, int* down_taps, int* latency);
+int gab_sat_set_params(gab_sat_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_sat_set_params_tracks(gab_sat_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                              gab_stream_t stream);
+int gab_sat_set_taps(gab_sat_plan* plan, const float* d_up, const float* d_down, gab_stream_t stream);
+int gab_sat_reset(gab_sat_plan* plan, gab_stream_t stream);
+int gab_sat_process(gab_sat_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_sat_process_batch(gab_sat_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_sat_apply(gab_sat_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_sat_params(gab_sat_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_sat_state(gab_sat_plan* plan, float** d_hist_in, float** d_hist_os, float** d_up, float** d_down);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
