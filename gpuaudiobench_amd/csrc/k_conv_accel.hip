@@ -943,17 +943,18 @@ typedef unsigned u4 __attribute__((ext_vector_type(4)));
 //     share the inverse wave forms from the prologue's spectrum (profiles/r19_near_products.txt).
 // The far role's schedule per transform (window nb, periods nb and nb + 1; the other group is one period out of step, so a
 // heavy interval of one meets a light one of the other):
-//   period nb:      pass 0 + write | read, pass 1 | write (+ spectra of bins 0-7) | read, pass 2 | Z exchange write |
-//                   Z exchange read, products by bin pairs, W exchange write
-//   period nb + 1:  (next window's requests) W exchange read, inverse pass 0 | write | read, pass 1 | write | read, last pass (4 of 16), carry out | -
+//   period nb:      pass 0 + write | read, pass 1 | write (+ spectra of bins 0-7) | read, pass 2 | Z trade | products by bin pairs, W trade
+//   period nb + 1:  (next window's requests) inverse pass 0 | write | read, pass 1 | write | read, last pass (4 of 16), carry out | -
 // The far product runs by BIN PAIRS (round 25, profiles/r25_far_pair_product.txt): thread t forms its eight low bins k = t + 256 r
 // and their partners N - k from ONE fetch of pm[k] (load_spectra's rule gives the partner's holder, thread 256 - t, the same entry:
-// every entry of the far spectra was asked for twice per transform).  The operands cross in one 2048-entry region of the group's
-// image (the eight high Z at position k - 2048; Z[N - k] read at 2048 - k), the partners' results in a second one (written at
-// (N - k) - 2048; read by the bin's holder behind the period's closing barrier): both lane-consecutive and unpadded, 4096 of the
-// image's 4352 entries, and the region read in an interval is never written in it.  Thread 0: bin 0 is its own partner; bin 2048 —
-// its own, nobody's partner — takes that place (pm[2048], the branch without conjugation, position 0 of the second region).  The
-// same calls on the same operands as the bins' holders made (spectral_product_partner_part): the same bits.
+// every entry of the far spectra was asked for twice per transform).  The operands Z[N - k] and the partners' results cross between
+// the two 32-lane halves of a wave (round 30, profiles/r30_far_lane_partner.txt): a group's threads are named so that thread
+// 256 - t is lane ^ 32 of thread t's wave, and the eight high registers change places with that lane's, in reverse order, by
+// sixteen v_permlane32_swap_b32 each way (round 25 sent them through two 2048-entry regions of the group's image: sixteen LDS
+// writes and sixteen reads per thread and transform).  Threads 0 and 128 are their own partners (lanes 0 and 32 of the group's
+// first wave: operands and results from and to their own registers, by selects in that wave alone); thread 0: bin 0 is its own
+// partner; bin 2048 — its own, nobody's partner — takes that place (pm[2048], the branch without conjugation).  The same calls on
+// the same operands as the bins' holders made (spectral_product_partner_part): the same bits.
 constexpr int kB12Threads = 768;
 constexpr int kB12SpecCf = 4 * kBinsA * 2;                         // [A pair 0, A pair 1, A2 pair 0, A2 pair 1][513] float4, in cf entries
 constexpr int kB12Tw1Cf = 16 * 15;
@@ -1005,6 +1006,14 @@ __device__ __forceinline__ void near_product_half(cf (&v)[16], const cf* fimg, c
     spectral_product_part<kNA, 16, R0, R1>(v, zp, ch, lane);
 }
 
+// a <- lane ^ 32's b, b <- lane ^ 32's a, in both halves of the wave: two lane-half swaps per dword ((a, b), then (b, a)).
+// EXEC all ones (wave-uniform control flow).
+__device__ __forceinline__ void trade_lane_halves(cf& a, cf& b) {
+    using WF = fft::WaveFFT1024<false>;
+    WF::swap_lane_halves<32>(a, b);
+    WF::swap_lane_halves<32>(b, a);
+}
+
 #ifdef GAB_ABLATE
 // diagnostic bit 64: in periods 32 and 33 of a launch every wave's lane 0 stamps s_memrealtime (100 MHz) when it ARRIVES at each of
 // the six barriers: slot = [block][wave (12)][period - 32][barrier]; tools/stamp_batch12.py
@@ -1049,7 +1058,12 @@ __device__ __forceinline__ void conv_split_batch12_resident(
     if (w >= 4) {
         // ---- far waves: group g turns pair g of the duo, one transform per two periods
         const int g = __builtin_amdgcn_readfirstlane((w - 4) >> 2);
-        const int ft = (tid - kThreads) & (kThreads - 1);
+        // The group's threads by LOGICAL index ft (round 30): wave fw's low lanes are threads 32 fw + j, its high lanes threads
+        // 256 - 32 fw - j (j = lane & 31), so that the holder of a thread's partner bins, thread 256 - ft, is lane ^ 32 of the
+        // same wave.  Threads 0 and 128 are their own partners: lanes 0 and 32 of the group's first wave.  Everything below
+        // (window, twiddles, LDS positions, spectra, carry) goes by ft: only which lane does which thread's work has changed.
+        const int fw = (w - 4) & 3;
+        const int ft = lane < 32 ? 32 * fw + lane : ((fw | (lane & 31)) == 0 ? kThreads / 2 : kThreads - 32 * fw - (lane & 31));
         cf* const img = far_img + g * kLdsHalf;
         const int q = 2 * d + g;
         const cf* const hp = reinterpret_cast<const cf*>(hist) + (size_t)q * kSlots * kB;
@@ -1105,16 +1119,17 @@ __device__ __forceinline__ void conv_split_batch12_resident(
         };
         cf z[16], zn[16];
 #ifdef GAB_ABLATE
-        const bool own_bins = (sp.debug & 128) != 0;                  // diagnostic bit 128: every thread forms its own sixteen bins' products
-#else
-        constexpr bool own_bins = false;
+        const bool own_bins = (sp.debug & 128) != 0;                  // diagnostic bit 128: every thread forms its own sixteen bins' products, partners through LDS
 #endif
         // The requests ride on the lighter steps (every instruction of a step costs the wave about a dozen clocks beside two
         // others on its SIMD: thirty-two requests in one interval made it the period's longest), the wait for the carry's stores
         // stands in the idle interval.  (Measured and not kept, profiles/r06_batch12_stamps.txt: steps cut as read + twiddle |
         // butterfly + write, so that no step is a bare write — 5.08 against 5.01 us per buffer.)
         // first half of a transform (period nb):   pass 0, write | read, twiddle, pass 1 | write (+ spectra of bins 0-7) |
-        //                                          read, twiddle, pass 2 | Z exchange write | Z exchange read, products by bin pairs, W exchange write
+        //                                          read, twiddle, pass 2 | Z trade | products by bin pairs, W trade
+        // The two trades are lane-half swaps within the wave (round 30, profiles/r30_far_lane_partner.txt): nothing of the product
+        // crosses through LDS.  (Measured and not kept, there: both trades beside the products, the interval before them empty —
+        // 4.90-4.95 against the parent's 4.74-4.76 us per buffer; the W trade at the head of the second period — no better.)
         auto first_half = [&](int nb) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = zn[r];
@@ -1189,45 +1204,54 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                 return;
             }
 #endif
-            // Z exchange: the eight HIGH values Z[t + 256 r], r >= 8, at position k - N / 2 of the image's first region (N / 2
-            // entries, lane-consecutive, unpadded)
+            // Z trade.  The thread's own bins back in order; Z[N - k] of its low bins k = t + 256 r is Z[(256 - t) + 256 (15 - r)],
+            // register 15 - r of thread 256 - t: the eight high registers change places with lane ^ 32's, in reverse order
+            cf zp[8], wp[8];
             {
-                const unsigned t = opaque_t();
-#pragma unroll
-                for (int r = 8; r < 16; ++r) img[t + 256u * (r - 8)] = z[B16::out_slot(r)];
-            }
-            GAB_B12BAR(nb, 4);                                          // 5
-            {
-                // the thread's own bins back in order; Z[N - k] of its low bins k = t + 256 r from position N / 2 - k (thread
-                // 0's bin 0 is its own partner; the position wraps to an entry nobody else reads); the low bins' products and
-                // their partners' from the same operands and the same entry of the spectra
                 cf o[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o[r] = z[B16::out_slot(r)];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) z[r] = o[r];            // z[r] = Z[t + 256 r]
-                const unsigned t = opaque_t();
-                const cf* const pb = img + (kNB / 2 - 256 * 7) - t;   // pb[256 (7 - r)] = region 0 [N / 2 - t - 256 r]
-                cf zp[8], wp[8];
-                zp[0] = img[(kNB / 2 - t) & (kNB / 2 - 1)];
-                if (t == 0) zp[0] = z[0];
 #pragma unroll
-                for (int r = 1; r < 8; ++r) zp[r] = pb[256 * (7 - r)];
-                spectral_product_partner_part<kNB, 16, 0, 8>(wp, z, zp, clo);
-                spectral_product_part<kNB, 16, 0, 8>(z, zp, clo, ft);
-                if (t == 0) {                                         // bin N / 2 stands where bin 0's partner would: thread 0's own, nobody's partner
-                    const cf P = mk(cny.x, cny.y), M = mk(cny.z, cny.w);
-                    wp[0] = fft::cfma_cj(z[8], M, fft::cmul(z[8], P));
+                for (int i = 0; i < 4; ++i) {
+                    zp[i] = z[8 + i];
+                    zp[7 - i] = z[15 - i];
+                    trade_lane_halves(zp[i], zp[7 - i]);              // zp[i] = their [15 - i], zp[7 - i] = their [8 + i]
                 }
-                // W exchange: the partners' results at position (N - k) - N / 2 of the second region (bin N / 2 at position 0)
-                cf* const qb = img + kNB / 2 + (kNB / 2 - 256 * 7) - t;
-                img[kNB / 2 + ((kNB / 2 - t) & (kNB / 2 - 1))] = wp[0];
+                if (fw == 0) {
+                    // threads 0 and 128 (lanes 0 and 32 of the first wave) are their own partners: bin 128 + 256 r pairs with own
+                    // register 15 - r; bin 256 r with own register 16 - r, bin 0 with itself (what the two received is dropped)
+                    const bool t0 = lane == 0, t128 = lane == 32;
+                    zp[0] = t0 ? z[0] : t128 ? z[15] : zp[0];
 #pragma unroll
-                for (int r = 1; r < 8; ++r) qb[256 * (7 - r)] = wp[r];
+                    for (int r = 1; r < 8; ++r) zp[r] = t0 ? z[16 - r] : t128 ? z[15 - r] : zp[r];
+                }
             }
-            GAB_B12BAR(nb, 5);                                          // 6
+            GAB_B12BAR(nb, 4);                                          // 5
+            // the low bins' products and their partners' from the same operands and the same entry of the spectra
+            spectral_product_partner_part<kNB, 16, 0, 8>(wp, z, zp, clo);
+            spectral_product_part<kNB, 16, 0, 8>(z, zp, clo, ft);
+            if (ft == 0) {                                            // bin N / 2 stands where bin 0's partner would: thread 0's own, nobody's partner
+                const cf P = mk(cny.x, cny.y), M = mk(cny.z, cny.w);
+                wp[0] = fft::cfma_cj(z[8], M, fft::cmul(z[8], P));
+            }
+            // W trade: wp[r] = W[N - k] belongs in register 15 - r of thread 256 - t: the Z trade back, into z[8..15]
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                z[8 + i] = wp[i];
+                z[15 - i] = wp[7 - i];
+                trade_lane_halves(z[8 + i], z[15 - i]);               // [8 + i] = their wp[7 - i], [15 - i] = their wp[i]
+            }
+            if (fw == 0) {                                            // own results into own registers (thread 0: bin N / 2 is register 8)
+                const bool t0 = lane == 0, t128 = lane == 32;
+                z[8] = t0 ? wp[0] : t128 ? wp[7] : z[8];
+#pragma unroll
+                for (int r = 9; r < 16; ++r) z[r] = t0 ? wp[16 - r] : t128 ? wp[15 - r] : z[r];
+            }
+            GAB_B12BAR(nb, 5);                                          // 6 (all sixteen results stay in registers)
         };
-        // second half (period nb + 1):   (half of the next window's requests) W exchange read, inverse pass 0 | write | read, twiddle, pass 1 |
+        // second half (period nb + 1):   (half of the next window's requests) inverse pass 0 | write | read, twiddle, pass 1 |
         //                                write (+ the other half) | read, twiddle, last pass (4 of 16), carry out | (the carry's stores leave)
         // (Measured and not kept, profiles/r25_far_pair_product.txt: that half of the requests in the idle interval instead, one
         // interval before pass 0 uses them — 4.85 against 4.73 us per buffer.)
@@ -1239,16 +1263,7 @@ __device__ __forceinline__ void conv_split_batch12_resident(
                 for (int r = 0; r < 16; ++r) zn[r] = mk(0.0f, 0.0f);  // (no value survives from the last window: registers)
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (nb_done >= 0) {
-                // the thread's own eight high results W[t + 256 r], r >= 8, from the second region (written by the partners'
-                // threads before the last period's closing barrier); the low ones are in z
-                if (!own_bins) {
-                    const unsigned t = opaque_t();
-#pragma unroll
-                    for (int r = 8; r < 16; ++r) z[r] = img[kNB / 2 + t + 256u * (r - 8)];
-                }
-                B16i::run(z);
-            }
+            if (nb_done >= 0) B16i::run(z);                           // all sixteen results W[t + 256 r] are in z
             GAB_B12BAR(period, 0);                                          // 1
             if (nb_done >= 0) {
                 const unsigned w0 = w0_of(opaque_t());
