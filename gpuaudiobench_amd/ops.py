@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1141,6 +1141,88 @@ class SaturatorPlan(_TrackPlan):
         return (self._h, _dev(x), _dev(out), _stream(stream))
 
     launch = _launcher("gab_sat_process")
+
+
+def nlms_params(step=0.5, floor_db=-60.0, taps=64):
+    """A row (all arguments scalars) or a table [n][2] float32 of NlmsPlan parameters {mu, eps} from the knobs of an
+    echo canceller; float64, rounded once.  mu = step; eps = taps * 10^(floor_db / 10): the window power of a reference
+    at floor_db, below which the normalisation stops raising the step."""
+    import numpy as np
+    args = [np.asarray(a, np.float64) for a in (step, floor_db, taps)]
+    scalar = all(a.ndim == 0 for a in args)
+    step, floor_db, taps = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    table = np.stack([step, taps * 10.0 ** (floor_db / 10.0)], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class NlmsPlan(_TrackPlan):
+    """gab_nlms_plan: a normalised-LMS adaptive filter per track (an echo canceller), bit for bit the contract of
+    gab_c_api.h.  Per track it reads a reference `ref` and an input `x`, writes the estimate (ref through the track's
+    `taps` taps: 64, 128, 256 or 512) and the error x - estimate, and adapts the taps on every sample.  Parameters per
+    track {mu, eps} (nlms_params makes them); a new plan holds zero taps and {0, 1}: the error is x and the estimate +0.
+    With mu = 0 and set_taps it is an FIR filter with its own taps per track.  New parameters are ramped in over the
+    next buffer unless ramp=False."""
+
+    _destroy = "gab_nlms_destroy"
+    FIELDS = ("mu", "eps")
+
+    def __init__(self, tracks, bufsize, taps=64):
+        self.taps = taps
+        self._create(tracks, bufsize, taps)
+
+    def set_params(self, table, ramp=True, first_track=None):
+        """table: device tensor [tracks][2], or [n][2] for tracks [first_track, first_track + n).
+        ramp=True: reached linearly over the next processed buffer; ramp=False: at once."""
+        n = self._rows(table, len(self.FIELDS), first_track)
+        self._set("params", _dev(table), first_track, n, 1 if ramp else 0)
+
+    def set_taps(self, w, first_track=None):
+        """w: device tensor [tracks][taps], or [n][taps] for tracks [first_track, first_track + n); finite values, in
+        force at once; the history stays."""
+        n = self._rows(w, self.taps, first_track, "taps")
+        self._set("taps", _dev(w), first_track, n)
+
+    def reset(self):
+        """Taps and history zero, current := target, a pending ramp dropped."""
+        super().reset()
+
+    def _run(self, what, x, ref, err, est, n):
+        assert x.numel() == (n or 1) * self.tracks * self.bufsize and ref.numel() == x.numel()
+        if err is None and est is None:
+            err = torch.empty_like(x)
+        assert all(o is None or o.numel() == x.numel() for o in (err, est))
+        rest = () if n is None else (n,)
+        check(self._fn(what)(self._h, _dev(x), _dev(ref), None if err is None else _dev(err),
+                             None if est is None else _dev(est), *rest, _stream()))
+        return err, est
+
+    def process(self, x, ref, err=None, est=None):
+        """One buffer, track-major [tracks*bufsize]: x the input (the microphone), ref the reference (the far end).
+        Returns (err, est).  err may be x itself and est may be ref itself.  With neither given a new err is made and
+        est is None; with one given the other is not computed."""
+        return self._run("process", x, ref, err, est, None)
+
+    def process_batch(self, xs, refs, err=None, est=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch."""
+        return self._run("process_batch", xs, refs, err, est, _n_buffers(self, xs))
+
+    def params(self):
+        """Copies of (current, target), each [tracks][2]."""
+        return self._tables("params", len(self.FIELDS))
+
+    def state(self):
+        """Copies of (taps [tracks][taps], history [tracks][taps - 1], the last reference samples, oldest first)."""
+        w, h, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib.gab_nlms_state(self._h, C.byref(w), C.byref(h), C.byref(n)))
+        return _view(w.value, self.tracks, n.value).clone(), _view(h.value, self.tracks, n.value - 1).clone()
+
+    def prepare(self, x, ref, err=None, est=None, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`.  Capture only with no ramp pending: gab_c_api.h, "Captured calls"."""
+        return (self._h, _dev(x), _dev(ref), None if err is None else _dev(err), None if est is None else _dev(est),
+                _stream(stream))
+
+    launch = _launcher("gab_nlms_process")
 
 
 _REVERB_SPREAD = 4.65    # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)

@@ -569,6 +569,8 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       flag, as if the ramp had run.
  *                       The saturator's process, process_batch and apply pick their form by the same flag and behave
  *                       the same way; capture them with no ramp pending (tests/test_saturator_gpu.py).
+ *                       The nlms plan's process and process_batch too (tests/test_nlms_gpu.py): the taps and the history
+ *                       are on the device and move with every replay.
  *   mix's ramp_first    the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
  *                       one that takes the ramp form.
  *   meter's decay       a launch argument: set_decay after the capture does not reach the replays.
@@ -1671,6 +1673,79 @@ int gab_sat_process_batch(gab_sat_plan* plan, const float* d_in, float* d_out, i
 int gab_sat_apply(gab_sat_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
 int gab_sat_params(gab_sat_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_sat_state(gab_sat_plan* plan, float** d_hist_in, float** d_hist_os, float** d_up, float** d_down);
+
+/* ---- nlms: an adaptive filter per track, normalised LMS (additive; no counterpart in the reference) ---------------
+ * An echo canceller, a feedback suppressor, hum or bleed removal with a reference: per track the plan reads a
+ * REFERENCE x (the far end, the loudspeaker feed) and an INPUT d (the microphone), writes the ESTIMATE y, x through the
+ * track's taps, and the ERROR e = d - y, the input with the echo removed, and adapts the taps on every sample.  With
+ * the step mu at 0 it is an FIR filter with its own taps per track.  T = tracks, B = bufsize, L = taps = 64 R with R in
+ * {1, 2, 4, 8}.
+ *   the arithmetic  Every operation is rounded once in float32.  Tap k = 64 q + l (q = 0..R-1, l = 0..63); the window
+ *                   is X[k] = x[n - k], zero before the stream's start and after a reset.  Per sample n, ascending:
+ *                     y   = T( C_q( w[64 q + l], X[64 q + l] ) )
+ *                             C_q, per l: acc = w[l] * X[l] (one rounded product), then
+ *                                         acc = fmaf(w[64 q + l], X[64 q + l], acc) for q = 1 .. R-1;
+ *                             T: the balanced binary tree over l = 0..63 in natural order, adjacent pairs first:
+ *                                32 sums of (2i, 2i + 1), then 16 of those, down to 1, each one rounded addition;
+ *                     P   = T( C_q( X, X ) )      the same chain and tree on the squares, recomputed on every sample:
+ *                                                 no running sum, so it cannot drift, is never negative and forgets a
+ *                                                 bad sample after L samples;
+ *                     e   = d[n] - y
+ *                     den = P + eps
+ *                     s   = mu / den              (the IEEE division)
+ *                     g   = s * e
+ *                     if g is finite (its exponent bits are not all ones):  w[k] = fmaf(g, X[k], w[k]) for every k;
+ *                     otherwise the taps are left as they are;
+ *                     err[n] = e,  est[n] = y     both from the taps BEFORE this sample's update.
+ *   bad inputs      An X[k] that is not finite makes y, hence e, hence g not finite: an infinity or a NaN in x reaches
+ *                   err and est for exactly L samples and never a tap; one in d reaches one sample of err and never a
+ *                   tap.  One track's samples never reach another track.  Overflow of a tap by FINITE arithmetic
+ *                   (samples near FLT_MAX) is not guarded.
+ *   rows            [T][GAB_NLMS_FIELDS] float32 = {mu, eps} per track.  A new plan holds zero taps and {0, 1}: est is all
+ *                   +0 and err is d, bit for bit.  The rule: mu finite and 0 <= mu <= 2 (-0.0 is taken); eps finite and
+ *                   2^-126 <= eps <= 2^64.  set_params (all tracks) and set_params_tracks ([first_track, first_track +
+ *                   n_tracks)) take a device table, checked on the device first: the first refused value is named as
+ *                   (track, field) with GAB_ERR_INVALID_ARG and the plan keeps its tables.  ramp = 0: in force at once.
+ *                   ramp = 1: over the next buffer processed (in a batch, its first), sample s takes, per field,
+ *                     fmaf(target - current, r[s], current),  r[s] = (float)((s + 1) / B)    (float64, rounded once)
+ *                   and behind that buffer current := target.  Synchronous with respect to `stream`.
+ *   state           d_taps [T][L]; d_history [T][L - 1], the last L - 1 reference samples, oldest first, shifted and
+ *                   not replaced, so right when B < L - 1.  Both on the device, exposed by gab_nlms_state (the plan's
+ *                   own memory).  set_taps / set_taps_tracks take device tables [n][L] of finite values (the first
+ *                   that is not is named as (track, tap), and the plan keeps its taps), are not ramped, are in force
+ *                   from the next sample processed and leave the history alone; synchronous with respect to `stream`.
+ *                   reset: taps and history zero, current := target, a pending ramp dropped.
+ *   blocks          d_in (d), d_ref (x), d_err, d_est: [n][T][B] float32, track-major, any 4-byte alignment, any B >= 1.
+ *                   One of d_err and d_est may be null (both: refused).  d_err may be d_in itself and d_est may be d_ref
+ *                   itself; every other overlap between an output and anything else is refused with its text.  One
+ *                   launch on `stream` per call or batch: a wave per track, four a workgroup, no workgroup barrier and
+ *                   no atomics; the wave holds its track's taps and window in registers for the whole call, so a batch
+ *                   moves the state once.  process_batch gives the bits of n process calls.
+ *   determinism     Output bits depend on the track's samples, its row and its taps.  Not on B, on the cut into calls or
+ *                   batches, or on alignment.  A shard of tracks as its own plan gives those tracks' bits.
+ * process and process_batch allocate nothing and wait for nothing, and all changing state but the pending flag is on
+ * the device: capture with no ramp pending ("Captured calls", above).  Arguments are checked before any device call,
+ * each refusal with its own text: tracks and bufsize >= 1, taps in {64, 128, 256, 512}, null pointers, n_buffers >= 1,
+ * the track range of a set, the overlaps above.  Fewer than 1024 tracks use a part of the device.  Out of scope: a leak
+ * term, double-talk detection, frequency-domain or block-exact forms, tap counts that are not 64 * 2^k, a call-level
+ * "do not adapt" kernel form (mu = 0 runs the same kernel), linked tracks.  One thread at a time per plan.              */
+typedef struct gab_nlms_plan gab_nlms_plan;
+#define GAB_NLMS_FIELDS 2
+int gab_nlms_create(gab_nlms_plan** plan, int tracks, int bufsize, int taps);
+int gab_nlms_destroy(gab_nlms_plan* plan);
+int gab_nlms_set_params(gab_nlms_plan* plan, const float* d_params, int ramp, gab_stream_t stream);
+int gab_nlms_set_params_tracks(gab_nlms_plan* plan, const float* d_params, int first_track, int n_tracks, int ramp,
+                               gab_stream_t stream);
+int gab_nlms_set_taps(gab_nlms_plan* plan, const float* d_taps, gab_stream_t stream);
+int gab_nlms_set_taps_tracks(gab_nlms_plan* plan, const float* d_taps, int first_track, int n_tracks,
+                             gab_stream_t stream);
+int gab_nlms_reset(gab_nlms_plan* plan, gab_stream_t stream);
+int gab_nlms_process(gab_nlms_plan* plan, const float* d_in, const float* d_ref, float* d_err, float* d_est,
+                     gab_stream_t stream);
+int gab_nlms_process_batch(gab_nlms_plan* plan, const float* d_in, const float* d_ref, float* d_err, float* d_est,
+                           int n_buffers, gab_stream_t stream);
+int gab_nlms_params(gab_nlms_plan* plan, float** d_current, float** d_target, size_t* n_floats);
+int gab_nlms_state(gab_nlms_plan* plan, float** d_taps, float** d_history, int* taps);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
