@@ -1,7 +1,8 @@
 // gab_stft.hpp — what the short-time Fourier plans (spectrum, resynthesis, denoise) share.  The fused
 // denoise kernel uses the constants, sample, power, wave_sync and the host side, and keeps analyse, pack and the Ring
-// written out in its own body (k_denoise.hip says why):
-//   device   the sample fetch, the analysis of a pair's frame, the power of a bin, the packing of a pair's rows, the
+// written out in its own body (k_denoise.hip says why); the fdaf plan (k_fdaf.hip) holds its frames in registers and
+// uses spectra, pack and wave_sync:
+//   device   the sample fetch, the analysis of a pair's frame (its gather, and spectra() behind it), the power of a bin, the packing of a pair's rows, the
 //            overlap-add ring, the history update, the wave's hand-over fence
 //   host     the two default windows, the hop grid and what the plans refuse of it, the power factors, the window rule
 #pragma once
@@ -42,23 +43,14 @@ __device__ __forceinline__ float sample(const float* __restrict__ in, const floa
     return in[((size_t)nb * T + t) * B + s];
 }
 
-// The frame of tracks ta and ta + 1 (hasb: the second is there) that starts at sample `start` of the call: lane j
-// gathers s[start + j + 64 r], multiplies by wn[r] = w[j + 64 r] in one rounded product, runs the wave-held forward
-// transform through img and unpacks the pair as fft_r2c_1024_kernel does.  xa[r], xb[r]: bin k = lane + 64 r of either
-// track; bins 0..512 are r < 8 plus (r = 8, lane 0), and zero above.  The partner reads of img are not fenced off here.
+// analyse() behind its gather, for a plan that holds its frames in registers (the fdaf plan, where a window of ones is
+// no product at all): lane j enters with z[r] = a[j + 64 r] + i b[j + 64 r], the packed frame of a pair, which goes
+// through the wave-held forward transform and is unpacked as fft_r2c_1024_kernel does.  xa[r], xb[r]: bin k = lane + 64 r
+// of either track; bins 0..512 are r < 8 plus (r = 8, lane 0), and zero above.  z is left holding the packed transform.
+// The partner reads of img are not fenced off here.
 template <class TW>
-__device__ __forceinline__ void analyse(const float* __restrict__ in, const float* hist, int T, int B, bool one_buffer,
-                                        int ta, bool hasb, int start, const float (&wn)[16], cf* img, const TW& t,
-                                        int lane, cf (&xa)[9], cf (&xb)[9]) {
-    cf z[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int n = lane + 64 * r;
-        const float sa = sample(in, hist, T, B, one_buffer, ta, start + n);
-        const float sb = hasb ? sample(in, hist, T, B, one_buffer, ta + 1, start + n) : 0.0f;
-        z[r] = fft::mk(__fmul_rn(wn[r], sa), __fmul_rn(wn[r], sb));
-    }
-    fft::WaveFFT1024<false>::run(z, img, t, lane);        // EXEC is all ones here: every loop above has reconverged
+__device__ __forceinline__ void spectra(cf (&z)[16], cf* img, const TW& t, int lane, cf (&xa)[9], cf (&xb)[9]) {
+    fft::WaveFFT1024<false>::run(z, img, t, lane);        // EXEC is all ones here: every loop of the caller has reconverged
     // partner Z[(N - k) mod N], k = lane + 64 r
     const unsigned rb = (unsigned)lane + ((unsigned)lane >> 4);
 #pragma unroll
@@ -76,6 +68,24 @@ __device__ __forceinline__ void analyse(const float* __restrict__ in, const floa
             xb[r] = fft::mk(0.5f * d.y, -0.5f * d.x);
         }
     }
+}
+
+// The frame of tracks ta and ta + 1 (hasb: the second is there) that starts at sample `start` of the call: lane j
+// gathers s[start + j + 64 r], multiplies by wn[r] = w[j + 64 r] in one rounded product, and hands the packed frame to
+// spectra().
+template <class TW>
+__device__ __forceinline__ void analyse(const float* __restrict__ in, const float* hist, int T, int B, bool one_buffer,
+                                        int ta, bool hasb, int start, const float (&wn)[16], cf* img, const TW& t,
+                                        int lane, cf (&xa)[9], cf (&xb)[9]) {
+    cf z[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int n = lane + 64 * r;
+        const float sa = sample(in, hist, T, B, one_buffer, ta, start + n);
+        const float sb = hasb ? sample(in, hist, T, B, one_buffer, ta + 1, start + n) : 0.0f;
+        z[r] = fft::mk(__fmul_rn(wn[r], sa), __fmul_rn(wn[r], sb));
+    }
+    spectra(z, img, t, lane, xa, xb);
 }
 
 // P[k] = (re re + im im) inv_k, every operation rounded once; inv_k is (float)(1 / S^2) at bins 0 and 512, else

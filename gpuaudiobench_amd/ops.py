@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms, fdaf) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1223,6 +1223,102 @@ class NlmsPlan(_TrackPlan):
                 _stream(stream))
 
     launch = _launcher("gab_nlms_process")
+
+
+def fdaf_params(step=0.5, floor_db=-60.0, partitions=1):
+    """A row (all arguments scalars) or a table [n][2] float32 of FdafPlan parameters {mu, eps} from the knobs of an
+    echo canceller; float64, rounded once.  mu = step; eps = partitions * 1024 * 10^(floor_db / 10): the bin power, in
+    the units of the unnormalised 1024-point transform, of a white reference at floor_db, below which the normalisation
+    stops raising the step.  One partition diverges at step 1 and is fine at 0.5; four and more take 1."""
+    import numpy as np
+    args = [np.asarray(a, np.float64) for a in (step, floor_db, partitions)]
+    scalar = all(a.ndim == 0 for a in args)
+    step, floor_db, partitions = np.broadcast_arrays(*[np.atleast_1d(a) for a in args])
+    table = np.stack([step, partitions * 1024.0 * 10.0 ** (floor_db / 10.0)], axis=-1).astype(np.float32)
+    return table[0] if scalar else table
+
+
+class FdafPlan(_TrackPlan):
+    """gab_fdaf_plan: a partitioned frequency-domain NLMS filter per track (the multidelay block filter), the long form
+    of NlmsPlan: `partitions` K in 1..32 of 512 taps each, adapted per bin once per block of 512 samples; bufsize a
+    multiple of 512.  Per track it reads a reference `ref` and an input `x` and writes the estimate (ref through the
+    taps) and the error x - estimate.  Parameters per track {mu, eps} (fdaf_params makes them), in force from the next
+    block: there is no ramp.  A new plan holds zero taps and {0, 1}: the error is x and the estimate +0.  With mu = 0 and
+    set_taps it is a partitioned FIR filter with its own long taps per track."""
+
+    _destroy = "gab_fdaf_destroy"
+    FIELDS = ("mu", "eps")
+    BLOCK, BINS = 512, 513
+
+    def __init__(self, tracks, bufsize, partitions=1):
+        self.partitions = partitions
+        self._create(tracks, bufsize, partitions)
+
+    def set_params(self, table, first_track=None):
+        """table: device tensor [tracks][2], or [n][2] for tracks [first_track, first_track + n); at once."""
+        n = self._rows(table, len(self.FIELDS), first_track)
+        self._set("params", _dev(table), first_track, n)
+
+    def set_taps(self, h, first_track=None):
+        """h: device tensor [tracks][512 partitions] of time-domain taps, or [n][...] for tracks [first_track,
+        first_track + n); finite values, in force at once; the delay line and the block count stay."""
+        n = self._rows(h, self.BLOCK * self.partitions, first_track, "taps")
+        self._set("taps", _dev(h), first_track, n)
+
+    def reset(self):
+        """Taps, delay line, previous block and block count zero; the parameters stay."""
+        super().reset()
+
+    def _run(self, what, x, ref, err, est, n):
+        assert x.numel() == (n or 1) * self.tracks * self.bufsize and ref.numel() == x.numel()
+        if err is None and est is None:
+            err = torch.empty_like(x)
+        assert all(o is None or o.numel() == x.numel() for o in (err, est))
+        rest = () if n is None else (n,)
+        check(self._fn(what)(self._h, _dev(x), _dev(ref), None if err is None else _dev(err),
+                             None if est is None else _dev(est), *rest, _stream()))
+        return err, est
+
+    def process(self, x, ref, err=None, est=None):
+        """One buffer, track-major [tracks*bufsize]: x the input (the microphone), ref the reference (the far end).
+        Returns (err, est).  err may be x itself and est may be ref itself.  With neither given a new err is made and
+        est is None; with one given the other is not computed."""
+        return self._run("process", x, ref, err, est, None)
+
+    def process_batch(self, xs, refs, err=None, est=None):
+        """Consecutive buffers [n][tracks*bufsize] in one launch."""
+        return self._run("process_batch", xs, refs, err, est, _n_buffers(self, xs))
+
+    def params(self):
+        """A copy of the table [tracks][2]."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        check(lib.gab_fdaf_params(self._h, C.byref(p), C.byref(n)))
+        return _view(p.value, self.tracks, len(self.FIELDS)).clone()
+
+    def state(self):
+        """Copies of (W [tracks][K][513] complex64, the partitions' half-spectra; X, the same shape, the delay line with
+        block b in slot b mod K; prev [tracks][512], the reference block before; count [tracks] int64, the blocks since
+        the reset)."""
+        w, x, pv, c, k = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib.gab_fdaf_state(self._h, C.byref(w), C.byref(x), C.byref(pv), C.byref(c), C.byref(k)))
+        shape = (self.tracks, k.value, self.BINS)
+        spectra = [torch.view_as_complex(_view(p.value, self.tracks, k.value * self.BINS * 2).clone()
+                                         .view(*shape, 2)) for p in (w, x)]
+        return spectra[0], spectra[1], _view(pv.value, self.tracks, self.BLOCK).clone(), _positions(c.value, self.tracks)
+
+    def taps(self):
+        """The taps in time [tracks][512 partitions]: the first 512 samples of each partition's inverse transform, by
+        torch.fft on a copy of W."""
+        w = self.state()[0]
+        return torch.fft.irfft(w, n=2 * self.BLOCK, dim=-1)[..., :self.BLOCK].reshape(self.tracks, -1).contiguous()
+
+    def prepare(self, x, ref, err=None, est=None, stream=None):
+        """The ctypes arguments of process(), built once for a loop over the same buffers or a graph capture;
+        `launch(args)`."""
+        return (self._h, _dev(x), _dev(ref), None if err is None else _dev(err), None if est is None else _dev(est),
+                _stream(stream))
+
+    launch = _launcher("gab_fdaf_process")
 
 
 _REVERB_SPREAD = 4.65    # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)

@@ -571,7 +571,9 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       the same way; capture them with no ramp pending (tests/test_saturator_gpu.py).
  *                       The nlms plan's process and process_batch too (tests/test_nlms_gpu.py): the taps and the history
  *                       are on the device and move with every replay.
- *   mix's ramp_first    the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
+ *                       The fdaf plan has no ramp and no host state at all: W, X, prev and count are the device's and
+ *                       move with every replay, whatever is pending or set (tests/test_fdaf_gpu.py).
+ *   mix's ramp_first   the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
  *                       one that takes the ramp form.
  *   meter's decay       a launch argument: set_decay after the capture does not reach the replays.
  *   alignment           eq picks the scan or the sequential kernel, mix, dynamics and meter the width of their loads,
@@ -1746,6 +1748,94 @@ int gab_nlms_process_batch(gab_nlms_plan* plan, const float* d_in, const float* 
                            int n_buffers, gab_stream_t stream);
 int gab_nlms_params(gab_nlms_plan* plan, float** d_current, float** d_target, size_t* n_floats);
 int gab_nlms_state(gab_nlms_plan* plan, float** d_taps, float** d_history, int* taps);
+
+/* ---- fdaf: a block adaptive filter per track, partitioned frequency-domain NLMS (additive; no counterpart) ---------
+ * The nlms plan's long form, the multidelay block filter (MDF): K = partitions of 512 taps each, L = 512 K taps up to
+ * 16 384 (341 ms at 48 kHz), adapted per bin once per BLOCK of 512 samples with 1024-point overlap-save transforms.
+ * d (d_in) is the microphone, x (d_ref) the far end; est is x through the taps, err = d - est.  With mu = 0 and set_taps
+ * it is a partitioned FIR filter with its own long taps per track.  T = tracks, B = bufsize, a positive multiple of 512
+ * (other sizes are refused): a buffer is B / 512 blocks, walked in order.  K in 1..32, any integer.
+ *   pairs           Tracks 2q and 2q + 1 share every transform as a + i b, as the spectrum, resynthesis and denoise
+ *                   plans' do.  An odd last track stands beside a partner of zero samples, zero taps and the row {0, 1},
+ *                   of which nothing is stored.
+ *   state           W [T][K][513][2], the partitions' half-spectra; X [T][K][513][2], the delay line as a ring: block
+ *                   b's spectra sit in slot b mod K; prev [T][512], the reference block before; count [T] (uint32), the
+ *                   blocks since the reset, skipped ones included (it wraps after 2^32 blocks).  On the device, exposed
+ *                   by gab_fdaf_state as the plan's own memory.  A new plan and a reset hold zeros everywhere.
+ *   the arithmetic  float32, every operation rounded once; fmaf is one rounding.  The two complex products:
+ *                     acc (+)= a b        re = fmaf(a.re, b.re, fmaf(-a.im, b.im, acc.re))
+ *                                         im = fmaf(a.re, b.im, fmaf( a.im, b.re, acc.im))
+ *                     acc (+)= conj(a) b  re = fmaf(a.re, b.re, fmaf( a.im, b.im, acc.re))
+ *                                         im = fmaf(a.re, b.im, fmaf(-a.im, b.re, acc.im))
+ *                   Per block b = count and pair, in this order:
+ *                     1. X[b mod K] = the half-spectra of the pair's window [prev | x_b]: the spectrum plan's analysis
+ *                        with a window of ones (no product), the same wave-held forward transform and unpack.  The
+ *                        slot holds, bit for bit, the row gab_spec_* (hop 512, complex) writes for that frame.
+ *                     2. Y[k] = sum_p X[(b - p) mod K][k] W_p[k], p ascending from acc = +0, the first product above;
+ *                        S[k] = sum_p fmaf(im, im, fmaf(re, re, S)) of the same spectra, p ascending from +0.  S is
+ *                        formed anew every block: it cannot drift, is never negative and forgets a bad block after K.
+ *                     3. The pair's Y packed as the resynthesis plan packs its rows, the inverse transform;
+ *                        est[n] = fmaf(z[512 + n], 2^-10, +0) (a -0 becomes +0), e[n] = d[n] - est[n].
+ *                     4. THE SKIP.  If any of the pair's 1024 values of e (both tracks) is not finite, steps 5 to 7 are
+ *                        skipped for this block and pair: W stays as it is, count still advances.
+ *                     5. E = the half-spectra of [0 | e] (512 zeros, then the block's errors), as in step 1.
+ *                     6. s[k] = mu / (S[k] + eps) (one addition, the IEEE division; per track); G[k] = (s E.re, s E.im);
+ *                        W_p[k] (+)= conj(X[(b - p) mod K][k]) G[k] for every p, the second product above.
+ *                     7. THE GRADIENT CONSTRAINT, alternated (the scheme of Speex's MDF): for partition c = b mod K
+ *                        only, the pair's W_c packed, inverse, times 2^-10, samples 512..1023 stored as +0, forward,
+ *                        unpacked as in step 1, stored.  One inverse and one forward a block whatever K is.  There is
+ *                        no unconstrained mode: without it the misalignment stalls between -10 and -30 dB.
+ *                   Then prev := x_b, count += 1.  A track whose mu is 0 never writes its W (its taps stay bit for bit,
+ *                   where steps 6 and 7 would move them by roundings), and a pair of two such tracks leaves steps 5 to 7
+ *                   out: an FIR filter costs two transforms and one pass a block.
+ *   bad inputs      An infinity or a NaN in x lies in two windows, its block's and the next one's, so in the delay
+ *                   line for K + 1 blocks: it is in that pair's err and est for exactly K + 1 blocks and never in W.
+ *                   One in d is in err for that sample only and costs the pair one block of adaptation.  Nothing
+ *                   crosses a pair.  Overflow by FINITE arithmetic (samples near FLT_MAX) is not guarded.
+ *   rows            [T][GAB_FDAF_FIELDS] float32 = {mu, eps} per track.  A new plan holds {0, 1}: est is all +0 and err
+ *                   is d, bit for bit.  The rule: mu finite and 0 <= mu <= 1 (-0.0 is taken); eps finite and 2^-126 <=
+ *                   eps <= 2^64.  S is in the units of the unnormalised transform: white noise of power P gives about
+ *                   1024 K P.  With K = 1 the filter diverges at mu = 1 and is fine at 0.5; K >= 4 takes 1.
+ *                   set_params (all tracks) and set_params_tracks take a device table, checked on the device first: the
+ *                   first refused value is named as (track, field) with GAB_ERR_INVALID_ARG and the plan keeps its
+ *                   table.  UNRAMPED: a block is the step's own granularity, and with one block a buffer a ramp over a
+ *                   buffer is nothing; in force from the next block processed.  Synchronous with respect to `stream`.
+ *   taps            set_taps / set_taps_tracks take device tables [n][512 K] of finite time-domain taps (the first that
+ *                   is not is named as (track, tap), and the plan keeps its taps) and fill W_p with the half-spectrum of
+ *                   [h[512 p .. 512 p + 512) | 512 zeros], each track alone in its transform: a small launch of the
+ *                   plan's own.  They leave X, prev and count alone; synchronous with respect to `stream`.  The taps in
+ *                   time are the first 512 samples of each partition's inverse transform.
+ *   blocks          d_in, d_ref, d_err, d_est: [n][T][B] float32, track-major, any 4-byte alignment.  One of d_err and
+ *                   d_est may be null (both: refused).  d_err may be d_in itself and d_est may be d_ref itself; every
+ *                   other overlap between an output and anything else is refused with its text.  One launch on `stream`
+ *                   per call or batch: a wave per pair, four a workgroup, no workgroup barrier and no atomics; the wave
+ *                   walks its pair's blocks in ascending order.  process_batch gives the bits of n process calls.
+ *   determinism     Output bits depend on the pair's samples, rows and state.  Not on B, on the cut into calls or
+ *                   batches, on alignment, or on which plan (a shard that starts on an even track) holds the pair.
+ * process and process_batch allocate nothing and wait for nothing, and all changing state is on the device: they can be
+ * captured ("Captured calls", above).  Arguments are checked before any device call, each refusal with its own text:
+ * tracks and bufsize >= 1, bufsize a multiple of 512, partitions in 1..32, null pointers, n_buffers >= 1, n_buffers *
+ * bufsize below 2^31 - 1024, the track range of a set, the overlaps above.  Fewer than 2048 tracks use a part of the
+ * device.  Out of scope: double-talk detection, a leak term, other block or transform sizes (buffers of 64 to 256
+ * samples), a smoothed power estimate, linked tracks, the gpubench driver, tests/walks.py, the strip helpers.  One
+ * thread at a time per plan.                                                                                          */
+typedef struct gab_fdaf_plan gab_fdaf_plan;
+#define GAB_FDAF_FIELDS 2
+int gab_fdaf_create(gab_fdaf_plan** plan, int tracks, int bufsize, int partitions);
+int gab_fdaf_destroy(gab_fdaf_plan* plan);
+int gab_fdaf_set_params(gab_fdaf_plan* plan, const float* d_params, gab_stream_t stream);
+int gab_fdaf_set_params_tracks(gab_fdaf_plan* plan, const float* d_params, int first_track, int n_tracks,
+                               gab_stream_t stream);
+int gab_fdaf_set_taps(gab_fdaf_plan* plan, const float* d_taps, gab_stream_t stream);
+int gab_fdaf_set_taps_tracks(gab_fdaf_plan* plan, const float* d_taps, int first_track, int n_tracks,
+                             gab_stream_t stream);
+int gab_fdaf_reset(gab_fdaf_plan* plan, gab_stream_t stream);
+int gab_fdaf_process(gab_fdaf_plan* plan, const float* d_in, const float* d_ref, float* d_err, float* d_est,
+                     gab_stream_t stream);
+int gab_fdaf_process_batch(gab_fdaf_plan* plan, const float* d_in, const float* d_ref, float* d_err, float* d_est,
+                           int n_buffers, gab_stream_t stream);
+int gab_fdaf_params(gab_fdaf_plan* plan, float** d_params, size_t* n_floats);
+int gab_fdaf_state(gab_fdaf_plan* plan, float** d_W, float** d_X, float** d_prev, unsigned** d_count, int* partitions);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
