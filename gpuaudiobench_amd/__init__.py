@@ -9,7 +9,7 @@ CPU; if the shared object is missing the import fails.
 from . import _capi
 from ._capi import GabError, lib, check, CONV_STATELESS, CONV_STREAMING, CONV_STREAMING_HOST_IO, DWG_NAIVE, DWG_ACCEL
 from .ops import (noop, gain, gainstats, datatransfer, iir, conv1d, rndmem, modal, modal_bank, dwg,
-                  fft_r2c_1024, ConvPlan, EqPlan, MixPlan, DelayPlan, MeterPlan, ResamplePlan, DynamicsPlan, dynamics_params, GatePlan, gate_params, CrossoverPlan, crossover_rows, LimiterPlan, limiter_params, SaturatorPlan, saturator_params, NlmsPlan, nlms_params, FdafPlan, fdaf_params, SpectrumPlan, spectrum_band_edges, ResynthesisPlan, synthesis_window, DenoisePlan, denoise_params, denoise_thresholds, ReverbPlan, reverb_params, FdtdPlan, LinkPlan, KeepWarm,
+                  fft_r2c_1024, ConvPlan, EqPlan, MixPlan, DelayPlan, MeterPlan, ResamplePlan, DynamicsPlan, dynamics_params, GatePlan, gate_params, CrossoverPlan, crossover_rows, LimiterPlan, limiter_params, SaturatorPlan, saturator_params, NlmsPlan, nlms_params, FdafPlan, fdaf_params, MatrixConvPlan, SpectrumPlan, spectrum_band_edges, ResynthesisPlan, synthesis_window, DenoisePlan, denoise_params, denoise_thresholds, ReverbPlan, reverb_params, FdtdPlan, LinkPlan, KeepWarm,
                   fdtd_default_params, device_count, modal_launch, dwg_route, MODAL_FORMS, DWG_CELLS, DWG_MIX, FDTD_FORMS)
 
 from . import harness
@@ -19,6 +19,6 @@ __all__ = [
     "harness", "Benchmark", "benchmark_names",
     "GabError", "lib", "check", "CONV_STATELESS", "CONV_STREAMING", "CONV_STREAMING_HOST_IO", "DWG_NAIVE", "DWG_ACCEL",
     "noop", "gain", "gainstats", "datatransfer", "iir", "conv1d", "rndmem", "modal", "modal_bank", "dwg",
-    "fft_r2c_1024", "ConvPlan", "EqPlan", "MixPlan", "DelayPlan", "MeterPlan", "ResamplePlan", "DynamicsPlan", "dynamics_params", "GatePlan", "gate_params", "CrossoverPlan", "crossover_rows", "LimiterPlan", "limiter_params", "SaturatorPlan", "saturator_params", "NlmsPlan", "nlms_params", "FdafPlan", "fdaf_params", "SpectrumPlan", "spectrum_band_edges", "ResynthesisPlan", "synthesis_window", "DenoisePlan", "denoise_params", "denoise_thresholds", "ReverbPlan", "reverb_params", "FdtdPlan", "LinkPlan", "KeepWarm", "fdtd_default_params", "device_count",
+    "fft_r2c_1024", "ConvPlan", "EqPlan", "MixPlan", "DelayPlan", "MeterPlan", "ResamplePlan", "DynamicsPlan", "dynamics_params", "GatePlan", "gate_params", "CrossoverPlan", "crossover_rows", "LimiterPlan", "limiter_params", "SaturatorPlan", "saturator_params", "NlmsPlan", "nlms_params", "FdafPlan", "fdaf_params", "MatrixConvPlan", "SpectrumPlan", "spectrum_band_edges", "ResynthesisPlan", "synthesis_window", "DenoisePlan", "denoise_params", "denoise_thresholds", "ReverbPlan", "reverb_params", "FdtdPlan", "LinkPlan", "KeepWarm", "fdtd_default_params", "device_count",
     "modal_launch", "dwg_route", "MODAL_FORMS", "DWG_CELLS", "DWG_MIX", "FDTD_FORMS",
 ]

@@ -316,6 +316,14 @@ PROTOTYPES = {
     "gab_fdaf_process_batch": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "gab_fdaf_params": (_I, [_P, C.POINTER(_P), C.POINTER(_Z)]),
     "gab_fdaf_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
+    "gab_mconv_create": (_I, [C.POINTER(_P), _I, _I, _I, _I]),
+    "gab_mconv_destroy": (_I, [_P]),
+    "gab_mconv_set_taps": (_I, [_P, _P, _I, _P]),
+    "gab_mconv_set_taps_range": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "gab_mconv_reset": (_I, [_P, _P]),
+    "gab_mconv_process": (_I, [_P, _P, _P, _P]),
+    "gab_mconv_process_batch": (_I, [_P, _P, _P, _I, _P]),
+    "gab_mconv_state": (_I, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_I)]),
     "gab_generate_noise":(_I, [_P, _Z, C.c_uint]),
     "gab_glibc_rand": (_I, [C.c_uint, C.c_ulonglong, _P, _Z]),
     "gab_shard_range": (_I, [_I, _I, _Z, C.POINTER(_Z), C.POINTER(_Z)]),

@@ -1,6 +1,6 @@
 // gab_plan.hpp — what the host halves of the plans share.  Who owns device memory, pinned memory,
-// events and streams: every plan.  For the sixteen track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate,
-// crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms and fdaf) also "check, then commit" for a set of parameters (one check
+// events and streams: every plan.  For the seventeen track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate,
+// crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms, fdaf and mconv) also "check, then commit" for a set of parameters (one check
 // kernel, a rule per table); the bodies of their
 // extern "C" entries (create, process_batch, a ranged set, the exposed table, destroy, and every call that starts with
 // a null check); the table that is ramped from current to target over one buffer.

@@ -1,7 +1,7 @@
 // gab_stft.hpp — what the short-time Fourier plans (spectrum, resynthesis, denoise) share.  The fused
 // denoise kernel uses the constants, sample, power, wave_sync and the host side, and keeps analyse, pack and the Ring
 // written out in its own body (k_denoise.hip says why); the fdaf plan (k_fdaf.hip) holds its frames in registers and
-// uses spectra, pack and wave_sync:
+// uses spectra, pack_rows, tap_spectrum and wave_sync, and so does the matrix-convolution plan (k_mconv.hip):
 //   device   the sample fetch, the analysis of a pair's frame (its gather, and spectra() behind it), the power of a bin, the packing of a pair's rows, the
 //            overlap-add ring, the history update, the wave's hand-over fence
 //   host     the two default windows, the hop grid and what the plans refuse of it, the power factors, the window rule
@@ -107,6 +107,52 @@ __device__ __forceinline__ cf pack(cf a, cf b, int k) {
     }
     return k > kN / 2 ? fft::mk(__fadd_rn(a.x, b.y), __fsub_rn(b.x, a.y))
                       : fft::mk(__fsub_rn(a.x, b.y), __fadd_rn(a.y, b.x));
+}
+
+// pack() of a pair's rows held in registers (a[r], b[r]: bin k = lane + 64 r, as spectra() leaves them): the bins above
+// 512 are bin N - k of another lane, so the rows go through the image (which must be free), and z becomes the pair's
+// packed spectrum, entry k = lane + 64 r.  Ends with the image free again.
+__device__ __forceinline__ void pack_rows(const cf (&a)[9], const cf (&b)[9], cf* img, int lane, cf (&z)[16]) {
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+        const int k = lane + 64 * r;
+        if (k <= kN / 2) {
+            img[k] = a[r];
+            img[kImgB + k] = b[r];
+        }
+    }
+    wave_sync();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int k = lane + 64 * r;
+        if (r < 8) {
+            z[r] = pack(a[r], b[r], k);
+        } else {
+            const int kk = kN - k;                         // (r = 8, lane 0: bin 512 itself)
+            z[r] = pack(img[kk], img[kImgB + kk], k);
+        }
+    }
+    wave_sync();
+}
+
+// The half-spectrum of one partition of time-domain taps, [h[0 .. 512) | 512 zeros], alone in its transform (the
+// partner's half is zeros), to dst[0 .. 513): what the fdaf and the matrix-convolution plans' set_taps store.
+template <class TW>
+__device__ __forceinline__ void tap_spectrum(const float* __restrict__ h, cf* __restrict__ dst, cf* img, const TW& t,
+                                             int lane) {
+    cf z[16];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        z[j] = fft::mk(h[lane + 64 * j], 0.0f);
+        z[j + 8] = fft::mk(0.0f, 0.0f);
+    }
+    cf xa[9], xb[9];
+    spectra(z, img, t, lane, xa, xb);
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+        const int k = lane + 64 * r;
+        if (k <= kN / 2) dst[k] = xa[r];
+    }
 }
 
 // A pair's accumulator in the wave's two LDS rows of 1024 floats, indexed from a moving base.  acc: the pair's rows

@@ -57,31 +57,6 @@ __device__ __forceinline__ cf fdaf_mac(cf x, cf w, cf acc) { return fft::cfma(x,
 __device__ __forceinline__ cf fdaf_step(cf x, cf g, cf w) { return fft::cfma_cj(x, g, w); }
 __device__ __forceinline__ float fdaf_power(cf x, float s) { return fmaf(x.y, x.y, fmaf(x.x, x.x, s)); }
 
-// The bins above 512 of a pair's rows are bin N - k of another lane: the rows go through the image (which must be
-// free), and z becomes the pair's packed spectrum, entry k = lane + 64 r.  Ends with the image free again.
-__device__ __forceinline__ void fdaf_pack(const cf (&a)[9], const cf (&b)[9], cf* img, int lane, cf (&z)[16]) {
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        const int k = lane + 64 * r;
-        if (k <= stft::kN / 2) {
-            img[k] = a[r];
-            img[stft::kImgB + k] = b[r];
-        }
-    }
-    stft::wave_sync();
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int k = lane + 64 * r;
-        if (r < 8) {
-            z[r] = stft::pack(a[r], b[r], k);
-        } else {
-            const int kk = stft::kN - k;                   // (r = 8, lane 0: bin 512 itself)
-            z[r] = stft::pack(img[kk], img[stft::kImgB + kk], k);
-        }
-    }
-    stft::wave_sync();
-}
-
 // Grid: x = group of four pairs.  in (d), ref (x), err, est: [n][T][B], B a multiple of 512; err may be in, est may be
 // ref, one of err and est may be null.  W, X: [T][K][513] complex.  prev: [T][512].  count: [T].  params: [T][2].
 __global__ __launch_bounds__(256) void fdaf_kernel(const float* in, const float* ref, float* err, float* est,
@@ -179,7 +154,7 @@ __global__ __launch_bounds__(256) void fdaf_kernel(const float* in, const float*
         }
         // ---- 3. the estimate and the error ----
         stft::wave_sync();                                 // every lane has read its partners of step 1
-        fdaf_pack(ya, yb, img, lane, z);
+        stft::pack_rows(ya, yb, img, lane, z);
         INV::run(z, img, t, lane);
         float ea[8], eb[8];
         bool bad = false;
@@ -244,7 +219,7 @@ __global__ __launch_bounds__(256) void fdaf_kernel(const float* in, const float*
             }
             // ---- 7. the constraint on partition c: its last 512 taps in time become +0 ----
             stft::wave_sync();                             // every lane has read its partners of step 5
-            fdaf_pack(ca, cb, img, lane, z);
+            stft::pack_rows(ca, cb, img, lane, z);
             INV::run(z, img, t, lane);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -290,21 +265,8 @@ __global__ __launch_bounds__(256) void fdaf_taps_kernel(const float* __restrict_
     using FWD = fft::WaveFFT1024<false>;
     FWD::Lean t;
     FWD::load_twiddles(t, tw, lane);
-    const float* const h = taps + ((size_t)ti * K + p) * kFdafBlock;
-    cf z[16];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        z[j] = fft::mk(h[lane + 64 * j], 0.0f);
-        z[j + 8] = fft::mk(0.0f, 0.0f);
-    }
-    cf xa[9], xb[9];
-    stft::spectra(z, img, t, lane, xa, xb);
-    cf* const Wp = W + ((size_t)(first_track + ti) * K + p) * stft::kBins;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-        const int k = lane + 64 * r;
-        if (k <= stft::kN / 2) Wp[k] = xa[r];
-    }
+    stft::tap_spectrum(taps + ((size_t)ti * K + p) * kFdafBlock, W + ((size_t)(first_track + ti) * K + p) * stft::kBins,
+                       img, t, lane);
 }
 
 const char* const kFdafFields[GAB_FDAF_FIELDS] = {"mu", "eps"};

@@ -96,7 +96,7 @@ def _positions(ptr, n):
 
 
 class _TrackPlan(_Handle):
-    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms, fdaf) share: `tracks` channels of
+    """What the track plans (eq, mix, delay, meter, resample, dynamics, reverb, gate, crossover, limiter, spectrum, resynthesis, denoise, saturator, nlms, fdaf, mconv) share: `tracks` channels of
     `bufsize` samples a buffer behind the functions gab_<plan>_* (the prefix is `_destroy`'s)."""
 
     def _fn(self, what):
@@ -1319,6 +1319,67 @@ class FdafPlan(_TrackPlan):
                 _stream(stream))
 
     launch = _launcher("gab_fdaf_process")
+
+
+class MatrixConvPlan(_TrackPlan, _Prepared):
+    """gab_mconv_plan: `inputs` channels summed into `outputs` channels through a partitioned FIR filter per (output,
+    input): `partitions` K in 1..32 of 512 taps each; bufsize a multiple of 512.  A binaural renderer, a true-stereo
+    reverb, an array decoder.  x is [inputs*bufsize], the result [outputs*bufsize], bus-major as MixPlan writes.  A new
+    plan holds zero taps: silence.  New taps are crossfaded in over the next buffer unless ramp=False."""
+
+    _destroy = "gab_mconv_destroy"
+    BLOCK, BINS = 512, 513
+
+    def __init__(self, inputs, outputs, bufsize, partitions=1):
+        self.inputs, self.outputs, self.partitions = inputs, outputs, partitions
+        self._create(inputs, bufsize, outputs, partitions)
+
+    def set_taps(self, h, ramp=True, first_output=None, first_input=None):
+        """h: device tensor [outputs][inputs][512 partitions] of finite time-domain taps.  With first_output and / or
+        first_input (the other then starts at 0) h is a 3-d [n_out][n_in][512 partitions] for outputs [first_output,
+        first_output + n_out) x inputs [first_input, first_input + n_in).  ramp=True: the next buffer processed is the
+        blend from the old taps' output to the new taps'; ramp=False: in force from the next block."""
+        L = self.BLOCK * self.partitions
+        ramped = 1 if ramp else 0
+        if first_output is None and first_input is None:
+            if h.numel() != self.outputs * self.inputs * L:
+                raise ValueError("taps must hold [outputs][inputs][%d] values (or give first_output / first_input)" % L)
+            check(lib.gab_mconv_set_taps(self._h, _dev(h), ramped, _stream()))
+            return
+        if h.dim() != 3 or h.shape[2] != L or h.shape[0] == 0 or h.shape[1] == 0:
+            raise ValueError("the taps of a range must be [n_out][n_in][%d]" % L)
+        check(lib.gab_mconv_set_taps_range(self._h, _dev(h), first_output or 0, h.shape[0], first_input or 0, h.shape[1],
+                                           ramped, _stream()))
+
+    def reset(self):
+        """The ring, the previous block and the block count zero; the taps stay and a pending ramp is dropped."""
+        super().reset()
+
+    def process(self, x, out=None):
+        """One buffer: x [inputs*bufsize] -> [outputs*bufsize].  out must not overlap x."""
+        return self._process("process", x, out, 1, (self.outputs * self.bufsize,))
+
+    def process_batch(self, xs, out=None):
+        """Consecutive buffers [n][inputs*bufsize] -> [n][outputs*bufsize]; a pending ramp runs through the first."""
+        n = _n_buffers(self, xs)
+        return self._process("process_batch", xs, out, n, (n * self.outputs * self.bufsize,), n)
+
+    def state(self):
+        """Copies of (H_current, H_target [outputs][inputs][K][513] complex64, the taps' half-spectra; X [K + 15][inputs]
+        [513] complex64, the ring with block b in slot b mod (K + 15); prev [inputs][512], the input block before;
+        count, the blocks since the reset)."""
+        hc, ht, x, pv, c, s = (C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0))
+        check(lib.gab_mconv_state(self._h, C.byref(hc), C.byref(ht), C.byref(x), C.byref(pv), C.byref(c), C.byref(s)))
+
+        def spectra(p, *shape):
+            rows = shape[0]
+            flat = _view(p.value, rows, torch.Size(shape[1:]).numel() * 2).clone()
+            return torch.view_as_complex(flat.view(*shape, 2))
+        taps = (self.outputs, self.inputs, self.partitions, self.BINS)
+        return (spectra(hc, *taps), spectra(ht, *taps), spectra(x, s.value, self.inputs, self.BINS),
+                _view(pv.value, self.inputs, self.BLOCK).clone(), int(_positions(c.value, 1)[0]))
+
+    launch = _launcher("gab_mconv_process")
 
 
 _REVERB_SPREAD = 4.65    # reverb_params: the longest line over the shortest (21.5 ms -> 100 ms)

@@ -573,6 +573,9 @@ int gab_fdtd_copy_pressure(gab_fdtd_plan* plan, float* d_dst, gab_stream_t strea
  *                       are on the device and move with every replay.
  *                       The fdaf plan has no ramp and no host state at all: W, X, prev and count are the device's and
  *                       move with every replay, whatever is pending or set (tests/test_fdaf_gpu.py).
+ *                       The mconv plan's process and process_batch pick their launches by the same flag (a ramp buffer
+ *                       takes a second product launch, the blend and the copy): capture them with no ramp pending, and
+ *                       the ring, prev and count move with every replay (tests/test_mconv_gpu.py).
  *   mix's ramp_first   the same flag: in a captured process_batch of n buffers the first buffer of every replay is the
  *                       one that takes the ramp form.
  *   meter's decay       a launch argument: set_decay after the capture does not reach the replays.
@@ -1836,6 +1839,76 @@ int gab_fdaf_process_batch(gab_fdaf_plan* plan, const float* d_in, const float* 
                            int n_buffers, gab_stream_t stream);
 int gab_fdaf_params(gab_fdaf_plan* plan, float** d_params, size_t* n_floats);
 int gab_fdaf_state(gab_fdaf_plan* plan, float** d_W, float** d_X, float** d_prev, unsigned** d_count, int* partitions);
+
+/* ---- mconv: a matrix of partitioned FIR filters, inputs summed into outputs (additive; no counterpart) -------------
+ * What the mix plan does with a gain per (track, bus), with a filter per (output, input): a binaural renderer (sources
+ * through a head-related response per ear), a true-stereo reverb (2 x 2), an array decoder, a crosstalk canceller.  I =
+ * inputs 1..4096 (the plan's tracks, and what a refusal of the common entries calls them), O = outputs 1..64, K =
+ * partitions 1..32 of 512 taps, L = 512 K taps per (output, input), I O K <= 65 536.  B = bufsize, a positive multiple
+ * of 512: a buffer is B / 512 blocks.  d_in [n][I][B] and d_out [n][O][B] (bus-major, as the mix plan writes), float32
+ * at any 4-byte alignment; any overlap of d_out with d_in is refused.
+ *   state           H_current and H_target [O][I][K][513][2], the taps' half-spectra; X [S][I][513][2], the ring of
+ *                   input spectra, S = K + 15 slots, block b in slot b mod S; prev [I][512], the input block before;
+ *                   count, one uint32, the blocks since the reset (the ring's position is count mod S: a stream is
+ *                   reset before 2^32 blocks, 1.4 years at 48 kHz).  On the device, exposed by gab_mconv_state as the
+ *                   plan's own memory.  A new plan holds zeros everywhere: its output is all +0.  A reset zeroes X, prev
+ *                   and count, keeps the taps and makes current := target (a pending ramp is dropped).
+ *   the arithmetic  float32, every operation rounded once; the product is the fdaf section's first, acc (+)= a b.  Per
+ *                   block b = count:
+ *                     1. Inputs 2q and 2q + 1 share a forward transform as a + i b: the window [prev | x_b], no window
+ *                        product, the stages of the fdaf plan's step 1.  X[b mod S] holds, bit for bit, the row
+ *                        gab_spec_* (hop 512, complex, a window of ones) writes for that frame.  An odd last input
+ *                        stands beside zeros.
+ *                     2. The inputs fall into groups of 32 by their index, [32 g, 32 g + 32): a cut that depends on I
+ *                        alone.  For output o and bin k the group partial is
+ *                          P_g = sum of X_i[(b - p) mod S][k] H[o][i][p][k], i ascending over the group and inside it
+ *                                p ascending, one chain from acc = +0;
+ *                        then Y_o = ((P_0 + P_1) + P_2) ..., g ascending, re and im by one rounded addition each.
+ *                     3. Outputs 2r and 2r + 1 share an inverse: Y packed as the fdaf plan's step 3 packs, the inverse
+ *                        transform, y[n] = fmaf(z[512 + n], 2^-10, +0).  An odd last output stands beside a zero spectrum.
+ *                     4. prev := x_b, count += 1.
+ *   taps            set_taps (the whole table [O][I][512 K]) and set_taps_range (outputs [first_output, first_output +
+ *                   n_outputs) x inputs [first_input, first_input + n_inputs), a table [n_outputs][n_inputs][512 K]) take
+ *                   device tables of finite time-domain taps, checked on the device first: the first that is not is
+ *                   named as (output, input, tap) with GAB_ERR_INVALID_ARG and the plan keeps its taps.  Each (output,
+ *                   input, partition) is transformed alone, [h[512 p .. 512 p + 512) | 512 zeros], as the fdaf plan's
+ *                   taps are.  Synchronous with respect to `stream`; X, prev and count stay.
+ *                   ramped = 0: into both tables.  The ring holds input spectra only, so the new taps act on every
+ *                   partition from the next block, and from there on the output is bit for bit that of a plan that had
+ *                   them from the start and was fed the same stream.
+ *                   ramped = 1: into H_target only, and the next buffer processed (of a batch: its first) is the ramp
+ *                   buffer: steps 2 and 3 run against both tables and sample s of the buffer is
+ *                   fmaf(y_target[s] - y_current[s], r[s], y_current[s]), r[s] = (s + 1) / B in float64, rounded once;
+ *                   then current := target by a copy on that call's stream.  The click-free move of a source.
+ *   bad inputs      An infinity or a NaN in an input lies in two windows, so in the ring for K + 1 blocks: it is in the
+ *                   outputs for at most K + 1 blocks, and because NaN 0 is NaN in every output whatever its taps.  It
+ *                   never reaches H.  From block K + 2 on the output is bit for bit that of a stream which held a zero
+ *                   in its place.  Overflow by FINITE arithmetic is not guarded.
+ *   determinism     Output bits depend on the samples, the taps and the state.  Not on B, on the cut into calls or
+ *                   batches, on alignment, or on which plan holds an output pair: a plan that holds outputs [2r, 2r + n)
+ *                   of the table gives those outputs' bits.
+ *   calls           A call is rounds of at most 16 blocks, three launches a round on `stream` (the forward transforms; the
+ *                   group partials into the plan's own scratch, no atomics; the sums and the inverses) and a fourth on
+ *                   the blocks of a ramp buffer.  The ring has the slots for a round.  process_batch gives the bits of
+ *                   n process calls.
+ * process and process_batch allocate nothing and wait for nothing, and all changing state is on the device: they can be
+ * captured ("Captured calls", above).  Arguments are checked before any device call, each refusal with its own text:
+ * inputs (as tracks) and bufsize >= 1, inputs <= 4096, outputs in 1..64, partitions in 1..32, the product of the three,
+ * bufsize a multiple of 512, null pointers, n_buffers >= 1, n_buffers * bufsize below 2^31 - 1024, the input (track)
+ * range and the output range of a set, the overlap.  Out of scope: sparse tables, other transform sizes, buffers below
+ * 512, non-uniform partitions, taps interpolated from a set, a taps getter, the gpubench driver, tests/walks.py, the
+ * strip helpers.  One thread at a time per plan.                                                                      */
+typedef struct gab_mconv_plan gab_mconv_plan;
+int gab_mconv_create(gab_mconv_plan** plan, int inputs, int bufsize, int outputs, int partitions);
+int gab_mconv_destroy(gab_mconv_plan* plan);
+int gab_mconv_set_taps(gab_mconv_plan* plan, const float* d_taps, int ramped, gab_stream_t stream);
+int gab_mconv_set_taps_range(gab_mconv_plan* plan, const float* d_taps, int first_output, int n_outputs, int first_input,
+                             int n_inputs, int ramped, gab_stream_t stream);
+int gab_mconv_reset(gab_mconv_plan* plan, gab_stream_t stream);
+int gab_mconv_process(gab_mconv_plan* plan, const float* d_in, float* d_out, gab_stream_t stream);
+int gab_mconv_process_batch(gab_mconv_plan* plan, const float* d_in, float* d_out, int n_buffers, gab_stream_t stream);
+int gab_mconv_state(gab_mconv_plan* plan, float** d_H_current, float** d_H_target, float** d_X, float** d_prev,
+                    unsigned** d_count, int* slots);
 
 /* ===================================================================== */
 /* G. host-side data generators of the harness                           */
